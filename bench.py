@@ -15,9 +15,14 @@ Under a launcher, --gpus must equal WORLD_SIZE.
 One process per GPU; N > 1 is batch data parallelism (weak scaling): each rank
 runs its own batch, the valid-voxel count is all-reduced before the loss so
 the CE mean is the global one, and the flat gradient is all-reduced (RCCL).
-Rank 0 prints one JSON line.  The CPU baseline (rank 0, N=1) times the CPU
-oracle (oracle/spff_oracle.py, PyTorch-CPU restatement of the reference path)
-on the same batch on the host cores (all physical cores the process is allotted).
+Rank 0 prints one JSON line.  A plain run sets up, warms up, times the K steps
+and prints the line (metric, value, ms_per_step, ...).  --full adds everything
+that takes runs of its own: the eager loop beside the HIP-graph replays, the
+per-class kernel timing pass with the roofline, the loss-pass timing and the
+CPU baseline (rank 0, N=1), which times the CPU oracle (oracle/spff_oracle.py,
+PyTorch-CPU restatement of the reference path) on the same batch on the host
+cores (all physical cores the process is allotted).  --dump-outputs DIR writes
+what the last timed step returned as DIR/<name>.npy.
 """
 from __future__ import annotations
 
@@ -294,11 +299,13 @@ def bench_unet3d(args, world, rank, device):
     sync_batchnorm(m)  # (world 1: nothing to synchronise)
     x, y = synthetic_batch(Bt, 1, D0, HW, HW, K, ignore_frac=0.01, seed=1000 + rank, device=device)
     params = list(m.parameters())
+    last = {}
 
     def step():
         for q in params:
             q.grad = None
         logits = m(x)
+        last["logits"] = logits.detach()
         cnt = global_valid_count(y, 255) if world > 1 else None
         from innovative3D.models import _WeightedCE
         loss, _conf = _WeightedCE.apply(logits, y, K, 255, None) if cnt is None else \
@@ -341,6 +348,8 @@ def bench_unet3d(args, world, rank, device):
     elapsed = time.perf_counter() - t0
     cprof = E.conv_prof_collect()
     E.conv_prof_enable(False)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, step_outputs(loss, None, last["logits"], params))
     ranks = rank_report(elapsed, args.steps, device) if world > 1 else None
     t = torch.tensor([elapsed], dtype=torch.float64, device=device)
     if world > 1:
@@ -373,7 +382,7 @@ def bench_unet3d(args, world, rank, device):
     }
     if ranks:
         out["ranks"] = ranks
-    if rank == 0 and world == 1 and args.cpu_baseline == "auto":
+    if args.full and rank == 0 and world == 1 and args.cpu_baseline == "auto":
         out["cpu_baseline"] = cpu_baseline_unet3d(st, K, args.cpu_steps)
         out["gpu_over_cpu"] = value / out["cpu_baseline"]["value"]
     if rank == 0:
@@ -485,11 +494,13 @@ def bench_swin(args, world, rank, device):
     lit.model.model.math = args.math
     x, y = synthetic_batch(Bt, 1, S_, S_, S_, K, ignore_frac=0.01, seed=1000 + rank, device=device)
     params = list(lit.parameters())
+    last = {}
 
     def step():
         for q in params:
             q.grad = None
         logits = lit(x)
+        last["logits"] = logits.detach()
         loss = M._SwinLoss.apply(logits, y, K, 255, False, 0.5)
         loss.backward()
         if world > 1:  # DDP semantics (the reference trains it under Lightning DDP): mean
@@ -515,6 +526,8 @@ def bench_swin(args, world, rank, device):
     elapsed = time.perf_counter() - t0
     cprof = E.conv_prof_collect()
     E.conv_prof_enable(False)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, step_outputs(loss, None, last["logits"], params))
     ranks = rank_report(elapsed, args.steps, device) if world > 1 else None
     t = torch.tensor([elapsed], dtype=torch.float64, device=device)
     if world > 1:
@@ -545,7 +558,7 @@ def bench_swin(args, world, rank, device):
     }
     if ranks:
         out["ranks"] = ranks
-    if rank == 0 and world == 1 and args.cpu_baseline == "auto":
+    if args.full and rank == 0 and world == 1 and args.cpu_baseline == "auto":
         out["cpu_baseline"] = cpu_baseline_swin(st, K, args.cpu_steps)
         out["gpu_over_cpu"] = value / out["cpu_baseline"]["value"]
     if rank == 0:
@@ -617,6 +630,45 @@ def rank_report(elapsed_local, steps, device):
     dist.all_gather(ts, t)
     return {"world_size": dist.get_world_size(), "backend": str(dist.get_backend()),
             "ms_per_step_by_rank": [float(v.item()) / steps * 1e3 for v in ts]}
+
+
+DUMP_BUDGET_BYTES = 60 * 1000 * 1000   # array data; the files with their headers stay below 64 MB
+
+
+def step_outputs(loss, conf, logits, params):
+    """What a caller of the timed step holds after it: the loss, the confusion matrix (SPFF
+    workloads), the logits and the parameter gradients (one flat array, parameter order)."""
+    arrays = {"loss": loss.reshape(1), "logits": logits,
+              "grads": torch.cat([p.grad.reshape(-1) for p in params if p.grad is not None])}
+    if conf is not None:
+        arrays["conf"] = conf
+    return arrays
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: write {name: tensor} as DIR/<name>.npy (float32; float64 for integer
+    and double tensors), DUMP_BUDGET_BYTES in all.  The budget is handed out smallest array
+    first; an array above its share is written as a 1-D sample of its flattened elements at
+    sorted indices drawn with a seed fixed by its name, so two builds write the same
+    elements."""
+    import zlib
+    import numpy as np
+    out = pathlib.Path(dirname)
+    out.mkdir(parents=True, exist_ok=True)
+    left = DUMP_BUDGET_BYTES
+    items = sorted(arrays.items(), key=lambda kv: kv[1].numel())
+    for i, (name, t) in enumerate(items):
+        t = t.detach()
+        wide = t.dtype in (torch.float64, torch.int64, torch.int32)
+        esize = 8 if wide else 4
+        cap = left // (len(items) - i) // esize
+        if t.numel() > cap:
+            g = torch.Generator().manual_seed(zlib.crc32(name.encode()))
+            idx = torch.randint(0, t.numel(), (cap,), generator=g).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        a = t.to(torch.float64 if wide else torch.float32).cpu().numpy()
+        left -= a.nbytes
+        np.save(out / f"{name}.npy", a)
 
 
 def _free_port():
@@ -714,6 +766,16 @@ def main():
     ap.add_argument("--pmc", default=str(ROOT / "profiles" / "r06_pmc_conv.json"),
                     help="per-launch HBM traffic summary from rocprofv3 --pmc "
                          "(scripts/pmc_traffic.py); used only when its workload key matches")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure: the eager loop next to the "
+                         "HIP-graph replays, the per-class kernel timing pass and the roofline "
+                         "built from it, the loss-pass timing and the CPU baseline.  Without it "
+                         "the run sets up, warms up, times the steps and prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step returned (loss, "
+                         "confusion matrix, logits, parameter gradients) as DIR/<name>.npy, "
+                         "float32 / float64; an array above its share of 64 MB is written as a "
+                         "fixed seeded sample of its elements")
     args = ap.parse_args()
 
     if "WORLD_SIZE" not in os.environ:
@@ -807,8 +869,10 @@ def main():
         runner = DataParallelSPFF(core, K, 255)
         vox_step = B * S * S * S
 
+    last = {}
+
     def step():
-        loss, _conf = runner.step(x, y)
+        loss, last["conf"] = runner.step(x, y)
         return loss
 
     for _ in range(args.warmup):
@@ -832,18 +896,24 @@ def main():
     # 1. the timed region: K steps with nothing but the step's own launches in it (the
     #    per-class HIP events of 2. add a queue packet before and after every profiled launch,
     #    ~1 ms per step of gaps: measured separately, never inside the timed region)
-    elapsed, loss = timed(step, args.steps)
+    #    With the HIP graph the replays are the headline; the eager loop of the same K steps
+    #    is timed beside them under --full only (and whenever the replays cannot be used).
+    eager = loss = None
+    if args.full or not use_graph:
+        eager, loss = timed(step, args.steps)
+        elapsed = eager
     graph_rec = None
     if use_graph:
         # the step captured once into a HIP graph (torch.cuda.CUDAGraph over the engine's
         # launches: no host syncs, static shapes, the plan's workspace fixed) and replayed:
         # the same kernels, without the host round trips between them
-        eager = elapsed
+        eager_ms = eager / args.steps * 1e3 if eager is not None else None
+        graph_ok = False
         try:
             side = torch.cuda.Stream(device)
             side.wait_stream(torch.cuda.current_stream(device))
             with torch.cuda.stream(side):
-                step()
+                loss = step()
             torch.cuda.current_stream(device).wait_stream(side)
             torch.cuda.synchronize()
             g = torch.cuda.CUDAGraph()
@@ -856,24 +926,103 @@ def main():
             # step's loss bit for bit (tests/test_gpu_graph.py); anything else means the
             # capture missed work, and the eager time stands
             same = float(gloss) == float(loss)
-            graph_rec = {"eager_ms_per_step": eager / args.steps * 1e3,
+            graph_rec = {"eager_ms_per_step": eager_ms,
                          "graph_ms_per_step": g_elapsed / args.steps * 1e3,
                          "replay_loss_equals_eager": same,
                          "note": ("value = the graph replays" if same else
                                   "value = the EAGER loop: the replay's loss differed") +
-                                 "; both loops without profiling events"}
+                                 "; both loops without profiling events" +
+                                 ("" if eager_ms is not None or not same else
+                                  "; the eager loop is timed with --full")}
             if same:
-                elapsed, loss = g_elapsed, gloss
+                elapsed, loss, graph_ok = g_elapsed, gloss, True
             else:
                 print(f"bench.py: HIP-graph replay loss {float(gloss)!r} != eager {float(loss)!r}; "
                       "reporting the eager time", file=sys.stderr, flush=True)
         except RuntimeError as e:
-            # a capture the runtime refuses: the eager loop above stands (and says why)
+            # a capture the runtime refuses: the eager loop stands (and says why)
             torch.cuda.synchronize()
-            graph_rec = {"eager_ms_per_step": eager / args.steps * 1e3, "error": repr(e)[:300],
+            graph_rec = {"eager_ms_per_step": eager_ms, "error": repr(e)[:300],
                          "note": "value = the EAGER loop: the HIP-graph capture failed"}
             print(f"bench.py: HIP-graph capture failed ({e!r}); reporting the eager time",
                   file=sys.stderr, flush=True)
+        if not graph_ok:
+            # the eager loop is the headline after all: time it now, so that its last step is
+            # also the one --dump-outputs writes
+            elapsed, loss = timed(step, args.steps)
+            graph_rec["eager_ms_per_step"] = elapsed / args.steps * 1e3
+    if args.dump_outputs and rank == 0:
+        # the last timed step's results: a replay leaves them in the tensors of the capture
+        dump_outputs(args.dump_outputs,
+                     step_outputs(loss, last["conf"], runner.last_logits, runner.params))
+
+    elapsed_local = elapsed
+    t = torch.tensor([elapsed], dtype=torch.float64, device=device)
+    if world > 1:
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+    elapsed = float(t.item())
+    value = world * vox_step * args.steps / elapsed
+    if registry:
+        shape = [B, 1, 5, HW, HW]
+    elif sharded:
+        shape = [1, args.in_ch, Dl * world, HW, HW]
+    else:
+        shape = [B, args.in_ch, S, S, S]
+    wkey = {"workload": args.workload, "shape": shape, "classes": K, "base": args.base,
+            "math": args.math, "n_gpus": world, "memory_layout": plan.layout}
+    if registry:
+        cfg = {"workload": f"SPFF-UNet fwd+ce_plus_macro_dice+bwd, batch {B} x 1ch x 5 x {HW} x "
+                           f"{HW} (registry layout) height-sharded into {world} x {Hl}-row slabs, "
+                           f"K={K}, base {args.base}",
+               "global_batch": B, "shape": [B, 1, 5, HW, HW], "parallelism": f"height{world}"}
+        metric = f"voxels/sec fwd+bwd, SPFF-UNet registry layout {B}x1x5x{HW}x{HW}, " \
+                 "height-sharded over N GPUs (strong scaling)"
+    elif sharded:
+        cfg = {"workload": f"SPFF-UNet fwd+ce_plus_macro_dice+bwd, one 1 x {args.in_ch}ch x "
+                           f"{Dl * world} x {HW} x {HW} volume depth-sharded into {world} x "
+                           f"{Dl}-slice slabs (BASELINE configs[3] at 8 GPUs), K={K}, base {args.base}",
+               "global_batch": 1, "shape": [1, args.in_ch, Dl * world, HW, HW],
+               "parallelism": f"depth{world}", "memory_layout": plan.layout,
+               "workspace_GiB": plan.ws_bytes / 2 ** 30}
+        metric = ("voxels/sec fwd+bwd, SPFF-UNet 5-ch volume depth-sharded (512^3 at 8 GPUs)"
+                  if not args.strong else
+                  f"voxels/sec fwd+bwd, SPFF-UNet one 5x{args.volume_depth}x{HW}x{HW} volume, "
+                  f"depth-sharded over N GPUs (strong scaling)")
+    else:
+        cfg = {"workload": f"SPFF-UNet fwd+ce_plus_macro_dice+bwd, batch {B} x {args.in_ch}ch x "
+                           f"{S}^3 per GPU, K={K}, base {args.base}",
+               "global_batch": B * world, "shape": [B, args.in_ch, S, S, S],
+               "parallelism": f"dp{world}"}
+        metric = "voxels/sec fwd+bwd, SPFF-UNet 5-ch 128^3 patch"
+    # the result line of a plain run; --full fills in the roofline, the profiled pass, the
+    # collectives' timing and the CPU baseline below
+    out = {
+        "metric": metric,
+        "value": value, "unit": "voxels/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True,
+        "scaling": "strong" if ((sharded and args.strong) or registry) else "weak",
+        "vs_baseline": None,
+        "dtype": "f32", "conv_math": args.math,
+        "conv_math_accuracy": CONV_MATH_ACCURACY.get(args.math),
+        "data": "synthetic (x~N(0,1), labels U[0,K) with 1% ignore=255; weights from weightgen seed 0)",
+        "config": cfg,
+        "workload_key": wkey,
+        "loss": float(loss.item()),
+        "roofline": None,
+        "cpu_baseline": None,
+        "build": build_record(),
+        "full": bool(args.full),
+    }
+    if graph_rec:
+        out["hip_graph"] = graph_rec
+    if world > 1:
+        out["ranks"] = rank_report(elapsed_local, args.steps, device)
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return
 
     # 2. per-class kernel timing: a separate pass of K eager steps with HIP events around the
     #    engine's launches on its stream (and, sharded, around the collective callbacks)
@@ -886,12 +1035,6 @@ def main():
     plan.prof_enable(False)
     coll = plan.coll_collect() if plan.coll_timing else {}
     plan.coll_timing = False
-    elapsed_local = elapsed
-    t = torch.tensor([elapsed], dtype=torch.float64, device=device)
-    if world > 1:
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-    elapsed = float(t.item())
-    value = world * vox_step * args.steps / elapsed
 
     # dominant kernel: the fwd/dgrad conv kernel (forward + input-grad convs), timed live
     ms = prof["conv_fwd"][0] + prof["conv_dgrad"][0]
@@ -901,14 +1044,6 @@ def main():
     achieved = fl / (ms * 1e-3) / 1e12 if ms > 0 else None
     # roofline.traffic: the PMC measurement is used only for the workload it was taken on
     # (scripts/pmc_traffic.py stores the bench line's workload_key); otherwise null
-    if registry:
-        shape = [B, 1, 5, HW, HW]
-    elif sharded:
-        shape = [1, args.in_ch, Dl * world, HW, HW]
-    else:
-        shape = [B, args.in_ch, S, S, S]
-    wkey = {"workload": args.workload, "shape": shape, "classes": K, "base": args.base,
-            "math": args.math, "n_gpus": world, "memory_layout": plan.layout}
     traffic, traffic_src = None, {"file": None, "matched": False}
     try:
         pm = json.loads(pathlib.Path(args.pmc).read_text())
@@ -970,51 +1105,9 @@ def main():
                  "(8*C B/voxel); in_bwd_apply = IN backward apply (12*C B/voxel); HIP events "
                  "on the engine stream; loss = k_loss + finaliser (K*4 + 8 + K*4 B/voxel), not "
                  "in the aggregate")}
-    if registry:
-        cfg = {"workload": f"SPFF-UNet fwd+ce_plus_macro_dice+bwd, batch {B} x 1ch x 5 x {HW} x "
-                           f"{HW} (registry layout) height-sharded into {world} x {Hl}-row slabs, "
-                           f"K={K}, base {args.base}",
-               "global_batch": B, "shape": [B, 1, 5, HW, HW], "parallelism": f"height{world}"}
-        metric = f"voxels/sec fwd+bwd, SPFF-UNet registry layout {B}x1x5x{HW}x{HW}, " \
-                 "height-sharded over N GPUs (strong scaling)"
-    elif sharded:
-        cfg = {"workload": f"SPFF-UNet fwd+ce_plus_macro_dice+bwd, one 1 x {args.in_ch}ch x "
-                           f"{Dl * world} x {HW} x {HW} volume depth-sharded into {world} x "
-                           f"{Dl}-slice slabs (BASELINE configs[3] at 8 GPUs), K={K}, base {args.base}",
-               "global_batch": 1, "shape": [1, args.in_ch, Dl * world, HW, HW],
-               "parallelism": f"depth{world}", "memory_layout": plan.layout,
-               "workspace_GiB": plan.ws_bytes / 2 ** 30}
-        metric = ("voxels/sec fwd+bwd, SPFF-UNet 5-ch volume depth-sharded (512^3 at 8 GPUs)"
-                  if not args.strong else
-                  f"voxels/sec fwd+bwd, SPFF-UNet one 5x{args.volume_depth}x{HW}x{HW} volume, "
-                  f"depth-sharded over N GPUs (strong scaling)")
-    else:
-        cfg = {"workload": f"SPFF-UNet fwd+ce_plus_macro_dice+bwd, batch {B} x {args.in_ch}ch x "
-                           f"{S}^3 per GPU, K={K}, base {args.base}",
-               "global_batch": B * world, "shape": [B, args.in_ch, S, S, S],
-               "parallelism": f"dp{world}"}
-        metric = "voxels/sec fwd+bwd, SPFF-UNet 5-ch 128^3 patch"
-    out = {
-        "metric": metric,
-        "value": value, "unit": "voxels/s", "n_gpus": world, "steps": args.steps,
-        "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True,
-        "scaling": "strong" if ((sharded and args.strong) or registry) else "weak",
-        "vs_baseline": None,
-        "dtype": "f32", "conv_math": args.math,
-        "conv_math_accuracy": CONV_MATH_ACCURACY.get(args.math),
-        "data": "synthetic (x~N(0,1), labels U[0,K) with 1% ignore=255; weights from weightgen seed 0)",
-        "config": cfg,
-        "workload_key": wkey,
-        "loss": float(loss.item()),
-        "roofline": roof,
-        "cpu_baseline": None,
-        "build": build_record(),
-    }
-    if graph_rec:
-        out["hip_graph"] = graph_rec
+    out["roofline"] = roof
     out["profiled_pass_ms_per_step"] = prof_elapsed / args.steps * 1e3
     if world > 1:
-        out["ranks"] = rank_report(elapsed_local, args.steps, device)
         bk = getattr(runner, "bucketer", None)
         out["collectives"] = {
             "per_step": {k: {"calls": v["calls"] / args.steps, "ms": v["ms"] / args.steps,

@@ -1,11 +1,12 @@
 #!/usr/bin/env python3
 """Summarise scripts/ab_bench.sh output: per library, ms/step of every round and the mean
-per-class ms/step (roofline.per_class_ms_per_step) -- gpurun_out/ab_<i>.jsonl."""
+per-class ms/step (roofline.per_class_ms_per_step of bench.py --full) -- $OUT/ab_<i>.jsonl
+(default bench_out/)."""
 import glob
 import json
 import sys
 
-for f in sorted(glob.glob(sys.argv[1] if len(sys.argv) > 1 else "gpurun_out/ab_[0-9]*.jsonl")):
+for f in sorted(glob.glob(sys.argv[1] if len(sys.argv) > 1 else "bench_out/ab_[0-9]*.jsonl")):
     rows = [json.loads(line) for line in open(f) if line.strip()]
     ms = [r["ms_per_step"] for r in rows]
     pc = {}

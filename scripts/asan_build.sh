@@ -26,10 +26,10 @@ for src in "$PKG"/csrc/*.hip; do
 done
 for p in "${pids[@]}"; do wait "$p"; done
 # the driver is plain host C++ (no HIP): amdclang++, then one hipcc link of everything
-/opt/rocm/llvm/bin/clang++ -O1 -g -std=c++17 -I"$ROOT/include" -fsanitize=address,undefined \
+/opt/rocm/llvm/bin/clang++ -O1 -g -std=c++17 -I"$ROOT/include" -fsanitize=address,undefined -fno-gpu-sanitize \
   -fno-sanitize-recover=undefined -fno-omit-frame-pointer -c "$ROOT/scripts/asan_plans.cpp" \
   -o "$OUT/asan_plans.main.o"
-$HIPCC -fsanitize=address,undefined --offload-arch=gfx950 "$OUT"/*.o -o "$OUT/asan_plans"
+$HIPCC -Xarch_host -fsanitize=address -Xarch_host -fsanitize=undefined --offload-arch=gfx950 "$OUT"/*.o -o "$OUT/asan_plans"
 echo "built $OUT/asan_plans"
 if [ "${1:-}" = "--run" ]; then
   ASAN_OPTIONS="${ASAN_OPTIONS:-detect_leaks=1:abort_on_error=0:halt_on_error=1}" \

@@ -12,9 +12,9 @@ rm -rf $O && mkdir -p $O
 run() { echo "[measure] $1"; }
 # (the profiler passes run the eager step: the same kernels as the graph replays the bench
 # line times, each launch visible to the kernel trace and the counter collection)
-PARGS="${BENCH_ARGS:-} --graph off"
+PARGS="${BENCH_ARGS:-} --graph off --full"
 run bench
-timeout -k 10 400 python bench.py ${BENCH_ARGS:-} > $O/bench.log 2>&1 || { echo "bench rc=$?"; exit 1; }
+timeout -k 10 400 python bench.py --full ${BENCH_ARGS:-} > $O/bench.log 2>&1 || { echo "bench rc=$?"; exit 1; }
 run prof
 timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/prof -o run --output-format csv -- python3 bench.py --steps 3 --warmup 1 --cpu-baseline skip ${PARGS} > $O/prof.log 2>&1 || { echo "prof rc=$?"; exit 1; }
 if [ "${M3_KBENCH:-1}" = 1 ]; then
