@@ -46,7 +46,9 @@ extern "C" {
  *   SPFF_MATH_F16X3   each operand scaled by a power of two (max |x| 2^e < 2^14, from an
  *                     on-device absmax) and split into 2 fp16 planes, 3 products on the
  *                     fp16 MFMA: <= 2^-22 |x| per operand, dropped l*l <= 2^-22 |xy|,
- *                     at the bf16x3 rate (the 1x1x1 / ConvTranspose GEMMs keep bf16x6) */
+ *                     at the bf16x3 rate (the ConvTranspose and head GEMMs follow the conv
+ *                     arithmetic: scaled fp16 planes too; the bias-free 1x1x1 convs and
+ *                     nn.Linear layers of the SwinUNETR / R2UNet3D plans run the fp32 MFMA) */
 /* largest num_classes of the SPFF / 3DUNet plans and of spff_loss / spff_confusion
  * (the SwinUNETR plan's soft-Dice loss: 32) */
 #define SPFF_MAX_CLASSES 128
@@ -302,6 +304,63 @@ int spff_loss_ex(const float* logits, const int64_t* labels, int64_t nvox, int n
                  int ignore_index, double smooth, const int64_t* count_override,
                  const float* class_weights, int clamp_denominator, float* out4,
                  float* dlogits, int64_t* conf, void* ws, void* stream);
+
+/* ---------------------------------------------------------------------------
+ * R2UNet3D variant (registry entry "R2UNet3D"): LitR2UNet3D_Published around
+ * R2UNet3D_backbone, the recurrent residual 3D U-Net.  Block(cin -> C, t):
+ *   x1 = inp(x) (1x1x1, no bias);
+ *   r_k = relu(IN(conv3x3x3(r_{k-1} + h_{k-1}))), r_0 = x1, h_0 = 0, h_k = r_k, k = 1..t,
+ *         one conv and one affine InstanceNorm3d shared by the t steps;
+ *   o = relu(IN(x1 + out(r_t))) (out: 1x1x1, no bias).
+ * Five levels (channels base << l) with MaxPool3d(2) down, ConvTranspose3d(2, stride 2)
+ * + concat [up, skip] up, and the wrapper's 1x1x1 head with bias.  InstanceNorm uses the
+ * instance statistics in training and evaluation alike, so forward has no mode.
+ * Parameters: one flat fp32 buffer in the Lit module's state-dict order and names
+ * ("backbone.e1.inp.weight", "backbone.e1.ru.conv.weight", "backbone.e1.ru.inn.weight",
+ * ... "backbone.d1.bn.bias", "head.weight", "head.bias": 73 entries).  D, H and W must be
+ * multiples of 16 (the wrapper's replicate padding and centre crop stay with the caller).
+ * Saved tensors (spff_r2u_saved_tensor), for <blk> in e1..e4, b, d4..d1: "<blk>.x1",
+ * "<blk>.ru<k>" (k = 1..t: step k's activation as stored, i.e. the ReLU output for k = t
+ * and twice it -- the next step's conv input r + h -- for k < t) and "<blk>.out".
+ * -------------------------------------------------------------------------- */
+typedef struct spff_r2u_cfg {
+  int batch, in_ch, depth, height, width;  /* input [B][Cin][D][H][W], Cin 1..8 */
+  int num_classes;   /* K, 2..32 (K = 1, the sigmoid branch, is not built) */
+  int base;          /* a multiple of 8; the registry uses 16 */
+  int t;             /* recurrence steps, 1..8; the registry uses 2 */
+  int math;          /* SPFF_MATH_* for the 3x3x3 convolutions */
+  int reserved[7];   /* zero */
+} spff_r2u_cfg;
+
+typedef struct spff_r2u spff_r2u;
+
+int spff_r2u_create(const spff_r2u_cfg* cfg, spff_r2u** out);
+void spff_r2u_destroy(spff_r2u* net);
+int spff_r2u_num_params(const spff_r2u* net);
+int spff_r2u_param_info(const spff_r2u* net, int i, const char** name, int* ndim,
+                        int64_t shape[5], int64_t* offset, int64_t* numel);
+int64_t spff_r2u_param_floats(const spff_r2u* net);
+size_t spff_r2u_workspace_bytes(const spff_r2u* net);
+/* forward: x [B][Cin][D][H][W] -> logits [B][D][H][W][K] (channel-last) */
+int spff_r2u_forward(spff_r2u* net, const float* x, const float* params, float* logits,
+                     void* workspace, void* stream);
+/* backward of the last forward: dlogits [B][D][H][W][K] -> dparams (every entry written;
+ * the shared conv / InstanceNorm gradients are summed over the steps t .. 1 in that order) */
+int spff_r2u_backward(spff_r2u* net, const float* dlogits, const float* params, float* dparams,
+                      void* workspace, void* stream);
+int spff_r2u_saved_tensor(const spff_r2u* net, void* workspace, const char* name,
+                          const float** ptr, int64_t* nvox, int* channels);
+/* LitR2UNet3D_Published._dice_only_loss_with_logits, multi-class branch: p = softmax(logits)
+ * and the one-hot labels, both masked by [y != ignore_index] (use_ignore = 0: no mask);
+ * classes k >= 1 only; a sample counts iff it has a valid voxel with label >= 1; per kept
+ * sample and class dice = (2 sum p g + 1e-6) / (sum p + sum g + 1e-6); loss = 1 - mean.
+ * out4 = [dice_mean, loss, kept_samples, N_valid]; no sample kept: loss = dice = 0 and
+ * dlogits = 0.  logits / dlogits [B][vox_per_sample][K] channel-last rows.
+ * ws >= spff_r2u_dice_loss_ws_bytes device bytes. */
+size_t spff_r2u_dice_loss_ws_bytes(int batch, int num_classes);
+int spff_r2u_dice_loss(const float* logits, const int64_t* labels, int batch,
+                       int64_t vox_per_sample, int num_classes, int use_ignore, int ignore_index,
+                       float* out4, float* dlogits, void* ws, void* stream);
 
 /* ------------------------------------------------------------------------
  * SwinUNETR variant (BASELINE config 5; registry "SwinUNETR", config.py:366-386

@@ -1,0 +1,654 @@
+// R2UNet3D variant: the recurrent residual 3D U-Net behind the registry entry
+// "R2UNet3D" (LitR2UNet3D_Published around R2UNet3D_backbone).
+//
+// Graph, levels l = 0..4 halve D, H, W (MaxPool3d(2)), channels C_l = base << l:
+//   e1 = blk(x); e2 = blk(pool(e1)); e3 = blk(pool(e2)); e4 = blk(pool(e3)); b = blk(pool(e4))
+//   d4 = blk([up4(b) | e4]); d3 = blk([up3(d4) | e3]); d2 = blk([up2(d3) | e2])
+//   d1 = blk([up1(d2) | e1]); logits = head(d1)          (head: 1x1x1 conv + bias)
+// Block(cin -> C, t):
+//   x1 = inp(x)                                  1x1x1, no bias
+//   r_0 = x1, h_0 = 0;  r_k = relu(IN_ru(conv(r_{k-1} + h_{k-1}))), h_k = r_k,  k = 1..t
+//   s  = x1 + out(r_t)                           1x1x1, no bias, residual operand of the GEMM
+//   o  = relu(IN_bn(s))
+// conv (3x3x3, no bias) and IN_ru (affine) are shared by the t steps.
+//
+// The doubling fold.  Step 1 convolves x1; every later step convolves r + h = 2 r_{k-1}.
+// relu(2 z) = 2 relu(z) exactly in fp32, so a step k < t is normalised with the doubled
+// affine (2 gamma, 2 beta) -- its coefficients come out as (2 al, 2 de), bitwise -- and its
+// activation pass writes a_k = 2 r_k, the next conv's input, directly: no pass for r + h, no
+// second tensor.  Step t uses (gamma, beta) and writes a_t = r_t.  In the backward a step
+// k < t is then an InstanceNorm with affine (2 gamma, 2 beta): its dgamma / dbeta are
+// doubled as they are accumulated, and its conv weight gradient needs no factor (its input
+// a_{k-1} already carries it).
+//
+// Accumulation order.  The shared conv weight and IN_ru affine receive t contributions.
+// Step t writes the gradient, steps t-1 .. 1 go to a scratch tensor and are added in that
+// order by k_r2u_acc on the plan's stream: one fixed order, bitwise repeatable.
+//
+// Everything else runs on the engine's kernels: conv3d_run / conv3d_wgrad (any
+// SPFF_MATH_*), slab_reduce + in_mean / in_rstd per (b, c) (InstanceNorm, eps 1e-5, biased
+// variance), act_apply / in_bwd_apply with ReLU's zero slope, linear_* for the bias-free
+// 1x1x1 convs (two-source [up | skip] views, residual operand), maxpool3_*, the 2x2x2
+// upconv_* GEMMs and head_*.  Level 0's inp has in_ch (1..8) input channels: it runs on the
+// same GEMM through the input's zero-padded 8-channel rows (x_cl) and a weight image whose
+// rows past in_ch are zero; no dedicated kernel.
+// Saved for backward per block: x1, y_k (raw conv outputs), a_k, s, o, the statistics and
+// the pool argmax bytes.
+#include "spff_internal.h"
+#include "swin_internal.h"
+#include "spff.h"
+
+#include <algorithm>
+#include <string>
+#include <vector>
+
+using namespace spff;
+
+namespace {
+
+int rfail(int code, const std::string& m) { return set_error(code, m.c_str()); }
+#define RHIPCK(expr)                                                                       \
+  do {                                                                                     \
+    hipError_t _e = (expr);                                                                \
+    if (_e != hipSuccess)                                                                  \
+      return rfail(SPFF_EHIP, std::string(#expr) + " -> " + hipGetErrorString(_e));        \
+  } while (0)
+#define RCK(expr)                   \
+  do {                              \
+    int _r = (expr);                \
+    if (_r != SPFF_OK) return _r;   \
+  } while (0)
+
+constexpr int NLVL = 5, NBLK = 9, NUP = 4, NSUB = 8, TMAX = 8;
+
+struct REnt {
+  std::string name;
+  std::vector<int64_t> shape;
+  int64_t off, numel;
+};
+
+struct RStat {
+  size_t mean, rstd, al, de;
+};
+
+struct RBlk {
+  std::string name;
+  int lvl, Cin, C;
+  int64_t w_inp = -1, w_ru = -1, g_ru = -1, b_ru = -1, w_out = -1, g_bn = -1, b_bn = -1;
+  size_t x1, y[TMAX], a[TMAX], s, o;
+  RStat st[TMAX], bn;
+  size_t gb2 = 0;            // [2][C]: 2 gamma_ru, 2 beta_ru (t > 1)
+  size_t pk_inp, pk_out;     // head_pack images of the two 1x1x1 convs
+  size_t pk[2] = {0, 0};     // batched conv images: forward, input gradient
+};
+
+struct RUp {
+  int Cin, Cout, lvl_low;
+  int64_t w, b;
+  size_t pk, out;
+};
+
+// dst[i] += scale * src[i]: the fixed-order accumulation of a shared parameter's
+// per-step gradients (scale 2 for the doubled IN affine of a step k < t) and the sum of
+// the two x1 gradients.  HBM-bound elementwise pass, float4 body + scalar tail.
+__global__ __launch_bounds__(256) void k_r2u_acc(float* __restrict__ dst,
+                                                 const float* __restrict__ src, int64_t n,
+                                                 float scale, int vec) {
+  const int64_t n4 = vec ? n >> 2 : 0;  // vec: both operands 16-byte aligned
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  const int64_t i0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  float4* d4 = reinterpret_cast<float4*>(dst);
+  const float4* s4 = reinterpret_cast<const float4*>(src);
+  for (int64_t i = i0; i < n4; i += stride) {
+    float4 d = d4[i];
+    const float4 v = s4[i];
+    d.x += scale * v.x; d.y += scale * v.y; d.z += scale * v.z; d.w += scale * v.w;
+    d4[i] = d;
+  }
+  for (int64_t i = 4 * n4 + i0; i < n; i += stride) dst[i] += scale * src[i];
+}
+
+// gb2 = [2 gamma | 2 beta]: the affine of the recurrence's steps k < t
+__global__ void k_r2u_double(const float* __restrict__ gamma, const float* __restrict__ beta,
+                             float* __restrict__ gb2, int C) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c < C) {
+    gb2[c] = 2.f * gamma[c];
+    gb2[C + c] = 2.f * beta[c];
+  }
+}
+
+hipError_t r2u_acc(float* dst, const float* src, int64_t n, float scale, hipStream_t s) {
+  // (workspace slots are 256-byte aligned and, with base % 8 == 0, the offsets of the
+  //  accumulated parameters are multiples of 4 floats: the float4 body is the usual path)
+  const int vec = !((reinterpret_cast<uintptr_t>(dst) | reinterpret_cast<uintptr_t>(src)) & 15);
+  const int64_t work = vec ? (n + 3) / 4 : n;
+  const unsigned grid = (unsigned)std::min<int64_t>((work + 255) / 256, 4096);
+  hipLaunchKernelGGL(k_r2u_acc, dim3(std::max(grid, 1u)), dim3(256), 0, s, dst, src, n, scale,
+                     vec);
+  return hipGetLastError();
+}
+
+}  // namespace
+
+struct spff_r2u {
+  spff_r2u_cfg cfg;
+  Vol vol[NLVL];
+  int f, K, ldx, t;
+  std::vector<REnt> params;
+  int64_t nparam = 0;
+  RBlk blk[NBLK];  // e1..e4, b, d4..d1
+  RUp up[NUP];     // up4, up3, up2, up1
+  int64_t head_w = -1, head_b = -1;
+  size_t head_pk = 0, x_cl = 0, pool[4] = {}, pidx[4] = {};
+  size_t red_ws = 0, red_out = 0, kk1 = 0, kk2 = 0, wg_ws = 0, wt = 0;
+  size_t tmp_w = 0, tmp_gb = 0, db_scr = 0;
+  bool pkb = false;
+  size_t wsl = 0;  // SPFF_MATH_F16X3 max |w| per block's conv (batched plans)
+  size_t G_out = 0, G_s = 0, G_1 = 0, G_2 = 0, G_dx = 0, dskip[4] = {};
+  size_t total = 0;
+  // per call
+  char* ws = nullptr;
+  const float* prm = nullptr;
+  float* dprm = nullptr;
+  hipStream_t st = nullptr;
+
+  float* F(size_t off) const { return reinterpret_cast<float*>(ws + off); }
+  const float* P(int64_t off) const { return prm + off; }
+  float* DP(int64_t off) const { return dprm + off; }
+  size_t alloc(size_t bytes) {
+    size_t o = total;
+    total += (bytes + 255) / 256 * 256;
+    return o;
+  }
+  int64_t reg(const std::string& name, std::vector<int64_t> shape) {
+    int64_t n = 1;
+    for (auto s : shape) n *= s;
+    params.push_back(REnt{name, shape, nparam, n});
+    nparam += n;
+    return nparam - n;
+  }
+};
+
+namespace {
+
+void reg_block(spff_r2u* p, RBlk& b) {
+  const int C = b.C;
+  const std::string n = "backbone." + b.name;
+  b.w_inp = p->reg(n + ".inp.weight", {C, b.Cin, 1, 1, 1});
+  b.w_ru = p->reg(n + ".ru.conv.weight", {C, C, 3, 3, 3});
+  b.g_ru = p->reg(n + ".ru.inn.weight", {C});
+  b.b_ru = p->reg(n + ".ru.inn.bias", {C});
+  b.w_out = p->reg(n + ".out.weight", {C, C, 1, 1, 1});
+  b.g_bn = p->reg(n + ".bn.weight", {C});
+  b.b_bn = p->reg(n + ".bn.bias", {C});
+}
+
+int build(spff_r2u* p) {
+  const spff_r2u_cfg& c = p->cfg;
+  if (c.batch < 1 || c.depth < 1 || c.height < 1 || c.width < 1)
+    return rfail(SPFF_EINVAL, "invalid batch / depth / height / width");
+  if (c.in_ch < 1 || c.in_ch > 8) return rfail(SPFF_EINVAL, "in_ch must be 1..8");
+  if (c.num_classes < 2 || c.num_classes > 32)
+    return rfail(SPFF_EINVAL, "num_classes must be 2..32 (the sigmoid branch, K = 1, is not built)");
+  if (c.base < 8 || c.base % 8) return rfail(SPFF_EINVAL, "base must be a multiple of 8");
+  if (c.t < 1 || c.t > TMAX) return rfail(SPFF_EINVAL, "t must be 1..8");
+  if (c.math < SPFF_MATH_F32 || c.math > SPFF_MATH_F16X3)
+    return rfail(SPFF_EINVAL, "math must be one of SPFF_MATH_*");
+  if (c.depth % 16 || c.height % 16 || c.width % 16)
+    return rfail(SPFF_ESHAPE,
+                 "D, H and W must be multiples of 16 (four MaxPool3d(2) whose outputs are "
+                 "concatenated with the ConvTranspose3d outputs); the Lit wrapper pads");
+  p->f = c.base;
+  p->K = c.num_classes;
+  p->t = c.t;
+  p->ldx = 8;
+  for (int l = 0; l < NLVL; ++l)
+    p->vol[l] = Vol{c.batch, c.depth >> l, c.height >> l, c.width >> l};
+  const int f = p->f, T = p->t;
+  const char* names[NBLK] = {"e1", "e2", "e3", "e4", "b", "d4", "d3", "d2", "d1"};
+  const int lvl[NBLK] = {0, 1, 2, 3, 4, 3, 2, 1, 0};
+  const int cin[NBLK] = {c.in_ch, f, 2 * f, 4 * f, 8 * f, 16 * f, 8 * f, 4 * f, 2 * f};
+  const int cc[NBLK] = {f, 2 * f, 4 * f, 8 * f, 16 * f, 8 * f, 4 * f, 2 * f, f};
+  for (int i = 0; i < NBLK; ++i) {
+    RBlk& b = p->blk[i];
+    b.name = names[i];
+    b.lvl = lvl[i];
+    b.Cin = cin[i];
+    b.C = cc[i];
+  }
+  // registration order of R2UNet3D_backbone.__init__, then the Lit head
+  for (int i = 0; i < 5; ++i) reg_block(p, p->blk[i]);
+  const char* upn[NUP] = {"up4", "up3", "up2", "up1"};
+  for (int u = 0; u < NUP; ++u) {
+    RUp& U = p->up[u];
+    U.Cin = 16 * f >> u;
+    U.Cout = 8 * f >> u;
+    U.lvl_low = 4 - u;
+    U.w = p->reg(std::string("backbone.") + upn[u] + ".weight", {U.Cin, U.Cout, 2, 2, 2});
+    U.b = p->reg(std::string("backbone.") + upn[u] + ".bias", {U.Cout});
+    reg_block(p, p->blk[5 + u]);
+  }
+  p->head_w = p->reg("head.weight", {p->K, f, 1, 1, 1});
+  p->head_b = p->reg("head.bias", {p->K});
+
+  // ---- workspace ----
+  const Vol& v0 = p->vol[0];
+  const int B = c.batch;
+  p->x_cl = p->alloc(nvox(v0) * p->ldx * sizeof(float));
+  size_t red_ws = 0, red_out = 0, wg = 0, wt = 0;
+  for (int i = 0; i < NBLK; ++i) {
+    RBlk& b = p->blk[i];
+    const Vol& v = p->vol[b.lvl];
+    const int64_t M = nvox(v);
+    const size_t act = M * b.C * sizeof(float);
+    const size_t bc = (size_t)B * b.C * sizeof(float);
+    auto stat = [&](RStat& s) {
+      s.mean = p->alloc(bc); s.rstd = p->alloc(bc); s.al = p->alloc(bc); s.de = p->alloc(bc);
+    };
+    b.x1 = p->alloc(act);
+    for (int k = 0; k < T; ++k) {
+      b.y[k] = p->alloc(act);
+      b.a[k] = p->alloc(act);
+      stat(b.st[k]);
+    }
+    b.s = p->alloc(act);
+    b.o = p->alloc(act);
+    stat(b.bn);
+    if (T > 1) b.gb2 = p->alloc((size_t)2 * b.C * sizeof(float));
+    // the GEMM reads level 0's input through its 8-channel rows: same image size
+    b.pk_inp = p->alloc(head_pack_floats(i == 0 ? p->ldx : b.Cin, b.C) * sizeof(float));
+    b.pk_out = p->alloc(head_pack_floats(b.C, b.C) * sizeof(float));
+    red_ws = std::max(red_ws, slab_reduce_ws_bytes(v, b.C, 2));
+    red_out = std::max(red_out, (size_t)B * b.C * v.D * 2 * sizeof(float));
+    wg = std::max(wg, conv3d_wgrad_ws_bytes(v, 3, b.C, b.C));
+    wg = std::max(wg, conv3d_splitk_bytes(v, 3, b.C, b.C));
+    wg = std::max(wg, linear_wgrad_ws_bytes(M, b.Cin, b.C));
+    wg = std::max(wg, linear_wgrad_ws_bytes(M, b.C, b.C));
+    wt = std::max(wt, conv3d_pack_bytes(3, b.C, b.C));
+  }
+  for (int l = 0; l < 4; ++l) {
+    const Vol& vl = p->vol[l + 1];
+    const int C = f << l;
+    p->pool[l] = p->alloc(nvox(vl) * C * sizeof(float));
+    p->pidx[l] = p->alloc(nvox(vl) * C);
+  }
+  for (int u = 0; u < NUP; ++u) {
+    RUp& U = p->up[u];
+    const Vol& vh = p->vol[U.lvl_low - 1];
+    U.out = p->alloc(nvox(vh) * U.Cout * sizeof(float));
+    U.pk = p->alloc(upconv_pack_floats(U.Cin, U.Cout, NSUB) * sizeof(float));
+    wg = std::max(wg, upconv_wgrad_ws_bytes(p->vol[U.lvl_low], U.Cin, U.Cout, NSUB));
+  }
+  p->head_pk = p->alloc(head_pack_floats(f, p->K) * sizeof(float));
+  wg = std::max(wg, head_wgrad_ws_bytes(nvox(v0), f, p->K));
+  p->red_ws = p->alloc(red_ws);
+  p->red_out = p->alloc(red_out);
+  p->kk1 = p->alloc((size_t)B * 16 * f * sizeof(float));
+  p->kk2 = p->alloc((size_t)B * 16 * f * sizeof(float));
+  p->wg_ws = p->alloc(wg);
+  p->tmp_w = p->alloc((size_t)16 * f * 16 * f * 27 * sizeof(float));
+  p->tmp_gb = p->alloc((size_t)2 * 16 * f * sizeof(float));
+  p->db_scr = p->alloc((size_t)16 * f * sizeof(float));
+  p->pkb = conv3d_packs_batched(c.math);
+  if (p->pkb) {
+    for (int i = 0; i < NBLK; ++i) {
+      RBlk& b = p->blk[i];
+      b.pk[0] = p->alloc(conv3d_pack_bytes(3, b.C, b.C));
+      b.pk[1] = p->alloc(conv3d_pack_bytes(3, b.C, b.C));
+    }
+    p->wsl = p->alloc(NBLK * sizeof(unsigned));
+  } else {
+    p->wt = p->alloc(wt);
+  }
+  size_t gmax = 0;  // max over levels of V_l * C_l
+  for (int l = 0; l < NLVL; ++l)
+    gmax = std::max(gmax, (size_t)nvox(p->vol[l]) * (size_t)(f << l) * sizeof(float));
+  p->G_out = p->alloc(gmax);
+  p->G_s = p->alloc(gmax);
+  p->G_1 = p->alloc(gmax);
+  p->G_2 = p->alloc(gmax);
+  p->G_dx = p->alloc(gmax);
+  for (int l = 0; l < 4; ++l)
+    p->dskip[l] = p->alloc(nvox(p->vol[l]) * (f << l) * sizeof(float));
+  return SPFF_OK;
+}
+
+// the weights' derived images at the forward start (they do not change between a step's
+// forward and backward): the 1x1x1 GEMM images, the doubled IN affine and, for the split
+// arithmetics, the conv images (forward and input gradient) in one launch pair
+int prep_weights(spff_r2u* p) {
+  const int math = p->cfg.math;
+  for (int i = 0; i < NBLK; ++i) {
+    RBlk& b = p->blk[i];
+    const int kin = i == 0 ? p->ldx : b.Cin;
+    float* pi = p->F(b.pk_inp);
+    float* po = p->F(b.pk_out);
+    // (level 0: head_pack zero-fills rows in_ch .. 31 of the forward image, which the
+    //  8-channel rows of x_cl meet with zeros of their own)
+    RHIPCK(head_pack(p->P(b.w_inp), pi, pi + head_pack_dgrad_offset(kin, b.C), b.Cin, b.C, p->st));
+    RHIPCK(head_pack(p->P(b.w_out), po, po + head_pack_dgrad_offset(b.C, b.C), b.C, b.C, p->st));
+    if (p->t > 1) {
+      hipLaunchKernelGGL(k_r2u_double, dim3((b.C + 255) / 256), dim3(256), 0, p->st,
+                         p->P(b.g_ru), p->P(b.b_ru), p->F(b.gb2), b.C);
+      RHIPCK(hipGetLastError());
+    }
+  }
+  if (!p->pkb) return SPFF_OK;
+  const bool f16 = math == SPFF_MATH_F16X3;
+  unsigned* sl = reinterpret_cast<unsigned*>(p->ws + p->wsl);
+  PrepJobs pj;
+  PackJobs kj;
+  if (f16) RHIPCK(spff::zero_async(sl, NBLK * sizeof(unsigned), p->st));
+  for (int i = 0; i < NBLK; ++i) {
+    RBlk& b = p->blk[i];
+    unsigned* wm = f16 ? sl + i : nullptr;
+    bool ok = true;
+    if (f16) ok = ok && prep_absmax(&pj, p->P(b.w_ru), (int64_t)b.C * b.C * 27, wm);
+    ok = ok && conv3d_pack_job(&kj, p->P(b.w_ru), p->F(b.pk[0]), 3, b.C, b.C, false, wm);
+    ok = ok && conv3d_pack_job(&kj, p->P(b.w_ru), p->F(b.pk[1]), 3, b.C, b.C, true, wm);
+    if (!ok) return rfail(SPFF_EINVAL, "weight preparation table overflow");
+  }
+  RHIPCK(prep_run(pj, p->st));
+  RHIPCK(conv3d_pack_many(kj, math, p->st));
+  return SPFF_OK;
+}
+
+// the block's conv image (forward or input gradient): the batched one, else packed now
+int conv_image(spff_r2u* p, const RBlk& b, bool dgrad, const Vol& v, const float** img,
+               const unsigned** wmax) {
+  if (p->pkb) {
+    *img = p->F(b.pk[dgrad ? 1 : 0]);
+    *wmax = p->cfg.math == SPFF_MATH_F16X3
+                ? reinterpret_cast<const unsigned*>(p->ws + p->wsl) + (int)(&b - p->blk)
+                : nullptr;
+    return SPFF_OK;
+  }
+  RHIPCK(conv3d_pack(p->P(b.w_ru), p->F(p->wt), v, 3, b.C, b.C, dgrad, p->cfg.math, p->st));
+  *img = p->F(p->wt);
+  *wmax = nullptr;
+  return SPFF_OK;
+}
+
+// InstanceNorm3d statistics of y per (b, c) and the apply coefficients al = gamma rstd,
+// de = beta - mean al
+int in_fwd(spff_r2u* p, const Vol& v, int C, const float* y, const RStat& s, const float* gamma,
+           const float* beta) {
+  RedArgs a{};
+  a.y = y;
+  RHIPCK(slab_reduce(RED_SUM, a, v, C, p->F(p->red_out), p->F(p->red_ws), p->st));
+  RHIPCK(in_mean(p->F(p->red_out), p->F(s.mean), v, C, p->st));
+  a.mean = p->F(s.mean);
+  RHIPCK(slab_reduce(RED_SQDEV, a, v, C, p->F(p->red_out), p->F(p->red_ws), p->st));
+  RHIPCK(in_rstd(p->F(p->red_out), gamma, beta, p->F(s.mean), p->F(s.rstd), p->F(s.al),
+                 p->F(s.de), v, C, p->st));
+  return SPFF_OK;
+}
+
+// InstanceNorm + ReLU backward: dy = rstd gamma (dr - k1 - xhat k2), dr = g [r > 0]
+int in_bwd(spff_r2u* p, const Vol& v, int C, const float* y, const float* g, float* dy,
+           const RStat& s, const float* gamma, float* dgamma, float* dbeta) {
+  RedArgs a{};
+  a.y = y; a.g = g; a.mean = p->F(s.mean); a.rstd = p->F(s.rstd);
+  a.al = p->F(s.al); a.de = p->F(s.de); a.neg = 0.f;
+  RHIPCK(slab_reduce(RED_BWD_IN, a, v, C, p->F(p->red_out), p->F(p->red_ws), p->st));
+  RHIPCK(in_bwd_stats(p->F(p->red_out), gamma, dgamma, dbeta, p->F(p->kk1), p->F(p->kk2), v, C,
+                      p->st));
+  RHIPCK(in_bwd_apply(y, g, dy, p->F(s.mean), p->F(s.rstd), p->F(s.al), p->F(s.de), gamma,
+                      nullptr, nullptr, p->F(p->kk1), p->F(p->kk2), v, C, p->st, 0.f));
+  return SPFF_OK;
+}
+
+// affine of recurrence step k (0-based): doubled for every step but the last
+const float* ru_gamma(const spff_r2u* p, const RBlk& b, int k) {
+  return k < p->t - 1 ? p->F(b.gb2) : p->P(b.g_ru);
+}
+const float* ru_beta(const spff_r2u* p, const RBlk& b, int k) {
+  return k < p->t - 1 ? p->F(b.gb2) + b.C : p->P(b.b_ru);
+}
+
+int fwd_block(spff_r2u* p, RBlk& b, const Src2& in, int kin) {
+  const Vol& v = p->vol[b.lvl];
+  const int C = b.C, math = p->cfg.math;
+  const int64_t M = nvox(v);
+  RHIPCK(linear_fwd2(in, kin, p->F(b.pk_inp), nullptr, p->F(b.x1), C, C, M, p->st));
+  const float* cur = p->F(b.x1);
+  for (int k = 0; k < p->t; ++k) {
+    const float* img;
+    const unsigned* wmax;
+    RCK(conv_image(p, b, false, v, &img, &wmax));
+    RHIPCK(conv3d_run(src1(cur, C), img, dst1(p->F(b.y[k]), C), v, 3, C, C, false, math, p->st,
+                      p->F(p->wg_ws), nullptr, 0, wmax));
+    RCK(in_fwd(p, v, C, p->F(b.y[k]), b.st[k], ru_gamma(p, b, k), ru_beta(p, b, k)));
+    RHIPCK(act_apply(p->F(b.y[k]), p->F(b.a[k]), p->F(b.st[k].al), p->F(b.st[k].de), nullptr,
+                     nullptr, v, C, p->st, 0.f));
+    cur = p->F(b.a[k]);
+  }
+  RHIPCK(linear_fwd(cur, C, C, p->F(b.pk_out), nullptr, p->F(b.s), C, C, M, p->F(b.x1), C, p->st));
+  RCK(in_fwd(p, v, C, p->F(b.s), b.bn, p->P(b.g_bn), p->P(b.b_bn)));
+  RHIPCK(act_apply(p->F(b.s), p->F(b.o), p->F(b.bn.al), p->F(b.bn.de), nullptr, nullptr, v, C,
+                   p->st, 0.f));
+  return SPFF_OK;
+}
+
+int bwd_block(spff_r2u* p, RBlk& b, const float* dout, const Dst2* dx, const Src2& in) {
+  const Vol& v = p->vol[b.lvl];
+  const int C = b.C, math = p->cfg.math, T = p->t;
+  const int64_t M = nvox(v);
+  const int64_t nw = (int64_t)C * C * 27;
+  float* ds = p->F(p->G_s);
+  float* g = p->F(p->G_1);
+  float* gn = p->F(p->G_2);
+  float* wgs = p->F(p->wg_ws);
+  // o = relu(IN_bn(s)): ds, which is also the residual branch's share of dx1
+  RCK(in_bwd(p, v, C, p->F(b.s), dout, ds, b.bn, p->P(b.g_bn), p->DP(b.g_bn), p->DP(b.b_bn)));
+  // s = x1 + out(a_t)
+  RHIPCK(linear_wgrad(p->F(b.a[T - 1]), C, C, ds, C, C, p->DP(b.w_out), p->F(p->db_scr), M, wgs,
+                      p->st));
+  RHIPCK(linear_dgrad(ds, C, C, p->F(b.pk_out) + head_pack_dgrad_offset(C, C), g, C, C, M, nullptr,
+                      p->st));
+  // the recurrence, steps t .. 1: g holds dL/da_k
+  for (int k = T - 1; k >= 0; --k) {
+    const bool last = k == T - 1;
+    float* dgam = last ? p->DP(b.g_ru) : p->F(p->tmp_gb);
+    float* dbet = last ? p->DP(b.b_ru) : p->F(p->tmp_gb) + C;
+    RCK(in_bwd(p, v, C, p->F(b.y[k]), g, g, b.st[k], ru_gamma(p, b, k), dgam, dbet));
+    if (!last) {  // affine (2 gamma, 2 beta): d/dgamma = 2 d/d(2 gamma)
+      RHIPCK(r2u_acc(p->DP(b.g_ru), dgam, C, 2.f, p->st));
+      RHIPCK(r2u_acc(p->DP(b.b_ru), dbet, C, 2.f, p->st));
+    }
+    const float* xin = k == 0 ? p->F(b.x1) : p->F(b.a[k - 1]);
+    float* dw = last ? p->DP(b.w_ru) : p->F(p->tmp_w);
+    RHIPCK(conv3d_wgrad(src1(xin, C), g, C, dw, v, 3, C, C, math, wgs, p->st));
+    if (!last) RHIPCK(r2u_acc(p->DP(b.w_ru), dw, nw, 1.f, p->st));
+    const float* img;
+    const unsigned* wmax;
+    RCK(conv_image(p, b, true, v, &img, &wmax));
+    RHIPCK(conv3d_run(src1(g, C), img, dst1(gn, C), v, 3, C, C, true, math, p->st, wgs, nullptr, 0,
+                      wmax));
+    std::swap(g, gn);
+  }
+  // x1 feeds the recurrent unit and the residual: dx1 = ds + (the unit's input gradient)
+  RHIPCK(r2u_acc(ds, g, M * C, 1.f, p->st));
+  RHIPCK(linear_wgrad2(in, b.Cin, ds, C, C, p->DP(b.w_inp), p->F(p->db_scr), M, wgs, p->st));
+  if (dx)
+    RHIPCK(linear_dgrad2(ds, C, C, p->F(b.pk_inp) + head_pack_dgrad_offset(b.Cin, C), *dx, b.Cin,
+                         M, 0, p->st));
+  return SPFF_OK;
+}
+
+int forward(spff_r2u* p, const float* x, float* logits) {
+  const spff_r2u_cfg& c = p->cfg;
+  const int f = p->f;
+  const Vol& v0 = p->vol[0];
+  RHIPCK(ncdhw_to_ndhwc(x, p->F(p->x_cl), v0, c.in_ch, p->ldx, p->st));
+  RCK(prep_weights(p));
+  RBlk* B = p->blk;
+  Src2 in = src1(p->F(p->x_cl), p->ldx);
+  int kin = p->ldx;
+  for (int l = 0; l < 4; ++l) {
+    RCK(fwd_block(p, B[l], in, kin));
+    RHIPCK(maxpool3_fwd(p->F(B[l].o), p->F(p->pool[l]),
+                        reinterpret_cast<uint8_t*>(p->ws + p->pidx[l]), p->vol[l], f << l, p->st));
+    in = src1(p->F(p->pool[l]), f << l);
+    kin = f << l;
+  }
+  RCK(fwd_block(p, B[4], in, kin));
+  const float* prev = p->F(B[4].o);
+  for (int u = 0; u < NUP; ++u) {
+    RUp& U = p->up[u];
+    float* pk = p->F(U.pk);
+    RHIPCK(upconv_pack(p->P(U.w), pk, pk + upconv_pack_dgrad_offset(U.Cin, U.Cout, NSUB), U.Cin,
+                       U.Cout, p->st, NSUB));
+    RHIPCK(upconv_fwd(prev, pk, p->P(U.b), p->F(U.out), p->vol[U.lvl_low], U.Cin, U.Cout, p->st,
+                      NSUB, p->cfg.math));
+    RBlk& d = B[5 + u];
+    const RBlk& skip = B[3 - u];
+    // torch.cat([up(x), skip], dim=1) read in place through the two-source view
+    RCK(fwd_block(p, d, Src2{p->F(U.out), p->F(skip.o), U.Cout, U.Cout, U.Cout}, 2 * U.Cout));
+    prev = p->F(d.o);
+  }
+  float* hp = p->F(p->head_pk);
+  RHIPCK(head_pack(p->P(p->head_w), hp, hp + head_pack_dgrad_offset(f, p->K), f, p->K, p->st));
+  RHIPCK(head_fwd(prev, hp, p->P(p->head_b), logits, nvox(v0), f, p->K, p->st, p->cfg.math));
+  return SPFF_OK;
+}
+
+int backward(spff_r2u* p, const float* dl) {
+  const int f = p->f;
+  const int64_t V0 = nvox(p->vol[0]);
+  RBlk* B = p->blk;
+  float* hp = p->F(p->head_pk);
+  RHIPCK(head_wgrad(p->F(B[8].o), dl, p->DP(p->head_w), p->DP(p->head_b), V0, f, p->K,
+                    p->F(p->wg_ws), p->st));
+  RHIPCK(head_dgrad(dl, hp + head_pack_dgrad_offset(f, p->K), p->F(p->G_out), V0, f, p->K, p->st,
+                    p->cfg.math));
+  for (int k = 0; k < NUP; ++k) {  // d1 <- up1 <- d2 ... <- up4
+    const int bi = 8 - k, ui = 3 - k;
+    RBlk& d = B[bi];
+    RUp& U = p->up[ui];
+    const int C = d.C, lvl = d.lvl;
+    Dst2 dx{p->F(p->G_dx), p->F(p->dskip[lvl]), C, C, C};
+    RCK(bwd_block(p, d, p->F(p->G_out), &dx, Src2{p->F(U.out), p->F(B[lvl].o), C, C, C}));
+    const Vol& low = p->vol[U.lvl_low];
+    RHIPCK(upconv_wgrad(p->F(B[bi - 1].o), p->F(p->G_dx), C, p->DP(U.w), p->DP(U.b), low, U.Cin,
+                        U.Cout, p->F(p->wg_ws), p->st, NSUB, p->cfg.math));
+    float* pk = p->F(U.pk);
+    RHIPCK(upconv_dgrad(p->F(p->G_dx), C, pk + upconv_pack_dgrad_offset(U.Cin, U.Cout, NSUB),
+                        p->F(p->G_out), low, U.Cin, U.Cout, p->st, NSUB, p->cfg.math));
+  }
+  {
+    Dst2 dx = dst1(p->F(p->G_dx), 8 * f);
+    RCK(bwd_block(p, B[4], p->F(p->G_out), &dx, src1(p->F(p->pool[3]), 8 * f)));
+  }
+  for (int l = 3; l >= 0; --l) {
+    const int C = f << l;
+    RHIPCK(maxpool3_bwd_add(p->F(p->G_dx), reinterpret_cast<const uint8_t*>(p->ws + p->pidx[l]),
+                            p->F(p->dskip[l]), C, p->F(p->dskip[l]), p->vol[l], C, p->st));
+    if (l > 0) {
+      Dst2 dx = dst1(p->F(p->G_dx), C / 2);
+      RCK(bwd_block(p, B[l], p->F(p->dskip[l]), &dx, src1(p->F(p->pool[l - 1]), C / 2)));
+    } else {
+      RCK(bwd_block(p, B[0], p->F(p->dskip[0]), nullptr, src1(p->F(p->x_cl), p->ldx)));
+    }
+  }
+  return SPFF_OK;
+}
+
+}  // namespace
+
+// =================================================================== C ABI ==
+extern "C" {
+
+int spff_r2u_create(const spff_r2u_cfg* cfg, spff_r2u** out) {
+  if (!cfg || !out) return rfail(SPFF_EINVAL, "null argument");
+  spff_r2u* p = new spff_r2u();
+  p->cfg = *cfg;
+  const int r = build(p);
+  if (r != SPFF_OK) {
+    delete p;
+    return r;
+  }
+  *out = p;
+  return SPFF_OK;
+}
+
+void spff_r2u_destroy(spff_r2u* p) { delete p; }
+
+int spff_r2u_num_params(const spff_r2u* p) { return p ? (int)p->params.size() : 0; }
+
+int spff_r2u_param_info(const spff_r2u* p, int i, const char** name, int* ndim, int64_t shape[5],
+                        int64_t* offset, int64_t* numel) {
+  if (!p || i < 0 || i >= (int)p->params.size()) return rfail(SPFF_EINVAL, "param index");
+  const REnt& e = p->params[i];
+  if (name) *name = e.name.c_str();
+  if (ndim) *ndim = (int)e.shape.size();
+  if (shape)
+    for (int k = 0; k < 5; ++k) shape[k] = k < (int)e.shape.size() ? e.shape[k] : 1;
+  if (offset) *offset = e.off;
+  if (numel) *numel = e.numel;
+  return SPFF_OK;
+}
+
+int64_t spff_r2u_param_floats(const spff_r2u* p) { return p ? p->nparam : 0; }
+size_t spff_r2u_workspace_bytes(const spff_r2u* p) { return p ? p->total : 0; }
+
+int spff_r2u_forward(spff_r2u* p, const float* x, const float* params, float* logits, void* ws,
+                     void* stream) {
+  if (!p || !x || !params || !logits || !ws) return rfail(SPFF_EINVAL, "null argument");
+  p->ws = static_cast<char*>(ws);
+  p->prm = params;
+  p->dprm = nullptr;
+  p->st = static_cast<hipStream_t>(stream);
+  return forward(p, x, logits);
+}
+
+int spff_r2u_backward(spff_r2u* p, const float* dlogits, const float* params, float* dparams,
+                      void* ws, void* stream) {
+  if (!p || !dlogits || !params || !dparams || !ws) return rfail(SPFF_EINVAL, "null argument");
+  p->ws = static_cast<char*>(ws);
+  p->prm = params;
+  p->dprm = dparams;
+  p->st = static_cast<hipStream_t>(stream);
+  return backward(p, dlogits);
+}
+
+int spff_r2u_saved_tensor(const spff_r2u* p, void* ws, const char* name, const float** ptr,
+                          int64_t* nv, int* ch) {
+  if (!p || !ws || !name || !ptr) return rfail(SPFF_EINVAL, "null argument");
+  const char* base = static_cast<const char*>(ws);
+  const std::string n(name);
+  auto ret = [&](size_t off, const Vol& v, int c) {
+    *ptr = reinterpret_cast<const float*>(base + off);
+    if (nv) *nv = nvox(v);
+    if (ch) *ch = c;
+    return SPFF_OK;
+  };
+  for (int i = 0; i < NBLK; ++i) {
+    const RBlk& b = p->blk[i];
+    const Vol& v = p->vol[b.lvl];
+    if (n == b.name + ".x1") return ret(b.x1, v, b.C);
+    if (n == b.name + ".out") return ret(b.o, v, b.C);
+    for (int k = 0; k < p->t; ++k)
+      if (n == b.name + ".ru" + std::to_string(k + 1)) return ret(b.a[k], v, b.C);
+  }
+  return rfail(SPFF_EINVAL, "unknown saved tensor " + n);
+}
+
+size_t spff_r2u_dice_loss_ws_bytes(int batch, int num_classes) {
+  return r2u_dice_ws_bytes(batch, num_classes);
+}
+
+int spff_r2u_dice_loss(const float* logits, const int64_t* labels, int batch,
+                       int64_t vox_per_sample, int num_classes, int use_ignore, int ignore_index,
+                       float* out4, float* dlogits, void* ws, void* stream) {
+  if (!logits || !labels || !out4 || !dlogits || !ws) return rfail(SPFF_EINVAL, "null argument");
+  if (batch < 1 || vox_per_sample < 1) return rfail(SPFF_EINVAL, "invalid batch / vox_per_sample");
+  if (num_classes < 2 || num_classes > 32)
+    return rfail(SPFF_EINVAL, "num_classes must be 2..32 (the sigmoid branch, K = 1, is not built)");
+  RHIPCK(r2u_dice_loss(logits, labels, batch, vox_per_sample, num_classes, use_ignore,
+                       ignore_index, out4, dlogits, ws, static_cast<hipStream_t>(stream)));
+  return SPFF_OK;
+}
+
+}  // extern "C"

@@ -50,6 +50,14 @@ size_t dice_ce_ws_bytes(int B, int K);
 hipError_t dice_ce_loss(const float* logits, const int64_t* labels, int B, int64_t vps, int K,
                         int ignore, int include_bg, double ce_weight, float* out4, float* dlogits,
                         void* ws, hipStream_t s);
+// LitR2UNet3D_Published._dice_only_loss_with_logits, multi-class branch (r2unet.hip): the
+// foreground-only soft Dice over the samples that have a valid foreground voxel, on the same
+// statistics and gradient kernels.  out4 = [dice_mean, loss, kept_samples, N_valid]; no
+// sample kept: loss = dice = 0 and dlogits = 0.  use_ignore = 0: no voxel is masked.
+size_t r2u_dice_ws_bytes(int B, int K);
+hipError_t r2u_dice_loss(const float* logits, const int64_t* labels, int B, int64_t vps, int K,
+                         int use_ignore, int ignore, float* out4, float* dlogits, void* ws,
+                         hipStream_t s);
 
 // ---------------------------------------------------- window attention --
 // One unshifted Swin window-attention layer over a token grid [B][D][H][W]:

@@ -731,4 +731,86 @@ hipError_t dice_ce_loss(const float* logits, const int64_t* labels, int B, int64
   return hipGetLastError();
 }
 
+// ------------------------------------ foreground-only soft Dice (R2UNet3D) --
+// LitR2UNet3D_Published._dice_only_loss_with_logits, multi-class branch, from the totals of
+// k_dice_stats / k_dice_sum (I_k, P_k, G_k per sample; for k >= 1 G_k counts valid voxels
+// only, the ignored ones being filed under class 0).  Sample b is kept iff sum_{k>=1} G_k > 0;
+// over the n kept samples and the nc = K - 1 foreground classes
+//   dice = (2 I + eps) / (P + G + eps),  loss = 1 - mean dice,
+// and the coefficients k_dice_grad consumes (dL/dp_k = m (alpha g_k + beta)) are
+//   alpha = -2 / (n nc den),  beta = (2 I + eps) / (n nc den^2),  den = P + G + eps,
+// zero for k = 0 and for dropped samples.  No CE term: scal[0] = 0.  No sample kept: every
+// coefficient is zero, so dlogits = 0, and loss = dice = 0.
+// out4 = [dice_mean, loss, kept_samples, N_valid].  One thread: B K <= a few hundred terms,
+// summed in (b, k) order.
+__global__ void k_r2u_dice_final(const double* __restrict__ tot, int B, int K,
+                                 float* __restrict__ coef, float* __restrict__ out4,
+                                 double* __restrict__ scal) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  const int nq = 3 * K + 2, nc = K - 1;
+  const double eps = 1e-6;
+  int n = 0;
+  double N = 0.0;
+  for (int b = 0; b < B; ++b) {
+    const double* q = tot + (int64_t)b * nq;
+    double fg = 0.0;
+    for (int k = 1; k < K; ++k) fg += q[2 * K + k];
+    if (fg > 0.0) ++n;
+    N += q[3 * K + 1];
+  }
+  double dsum = 0.0;
+  for (int b = 0; b < B; ++b) {
+    const double* q = tot + (int64_t)b * nq;
+    double fg = 0.0;
+    for (int k = 1; k < K; ++k) fg += q[2 * K + k];
+    const bool kept = fg > 0.0;
+    for (int k = 0; k < K; ++k) {
+      float a = 0.f, be = 0.f;
+      if (kept && k >= 1) {
+        const double I = q[k], den = q[K + k] + q[2 * K + k] + eps;
+        const double w = 1.0 / ((double)n * nc);
+        dsum += (2.0 * I + eps) / den;
+        a = (float)(-2.0 * w / den);
+        be = (float)((2.0 * I + eps) * w / (den * den));
+      }
+      coef[((int64_t)b * K + k) * 2 + 0] = a;
+      coef[((int64_t)b * K + k) * 2 + 1] = be;
+    }
+  }
+  const double dice = n > 0 ? dsum / ((double)n * nc) : 0.0;
+  out4[0] = (float)dice;
+  out4[1] = n > 0 ? (float)(1.0 - dice) : 0.f;
+  out4[2] = (float)n;
+  out4[3] = (float)N;
+  scal[0] = 0.0;
+}
+
+size_t r2u_dice_ws_bytes(int B, int K) { return dice_ce_ws_bytes(B, K); }
+
+hipError_t r2u_dice_loss(const float* logits, const int64_t* labels, int B, int64_t vps, int K,
+                         int use_ignore, int ignore, float* out4, float* dlogits, void* ws,
+                         hipStream_t s) {
+  if (K < 2 || K > DL_KMAX || B < 1 || vps < 1) return hipErrorInvalidValue;
+  // no mask: a label value no voxel carries (labels are class indices, >= 0)
+  const int ign = use_ignore ? ignore : -1;
+  double* part = static_cast<double*>(ws);
+  double* tot = part + (size_t)B * DL_GRID * (3 * K + 2);
+  double* scal = tot + (size_t)B * (3 * K + 2);
+  float* coef = reinterpret_cast<float*>(scal + 8);
+  const size_t lds = (size_t)(DL_T / 64) * 64 * (K + 1) * sizeof(float);
+  hipLaunchKernelGGL(k_dice_stats, dim3(DL_GRID, B), dim3(DL_T), lds, s, logits, labels, vps, K,
+                     ign, part);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_dice_sum, dim3(3 * K + 2, B), dim3(256), 0, s, part, DL_GRID, 3 * K + 2,
+                     tot);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  hipLaunchKernelGGL(k_r2u_dice_final, dim3(1), dim3(64), 0, s, tot, B, K, coef, out4, scal);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  const int64_t V = (int64_t)B * vps;
+  hipLaunchKernelGGL(k_dice_grad, dim3((unsigned)std::min<int64_t>(cdiv64(V, DL_T), 2048)),
+                     dim3(DL_T), lds, s, logits, labels, vps, V, K, ign, coef, scal, dlogits);
+  return hipGetLastError();
+}
+
 }  // namespace spff

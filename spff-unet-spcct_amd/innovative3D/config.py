@@ -10,9 +10,9 @@ engine implements.  Differences, all deliberate:
   directories are created by whoever writes to them (train.py);
 * ``INNOVATIVE3D_VARIANT`` actually selects (SURVEY F11): ``selected_variants()``;
 * of the non-SPCT baselines "3DUNet" (BASELINE config 3, SURVEY §8(f) rank 2:
-  Cicek3DUNet + depth adapter) and "SwinUNETR" (BASELINE config 5, §8(f) rank 3)
-  are registered, both on the engine; UNETR, R2UNet3D and ResUNet++ are outside
-  the SPFF hot path (SURVEY §8);
+  Cicek3DUNet + depth adapter), "SwinUNETR" (BASELINE config 5, §8(f) rank 3) and
+  "R2UNet3D" (the recurrent residual U-Net with its Dice-only loss) are
+  registered, all on the engine; UNETR and ResUNet++ are not built (SURVEY §8);
 * the DICOM data module (``MultiDicomDataModule3D``) is the device-resident
   one of innovative3D/datasets.py (resize, ROI rasterisation and TrainGridAug as
   HIP kernels); DICOM files are decoded by pydicom when installed, else by the native
@@ -145,6 +145,15 @@ _add_variant("SwinUNETR",
                          warmup_epochs=5, use_ce_alongside_dice=True, ce_weight=0.5,
                          ignore_index=IGNORE_INDEX, include_bg_in_dice=False),
              MultiDicomDataModule3D, CHECKPOINT_DIR / "SwinUNETR")
+
+# R2UNet3D (config.py:347-361).  build_class drops the kwargs LitR2UNet3D_Published does
+# not take (include_bg_in_dice, ce_weight, dice_weight), exactly like the reference.
+_add_variant("R2UNet3D",
+             build_class("LitR2UNet3D_Published", num_classes=NUM_CLASSES, in_channels=1,
+                         base_features=16, t=2, lr=1e-3, weight_decay=0.0, ignore_index=255,
+                         include_bg_in_dice=False, ce_weight=0.0, dice_weight=1.0,
+                         pad_multiple=16),
+             MultiDicomDataModule3D, CHECKPOINT_DIR / "R2UNet3D")
 
 VARIANT_NAMES = [v[0] for v in VARIANTS]
 SELECTED_VARIANT = os.getenv("INNOVATIVE3D_VARIANT")

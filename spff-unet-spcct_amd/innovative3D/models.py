@@ -1125,3 +1125,189 @@ class LitSwinUNETR_Published(pl.LightningModule):
     def configure_optimizers(self):
         return torch.optim.AdamW(self.parameters(), lr=self.hparams.lr,
                                  weight_decay=self.hparams.weight_decay, betas=(0.9, 0.999))
+
+
+# ============================================================================
+# R2UNet3D (registry "R2UNet3D"): LitR2UNet3D_Published around
+# R2UNet3D_backbone, the recurrent residual 3D U-Net, on the engine's spff_r2u
+# plan (csrc/r2unet.hip).  The module tree below only holds parameters under the
+# reference's state-dict names; backbone and head run as one plan from the Lit
+# module's forward.  Parity: tests/golden/r2u_*.npz.
+# ============================================================================
+class _RecurrentUnit3D(nn.Module):
+    """t steps of relu(InstanceNorm(conv3x3x3(out + h))) with one shared conv and norm."""
+
+    def __init__(self, channels: int, t: int = 2):
+        super().__init__()
+        self.t = int(t)
+        self.conv = nn.Conv3d(channels, channels, 3, padding=1, bias=False)
+        self.inn = nn.InstanceNorm3d(channels, affine=True)
+        self.act = nn.ReLU(inplace=True)
+
+
+class _RRCNNBlock3D(nn.Module):
+    """x1 = inp(x); o = relu(InstanceNorm(x1 + out(ru(x1)))), inp / out 1x1x1 without bias."""
+
+    def __init__(self, cin: int, cout: int, t: int = 2):
+        super().__init__()
+        self.inp = nn.Conv3d(cin, cout, 1, bias=False)
+        self.ru = _RecurrentUnit3D(cout, t=t)
+        self.out = nn.Conv3d(cout, cout, 1, bias=False)
+        self.bn = nn.InstanceNorm3d(cout, affine=True)
+        self.act = nn.ReLU(inplace=True)
+
+
+class R2UNet3D_backbone(nn.Module):
+    """Five levels of recurrent residual blocks (channels base * {1, 2, 4, 8, 16}),
+    MaxPool3d(2) down, ConvTranspose3d(2, stride 2) + cat([up, skip]) up.  A parameter
+    container: the engine plan covers backbone and head together, so it runs from
+    LitR2UNet3D_Published.forward."""
+
+    def __init__(self, in_channels: int = 1, base: int = 16, t: int = 2):
+        super().__init__()
+        c = [base, base * 2, base * 4, base * 8, base * 16]
+        self.in_channels, self.base, self.t = int(in_channels), int(base), int(t)
+        self.e1 = _RRCNNBlock3D(in_channels, c[0], t=t); self.p1 = nn.MaxPool3d(2)  # noqa: E702
+        self.e2 = _RRCNNBlock3D(c[0], c[1], t=t); self.p2 = nn.MaxPool3d(2)  # noqa: E702
+        self.e3 = _RRCNNBlock3D(c[1], c[2], t=t); self.p3 = nn.MaxPool3d(2)  # noqa: E702
+        self.e4 = _RRCNNBlock3D(c[2], c[3], t=t); self.p4 = nn.MaxPool3d(2)  # noqa: E702
+        self.b = _RRCNNBlock3D(c[3], c[4], t=t)
+        for i, n in ((3, "4"), (2, "3"), (1, "2"), (0, "1")):
+            setattr(self, "up" + n, nn.ConvTranspose3d(c[i + 1], c[i], 2, 2))
+            setattr(self, "d" + n, _RRCNNBlock3D(c[i] + c[i], c[i], t=t))
+        self.out_ch = c[0]
+
+    def forward(self, x):
+        raise NotImplementedError("R2UNet3D_backbone holds parameters only: the engine plan runs "
+                                  "backbone and head together (LitR2UNet3D_Published.forward)")
+
+
+class _R2UFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, plan, flat, grad_hook, *params):
+        logits_cl = plan.forward(x, flat)
+        ctx.plan, ctx.gen, ctx.flat, ctx.grad_hook = plan, plan.generation, flat, grad_hook
+        plan._pending_gen = plan.generation if any(ctx.needs_input_grad) else None
+        ctx.param_ids = tuple(id(p) for p in params)
+        ctx.slices = [(off, n, shape) for (_name, shape, off, n) in plan.params]
+        return logits_cl.permute(0, 4, 1, 2, 3)
+
+    @staticmethod
+    def backward(ctx, g):
+        plan = ctx.plan
+        if plan.generation != ctx.gen:
+            raise E.SpffError("R2UNet3D engine: another forward ran on this model before the "
+                              "backward of this one; the engine keeps one forward's activations")
+        g_cl = g.permute(0, 2, 3, 4, 1).contiguous()
+        dflat = plan.backward(g_cl, ctx.flat, grad_hook=ctx.grad_hook)
+        plan._pending_gen = None
+        _mark_covered(ctx.grad_hook, ctx.param_ids)
+        grads = [dflat[o:o + n].view(s) for (o, n, s) in ctx.slices]
+        return (None, None, None, None, *grads)
+
+
+class _R2UDiceLoss(torch.autograd.Function):
+    """(loss, dice) of the foreground-only soft Dice; dice carries no gradient."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, K, ignore_index):
+        lcl = logits.permute(0, 2, 3, 4, 1).contiguous()
+        out4, dl = E.r2u_dice_loss_forward(lcl, labels, K, ignore_index)
+        ctx.dl = dl
+        ctx.mark_non_differentiable(out4)
+        return out4[1].clone(), out4
+
+    @staticmethod
+    def backward(ctx, g, _g4=None):
+        dl = ctx.dl
+        E.scale_(dl, g.reshape(1))
+        return dl.permute(0, 4, 1, 2, 3), None, None, None
+
+
+class LitR2UNet3D_Published(pl.LightningModule):
+    """Registry "R2UNet3D": replicate-pad D, H, W to multiples of ``pad_multiple`` ->
+    R2UNet3D_backbone -> 1x1x1 head -> centre crop (padding and cropping are torch
+    plumbing, backbone and head one engine plan); foreground-only soft-Dice loss over the
+    samples that have foreground, on the HIP loss kernels; Adam.  ``math`` (attribute)
+    selects the conv arithmetic of new plans.  ``num_classes == 1`` (the reference's sigmoid
+    branch) is not built."""
+
+    def __init__(self, num_classes: int, in_channels: int = 1, base_features: int = 16, t: int = 2,
+                 lr: float = 1e-3, weight_decay: float = 0.0, pad_multiple: int = 16,
+                 ignore_index: Optional[int] = None):
+        super().__init__()
+        if int(num_classes) == 1:
+            raise NotImplementedError("LitR2UNet3D_Published: num_classes == 1 (single-channel "
+                                      "sigmoid Dice) is not built on the engine; use >= 2 classes")
+        self.save_hyperparameters({
+            "num_classes": num_classes, "in_channels": in_channels,
+            "base_features": base_features, "t": t, "lr": lr, "weight_decay": weight_decay,
+            "pad_multiple": pad_multiple, "ignore_index": ignore_index})
+        self.backbone = R2UNet3D_backbone(in_channels=in_channels, base=base_features, t=t)
+        self.binary = False
+        self.head = nn.Conv3d(self.backbone.out_ch, num_classes, 1)
+        self._flat = None
+
+    def _plan(self, x):
+        B, C, D, H, W = x.shape
+        bb = self.backbone
+        if C != bb.in_channels:
+            raise ValueError(f"expected {bb.in_channels} input channels, got {C}")
+        return E.get_r2u_plan(batch=B, in_ch=C, depth=D, height=H, width=W,
+                              num_classes=int(self.hparams.num_classes), base=bb.base, t=bb.t,
+                              device=x.device, math=getattr(self, "math", None), owner=self)
+
+    _engine_params = SwinUNETR._engine_params
+    _ensure_flat = SwinUNETR._ensure_flat
+
+    def forward(self, x):
+        x = _pick_first_if_seq(x)
+        E.require_device(x, "LitR2UNet3D_Published.forward")
+        if x.ndim == 4:
+            x = x.unsqueeze(1)
+        m = int(self.hparams.pad_multiple)
+        if m % 16:
+            raise NotImplementedError("pad_multiple must be a multiple of 16 (four poolings)")
+        x_pad, orig = _pad_to_mult16_3d(x.float(), multiple=m)
+        plan = self._plan(x_pad)
+        params = self._engine_params(plan)
+        flat = self._ensure_flat(plan, params, x_pad.device)
+        if torch.is_grad_enabled() and any(p.requires_grad for p in params):
+            y = _R2UFunction.apply(x_pad, plan, flat, getattr(self, "grad_hook", None), *params)
+        else:
+            y = plan.forward(x_pad, flat).permute(0, 4, 1, 2, 3)
+        return _center_crop_3d(y, orig)
+
+    @staticmethod
+    def _dice_only_loss_with_logits(logits, y, ignore_index=None, eps=1e-6):
+        """Foreground-only soft Dice over the samples with foreground: (loss, dice_mean);
+        both 0 (and no gradient) when no sample has foreground."""
+        if eps != 1e-6:
+            raise NotImplementedError("the loss kernel's eps is 1e-6")
+        if logits.shape[1] == 1:
+            raise NotImplementedError("the single-channel sigmoid Dice branch is not built")
+        if y.ndim == 5 and y.size(1) == 1:
+            y = y[:, 0]
+        loss, out4 = _R2UDiceLoss.apply(logits, y, int(logits.shape[1]),
+                                        None if ignore_index is None else int(ignore_index))
+        return loss, out4[0]
+
+    def _step(self, batch, stage):
+        x, y = batch if isinstance(batch, (list, tuple)) else (batch["image"], batch["label"])
+        logits = self(x)
+        y = torch.as_tensor(y).to(logits.device)
+        loss, dice = self._dice_only_loss_with_logits(logits, y,
+                                                      ignore_index=self.hparams.ignore_index)
+        self.log(f"{stage}_loss", loss, on_epoch=True, prog_bar=True, sync_dist=True)
+        self.log(f"{stage}_macro_dice", dice, on_epoch=True, prog_bar=True, sync_dist=True)
+        return loss
+
+    def training_step(self, batch, _):
+        return self._step(batch, "train")
+
+    def validation_step(self, batch, _):
+        return self._step(batch, "val")
+
+    def configure_optimizers(self):
+        return torch.optim.Adam(self.parameters(), lr=self.hparams.lr,
+                                weight_decay=self.hparams.weight_decay)
