@@ -362,6 +362,81 @@ int spff_r2u_dice_loss(const float* logits, const int64_t* labels, int batch,
                        int64_t vox_per_sample, int num_classes, int use_ignore, int ignore_index,
                        float* out4, float* dlogits, void* ws, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * ResUNet++ variant (registry entry "ResUNet++"): LitResUNetPP3D_Published around
+ * ResUNetPP3D_backbone.  Channels c = base * (1, 2, 4, 8, 16), five levels, MaxPool3d(2).
+ *   ResidualUnit(cin -> C): s = skip(x) (1x1x1 without bias; the identity when cin == C),
+ *     a1 = relu(IN1(c1(x))), out = relu(IN2(c2(a1)) + s); c1, c2 3x3x3 without bias.
+ *   e1..e4 with pools between; b = b_aspp_out(ASPP(b_aspp_in(pool(e4)))).
+ *   ASPP(C): four 3x3x3 convs of one input with dilation = padding = 1, 2, 4, 8, concatenated
+ *     in branch order, then a 1x1x1 conv without bias and a ReLU.
+ *   SE(C): x * sigmoid(W2 relu(W1 mean(x) + b1) + b2), hidden max(1, C / 16).
+ *   Decoder level l = 4..2: u = up_l(below); s = u * sigmoid(psi(relu(W_x u + W_g se_l(e_l))))
+ *     (the gate multiplies the up-sampled tensor: the reference's argument order);
+ *     d_l = ResidualUnit([u | s]).  Level 1 has no gate: d1 = ResidualUnit([u1 | se1(e1)]).
+ *   logits = head(d1), a 1x1x1 conv with bias.
+ * Parameters: one flat fp32 buffer in the Lit module's named_parameters() order and names
+ * ("backbone.e1.c1.weight" ... "backbone.d1.skip.weight", "head.weight", "head.bias": 118
+ * entries; b_aspp_out has no skip.weight).  D, H and W must be multiples of 16 and the
+ * bottleneck must keep more than one voxel per sample (InstanceNorm).
+ * Saved tensors (spff_rupp_saved_tensor): for <blk> in e1..e4, b_aspp_in, b_aspp_out,
+ * d4..d1: "<blk>.a1" and "<blk>.out"; "b_aspp.out"; "ag<l>.att" (the gate's hidden row
+ * after its ReLU, l = 4..2).
+ * -------------------------------------------------------------------------- */
+typedef struct spff_rupp_cfg {
+  int batch, in_ch, depth, height, width;  /* input [B][Cin][D][H][W], Cin 1..8 */
+  int num_classes;   /* K, 2..32 */
+  int base;          /* a multiple of 8; the registry uses 16 */
+  int math;          /* SPFF_MATH_* for the undilated 3x3x3 convolutions (the ASPP's dilated
+                        convolutions always run fp32 MFMA arithmetic) */
+  int reserved[8];   /* zero */
+} spff_rupp_cfg;
+
+typedef struct spff_rupp spff_rupp;
+
+int spff_rupp_create(const spff_rupp_cfg* cfg, spff_rupp** out);
+void spff_rupp_destroy(spff_rupp* net);
+int spff_rupp_num_params(const spff_rupp* net);
+int spff_rupp_param_info(const spff_rupp* net, int i, const char** name, int* ndim,
+                         int64_t shape[5], int64_t* offset, int64_t* numel);
+int64_t spff_rupp_param_floats(const spff_rupp* net);
+size_t spff_rupp_workspace_bytes(const spff_rupp* net);
+/* forward: x [B][Cin][D][H][W] -> logits [B][D][H][W][K] (channel-last) */
+int spff_rupp_forward(spff_rupp* net, const float* x, const float* params, float* logits,
+                      void* workspace, void* stream);
+/* backward of the last forward: dlogits [B][D][H][W][K] -> dparams (every entry written) */
+int spff_rupp_backward(spff_rupp* net, const float* dlogits, const float* params,
+                       float* dparams, void* workspace, void* stream);
+int spff_rupp_saved_tensor(const spff_rupp* net, void* workspace, const char* name,
+                           const float** ptr, int64_t* nvox, int* channels);
+/* dice_ce_loss_with_metrics: p = softmax(logits) and the one-hot labels, both masked by
+ * [y != ignore_index] (use_ignore = 0: no mask); I, P, G summed over the whole batch;
+ * dice_k = (2 I_k + 1e-6) / (P_k + G_k + 1e-6) over the classes 1..K-1 (include_bg: 0..K-1);
+ * loss = dice_weight (1 - mean_k dice_k) + ce_weight CE, CE the mean over valid voxels.
+ * out4 = [ce, loss, dice_mean, N_valid]; logits / dlogits [B][vox_per_sample][K]
+ * channel-last rows.  ws >= spff_rupp_loss_ws_bytes device bytes. */
+size_t spff_rupp_loss_ws_bytes(int batch, int num_classes);
+int spff_rupp_loss(const float* logits, const int64_t* labels, int batch, int64_t vox_per_sample,
+                   int num_classes, int use_ignore, int ignore_index, int include_bg,
+                   double ce_weight, double dice_weight, float* out4, float* dlogits, void* ws,
+                   void* stream);
+/* Op-level dilated 3x3x3 convolution (the ASPP branches): dilation = padding = `dilation`
+ * in all three axes, channel-last rows with pitches ldx / ldy (multiples of 4 floats, so a
+ * branch can write its channel range of a wider row), weight W[cout][cin][3][3][3]; cin and
+ * cout multiples of 4.  fp32 MFMA arithmetic.  Taps that lie outside the volume for every
+ * output voxel are skipped (their weight gradient is zero).  dgrad: dx [.][ldx] = the input
+ * gradient of dy [.][ldy], added to dx when accumulate != 0.  ws >=
+ * spff_conv3d_dil_ws_bytes(cin, cout). */
+size_t spff_conv3d_dil_ws_bytes(int cin, int cout);
+int spff_conv3d_dil_fwd(const float* x, int ldx, const float* w, float* y, int ldy, int B, int D,
+                        int H, int W, int cin, int cout, int dilation, void* ws, void* stream);
+int spff_conv3d_dil_dgrad(const float* dy, int ldy, const float* w, float* dx, int ldx, int B,
+                          int D, int H, int W, int cin, int cout, int dilation, int accumulate,
+                          void* ws, void* stream);
+int spff_conv3d_dil_wgrad(const float* x, int ldx, const float* dy, int ldy, float* dw, int B,
+                          int D, int H, int W, int cin, int cout, int dilation, void* ws,
+                          void* stream);
+
 /* ------------------------------------------------------------------------
  * SwinUNETR variant (BASELINE config 5; registry "SwinUNETR", config.py:366-386
  * -> LitSwinUNETR_Published / SwinUNETR_Published, models.py:858-982, i.e.

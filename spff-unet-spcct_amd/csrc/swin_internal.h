@@ -58,6 +58,13 @@ size_t r2u_dice_ws_bytes(int B, int K);
 hipError_t r2u_dice_loss(const float* logits, const int64_t* labels, int B, int64_t vps, int K,
                          int use_ignore, int ignore, float* out4, float* dlogits, void* ws,
                          hipStream_t s);
+// LitResUNetPP3D_Published._loss (dice_ce_loss_with_metrics, resunetpp.hip): soft Dice with
+// I, P, G pooled over the whole batch plus the mean CE over valid voxels, on the same
+// kernels.  out4 = [ce, loss, dice_mean, N_valid]; use_ignore = 0: no voxel is masked.
+size_t rupp_loss_ws_bytes(int B, int K);
+hipError_t rupp_loss(const float* logits, const int64_t* labels, int B, int64_t vps, int K,
+                     int use_ignore, int ignore, int include_bg, double ce_weight,
+                     double dice_weight, float* out4, float* dlogits, void* ws, hipStream_t s);
 
 // ---------------------------------------------------- window attention --
 // One unshifted Swin window-attention layer over a token grid [B][D][H][W]:

@@ -813,4 +813,81 @@ hipError_t r2u_dice_loss(const float* logits, const int64_t* labels, int B, int6
   return hipGetLastError();
 }
 
+// ------------------------------ batch-pooled soft Dice + CE (ResUNet++) --
+// dice_ce_loss_with_metrics: I_k, P_k, G_k pooled over the whole batch (the per-sample
+// totals of k_dice_stats / k_dice_sum added in sample order), classes k >= sc,
+//   dice_k = (2 I_k + eps) / (P_k + G_k + eps),  loss = dw (1 - mean_k dice_k) + cw CE.
+// k_dice_stats files the ignored voxels under class 0 of G; the reference's one-hot drops
+// them, so with the background included (sc = 0) G_0 -= V - N_valid.  The coefficients
+// k_dice_grad consumes (dL/dp_k = m (alpha g_k + beta)) are the same for every sample:
+//   alpha = -2 dw / (nc den),  beta = dw (2 I + eps) / (nc den^2),  den = P + G + eps;
+// scal[0] = cw / N_valid (the CE gradient scale).  out4 = [ce, loss, dice_mean, N_valid].
+__global__ void k_rupp_loss_final(const double* __restrict__ tot, int B, int K, int sc, double V,
+                                  double cw, double dw, float* __restrict__ coef,
+                                  float* __restrict__ out4, double* __restrict__ scal) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  const int nq = 3 * K + 2, nc = K - sc;
+  const double eps = 1e-6;
+  double ce = 0.0, N = 0.0;
+  for (int b = 0; b < B; ++b) {
+    ce += tot[(int64_t)b * nq + 3 * K];
+    N += tot[(int64_t)b * nq + 3 * K + 1];
+  }
+  double dsum = 0.0;
+  for (int k = 0; k < K; ++k) {
+    double I = 0.0, P = 0.0, G = 0.0;
+    for (int b = 0; b < B; ++b) {
+      const double* q = tot + (int64_t)b * nq;
+      I += q[k]; P += q[K + k]; G += q[2 * K + k];
+    }
+    if (k == 0) G -= V - N;
+    float a = 0.f, be = 0.f;
+    if (k >= sc) {
+      const double den = P + G + eps;
+      dsum += (2.0 * I + eps) / den;
+      a = (float)(-2.0 * dw / ((double)nc * den));
+      be = (float)(dw * (2.0 * I + eps) / ((double)nc * den * den));
+    }
+    for (int b = 0; b < B; ++b) {
+      coef[((int64_t)b * K + k) * 2 + 0] = a;
+      coef[((int64_t)b * K + k) * 2 + 1] = be;
+    }
+  }
+  const double dice = dsum / (double)nc;
+  const double cem = N > 0 ? ce / N : NAN;  // F.cross_entropy: 0/0 -> nan
+  out4[0] = (float)cem;
+  out4[1] = (float)(dw * (1.0 - dice) + cw * cem);
+  out4[2] = (float)dice;
+  out4[3] = (float)N;
+  scal[0] = N > 0 ? cw / N : 0.0;
+}
+
+size_t rupp_loss_ws_bytes(int B, int K) { return dice_ce_ws_bytes(B, K); }
+
+hipError_t rupp_loss(const float* logits, const int64_t* labels, int B, int64_t vps, int K,
+                     int use_ignore, int ignore, int include_bg, double ce_weight,
+                     double dice_weight, float* out4, float* dlogits, void* ws, hipStream_t s) {
+  if (K < 2 || K > DL_KMAX || B < 1 || vps < 1) return hipErrorInvalidValue;
+  const int ign = use_ignore ? ignore : -1;  // no mask: a value no label carries
+  double* part = static_cast<double*>(ws);
+  double* tot = part + (size_t)B * DL_GRID * (3 * K + 2);
+  double* scal = tot + (size_t)B * (3 * K + 2);
+  float* coef = reinterpret_cast<float*>(scal + 8);
+  const size_t lds = (size_t)(DL_T / 64) * 64 * (K + 1) * sizeof(float);
+  hipLaunchKernelGGL(k_dice_stats, dim3(DL_GRID, B), dim3(DL_T), lds, s, logits, labels, vps, K,
+                     ign, part);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_dice_sum, dim3(3 * K + 2, B), dim3(256), 0, s, part, DL_GRID, 3 * K + 2,
+                     tot);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  const int64_t V = (int64_t)B * vps;
+  hipLaunchKernelGGL(k_rupp_loss_final, dim3(1), dim3(64), 0, s, tot, B, K, include_bg ? 0 : 1,
+                     (double)V, ce_weight, dice_weight, coef, out4, scal);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  hipLaunchKernelGGL(k_dice_grad, dim3((unsigned)std::min<int64_t>(cdiv64(V, DL_T), 2048)),
+                     dim3(DL_T), lds, s, logits, labels, vps, V, K, ign, coef, scal, dlogits);
+  return hipGetLastError();
+}
+
 }  // namespace spff

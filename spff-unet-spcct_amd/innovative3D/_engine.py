@@ -63,6 +63,14 @@ class spff_r2u_cfg(ctypes.Structure):
     ]
 
 
+class spff_rupp_cfg(ctypes.Structure):
+    _fields_ = [
+        ("batch", ctypes.c_int), ("in_ch", ctypes.c_int), ("depth", ctypes.c_int),
+        ("height", ctypes.c_int), ("width", ctypes.c_int), ("num_classes", ctypes.c_int),
+        ("base", ctypes.c_int), ("math", ctypes.c_int), ("reserved", ctypes.c_int * 8),
+    ]
+
+
 class spff_swin_cfg(ctypes.Structure):
     _fields_ = [
         ("batch", ctypes.c_int), ("in_ch", ctypes.c_int), ("depth", ctypes.c_int),
@@ -190,6 +198,25 @@ _SIGS = {
                                    ctypes.POINTER(_L), ctypes.POINTER(_I)]),
     "spff_r2u_dice_loss_ws_bytes": (_S, [_I, _I]),
     "spff_r2u_dice_loss": (_I, [_P, _P, _I, _L, _I, _I, _I, _P, _P, _P, _P]),
+    # ResUNet++ variant
+    "spff_rupp_create": (_I, [ctypes.POINTER(spff_rupp_cfg), ctypes.POINTER(_P)]),
+    "spff_rupp_destroy": (None, [_P]),
+    "spff_rupp_num_params": (_I, [_P]),
+    "spff_rupp_param_info": (_I, [_P, _I, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(_I),
+                                  ctypes.POINTER(_L), ctypes.POINTER(_L), ctypes.POINTER(_L)]),
+    "spff_rupp_param_floats": (_L, [_P]),
+    "spff_rupp_workspace_bytes": (_S, [_P]),
+    "spff_rupp_forward": (_I, [_P, _P, _P, _P, _P, _P]),
+    "spff_rupp_backward": (_I, [_P, _P, _P, _P, _P, _P]),
+    "spff_rupp_saved_tensor": (_I, [_P, _P, ctypes.c_char_p, ctypes.POINTER(_P),
+                                    ctypes.POINTER(_L), ctypes.POINTER(_I)]),
+    "spff_rupp_loss_ws_bytes": (_S, [_I, _I]),
+    "spff_rupp_loss": (_I, [_P, _P, _I, _L, _I, _I, _I, _I, ctypes.c_double, ctypes.c_double,
+                            _P, _P, _P, _P]),
+    "spff_conv3d_dil_ws_bytes": (_S, [_I, _I]),
+    "spff_conv3d_dil_fwd": (_I, [_P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
+    "spff_conv3d_dil_dgrad": (_I, [_P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
+    "spff_conv3d_dil_wgrad": (_I, [_P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
     # SwinUNETR variant (BASELINE config 5)
     "spff_swin_create": (_I, [ctypes.POINTER(spff_swin_cfg), ctypes.POINTER(_P)]),
     "spff_swin_destroy": (None, [_P]),
@@ -1067,6 +1094,130 @@ def r2u_dice_loss_forward(logits_cl: torch.Tensor, labels: torch.Tensor, K: int,
                                    int(ignore_index) if ignore_index is not None else 0,
                                    _ptr(out4), _ptr(dl), _ptr(ws), _stream(dev)),
           "spff_r2u_dice_loss")
+    return out4, dl
+
+
+class RUPPPlan:
+    """Engine plan of the ResUNet++ variant (include/spff.h spff_rupp_*): residual units,
+    ASPP bottleneck, SE and attention-gated skips + the 1x1x1 head of
+    LitResUNetPP3D_Published.  Parameters are one flat fp32 buffer in the Lit module's
+    named_parameters() order and names (``params``); D, H and W are multiples of 16 (the
+    wrapper pads and crops)."""
+
+    def __init__(self, batch, in_ch, depth, height, width, num_classes, base=16,
+                 device=None, math=None):
+        math = default_math() if math is None else math
+        if math not in MATH_NAMES:
+            raise SpffError(f"math={math!r}: expected one of {sorted(MATH_NAMES)}")
+        cfg = spff_rupp_cfg()
+        cfg.batch, cfg.in_ch, cfg.depth, cfg.height, cfg.width = batch, in_ch, depth, height, width
+        cfg.num_classes, cfg.base = num_classes, base
+        cfg.math = MATH_NAMES[math]
+        self.cfg, self.math, self.device = cfg, math, device
+        L = lib()
+        h = ctypes.c_void_p()
+        check(L.spff_rupp_create(ctypes.byref(cfg), ctypes.byref(h)), "spff_rupp_create")
+        self._h = h
+        self.params: List[Tuple[str, Tuple[int, ...], int, int]] = []
+        for i in range(L.spff_rupp_num_params(h)):
+            name, nd = ctypes.c_char_p(), ctypes.c_int()
+            shape, off, n = (ctypes.c_int64 * 5)(), ctypes.c_int64(), ctypes.c_int64()
+            check(L.spff_rupp_param_info(h, i, ctypes.byref(name), ctypes.byref(nd), shape,
+                                         ctypes.byref(off), ctypes.byref(n)),
+                  "spff_rupp_param_info")
+            self.params.append((name.value.decode(), tuple(shape[k] for k in range(nd.value)),
+                                off.value, n.value))
+        self.nfloats = int(L.spff_rupp_param_floats(h))
+        self.ws_bytes = int(L.spff_rupp_workspace_bytes(h))
+        self._ws: Optional[torch.Tensor] = None
+        self.generation = 0
+
+    def __del__(self):
+        try:
+            if getattr(self, "_h", None) is not None and _lib is not None:
+                _lib.spff_rupp_destroy(self._h)
+        except Exception:
+            pass
+
+    def workspace(self, device) -> torch.Tensor:
+        if self._ws is None or self._ws.device != device:
+            self._ws = _alloc_workspace(self, device)
+        return self._ws
+
+    def forward(self, x: torch.Tensor, flat: torch.Tensor,
+                out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """x [B,Cin,D,H,W] fp32 -> logits channel-last [B,D,H,W,K]."""
+        c = self.cfg
+        require_device(x, "ResUNet++ forward")
+        if tuple(x.shape) != (c.batch, c.in_ch, c.depth, c.height, c.width):
+            raise SpffError(f"input shape {tuple(x.shape)} does not match plan")
+        if x.dtype != torch.float32:
+            raise SpffError("the engine computes in fp32; got " + str(x.dtype))
+        x = x.contiguous()
+        if out is None:
+            out = torch.empty((c.batch, c.depth, c.height, c.width, c.num_classes),
+                              dtype=torch.float32, device=x.device)
+        ws = self.workspace(x.device)
+        self.generation += 1
+        check(lib().spff_rupp_forward(self._h, _ptr(x), _ptr(flat), _ptr(out), _ptr(ws),
+                                      _stream(x.device)), "spff_rupp_forward")
+        return out
+
+    def backward(self, dlogits_cl: torch.Tensor, flat: torch.Tensor,
+                 grad_hook=None) -> torch.Tensor:
+        """``grad_hook`` as UNet3DPlan.backward: the whole gradient at once."""
+        dlogits_cl = dlogits_cl.contiguous()
+        dflat = torch.empty(self.nfloats, dtype=torch.float32, device=dlogits_cl.device)
+        ws = self.workspace(dlogits_cl.device)
+        check(lib().spff_rupp_backward(self._h, _ptr(dlogits_cl), _ptr(flat), _ptr(dflat),
+                                       _ptr(ws), _stream(dlogits_cl.device)),
+              "spff_rupp_backward")
+        _whole_buffer_hook(grad_hook, dflat)
+        return dflat
+
+    def saved(self, name: str) -> torch.Tensor:
+        ws = self._ws
+        if ws is None:
+            raise SpffError("no forward has run")
+        ptr, nv, ch = ctypes.c_void_p(), ctypes.c_int64(), ctypes.c_int()
+        check(lib().spff_rupp_saved_tensor(self._h, _ptr(ws), name.encode(), ctypes.byref(ptr),
+                                           ctypes.byref(nv), ctypes.byref(ch)),
+              "spff_rupp_saved_tensor")
+        off = ptr.value - ws.data_ptr()
+        n = nv.value * ch.value
+        return ws[off:off + 4 * n].view(torch.float32).view(nv.value, ch.value).clone()
+
+
+def get_rupp_plan(owner=None, tag: str = "", **kw) -> RUPPPlan:
+    """ResUNet++ plans, owned like get_plan."""
+    key = ("rupp", kw["batch"], kw["in_ch"], kw["depth"], kw["height"], kw["width"],
+           kw["num_classes"], kw.get("base", 16), kw.get("math") or default_math())
+    return _owned_plan(owner, "rupp:" + tag, key, lambda: RUPPPlan(**kw))
+
+
+def rupp_loss_forward(logits_cl: torch.Tensor, labels: torch.Tensor, K: int,
+                      ignore_index: Optional[int], include_bg: bool = False,
+                      ce_weight: float = 1.0, dice_weight: float = 1.0):
+    """dice_ce_loss_with_metrics (LitResUNetPP3D_Published._loss) on the HIP kernels:
+    returns (out4 = [ce, loss, dice_mean, N_valid], dlogits_cl).  Dice sums are pooled over
+    the whole batch; ``ignore_index`` None: no voxel is masked."""
+    require_device(logits_cl, "ResUNet++ loss")
+    logits_cl = logits_cl.contiguous()
+    B = logits_cl.shape[0]
+    labels = labels.to(device=logits_cl.device, dtype=torch.int64).contiguous()
+    V = labels.numel()
+    if logits_cl.numel() != V * K or V % B:
+        raise SpffError(f"logits ({tuple(logits_cl.shape)}) / labels ({tuple(labels.shape)}) mismatch")
+    dev = logits_cl.device
+    out4 = torch.empty(4, dtype=torch.float32, device=dev)
+    dl = torch.empty_like(logits_cl)
+    ws = torch.empty(int(lib().spff_rupp_loss_ws_bytes(B, K)), dtype=torch.uint8, device=dev)
+    check(lib().spff_rupp_loss(_ptr(logits_cl), _ptr(labels), B, V // B, K,
+                               int(ignore_index is not None),
+                               int(ignore_index) if ignore_index is not None else 0,
+                               int(bool(include_bg)), float(ce_weight), float(dice_weight),
+                               _ptr(out4), _ptr(dl), _ptr(ws), _stream(dev)),
+          "spff_rupp_loss")
     return out4, dl
 
 

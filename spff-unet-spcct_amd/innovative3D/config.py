@@ -10,9 +10,10 @@ engine implements.  Differences, all deliberate:
   directories are created by whoever writes to them (train.py);
 * ``INNOVATIVE3D_VARIANT`` actually selects (SURVEY F11): ``selected_variants()``;
 * of the non-SPCT baselines "3DUNet" (BASELINE config 3, SURVEY §8(f) rank 2:
-  Cicek3DUNet + depth adapter), "SwinUNETR" (BASELINE config 5, §8(f) rank 3) and
+  Cicek3DUNet + depth adapter), "ResUNet++" (residual units, ASPP, SE and
+  attention gates; Dice + CE), "SwinUNETR" (BASELINE config 5, §8(f) rank 3) and
   "R2UNet3D" (the recurrent residual U-Net with its Dice-only loss) are
-  registered, all on the engine; UNETR and ResUNet++ are not built (SURVEY §8);
+  registered, all on the engine; only UNETR is not built (SURVEY §8);
 * the DICOM data module (``MultiDicomDataModule3D``) is the device-resident
   one of innovative3D/datasets.py (resize, ROI rasterisation and TrainGridAug as
   HIP kernels); DICOM files are decoded by pydicom when installed, else by the native
@@ -133,6 +134,15 @@ def make_cicek_depth_adapter_sgd_wce():
 
 _add_variant("3DUNet", make_cicek_depth_adapter_sgd_wce, MultiDicomDataModule3D,
              CHECKPOINT_DIR / "3DUNet")
+
+# ResUNet++ (config.py:391-404): residual units, ASPP bottleneck, SE + attention-gated
+# skips; Dice + CE, Adam.
+_add_variant("ResUNet++",
+             build_class("LitResUNetPP3D_Published", num_classes=NUM_CLASSES, in_channels=1,
+                         base_features=16, include_bg_in_dice=False, ce_weight=0.5,
+                         dice_weight=0.5, lr=1e-4, weight_decay=1e-5, ignore_index=IGNORE_INDEX,
+                         pad_multiple=16),
+             MultiDicomDataModule3D, CHECKPOINT_DIR / "ResUNet++")
 
 # SwinUNETR (config.py:366-386; BASELINE config 5).  build_class drops the kwargs
 # LitSwinUNETR_Published does not take (window_size), exactly like the reference.

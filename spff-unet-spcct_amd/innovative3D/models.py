@@ -1311,3 +1311,227 @@ class LitR2UNet3D_Published(pl.LightningModule):
     def configure_optimizers(self):
         return torch.optim.Adam(self.parameters(), lr=self.hparams.lr,
                                 weight_decay=self.hparams.weight_decay)
+
+
+# ============================================================================
+# ResUNet++ (registry "ResUNet++"): LitResUNetPP3D_Published around
+# ResUNetPP3D_backbone -- residual units, an ASPP bottleneck, SE on the skips and
+# attention gates at the concats -- on the engine's spff_rupp plan
+# (csrc/resunetpp.hip).  The module tree below only holds parameters under the
+# reference's state-dict names; backbone and head run as one plan from the Lit
+# module's forward.  Parity: tests/golden/rupp_*.npz.
+# ============================================================================
+class ResidualUnit3D(nn.Module):
+    """out = relu(IN2(c2(relu(IN1(c1(x))))) + skip(x)); skip is a bias-free 1x1x1 conv, or
+    the identity when cin == cout."""
+
+    def __init__(self, cin: int, cout: int):
+        super().__init__()
+        self.c1 = nn.Conv3d(cin, cout, 3, padding=1, bias=False)
+        self.n1 = nn.InstanceNorm3d(cout, affine=True)
+        self.c2 = nn.Conv3d(cout, cout, 3, padding=1, bias=False)
+        self.n2 = nn.InstanceNorm3d(cout, affine=True)
+        self.act = nn.ReLU(inplace=True)
+        self.skip = nn.Conv3d(cin, cout, 1, bias=False) if cin != cout else nn.Identity()
+
+
+class ASPP3D(nn.Module):
+    """Four bias-free 3x3x3 convs of one input (dilation = padding = d), concatenated in
+    branch order, then a bias-free 1x1x1 conv and a ReLU."""
+
+    def __init__(self, in_channels: int, out_channels: int, dilations=(1, 2, 4, 8)):
+        super().__init__()
+        self.branches = nn.ModuleList([
+            nn.Conv3d(in_channels, out_channels, 3, padding=d, dilation=d, bias=False)
+            for d in dilations])
+        self.proj = nn.Sequential(
+            nn.Conv3d(len(dilations) * out_channels, out_channels, 1, bias=False),
+            nn.ReLU(inplace=True))
+
+
+class SE3D(nn.Module):
+    """x * sigmoid(W2 relu(W1 mean(x) + b1) + b2), hidden = max(1, channels // reduction)."""
+
+    def __init__(self, channels: int, reduction: int = 16):
+        super().__init__()
+        hidden = max(1, channels // reduction)
+        self.pool = nn.AdaptiveAvgPool3d(1)
+        self.fc = nn.Sequential(nn.Conv3d(channels, hidden, 1, bias=True), nn.ReLU(inplace=True),
+                                nn.Conv3d(hidden, channels, 1, bias=True), nn.Sigmoid())
+
+
+class AttentionGate3d(nn.Module):
+    """forward(x_skip, g) = x_skip * sigmoid(psi(relu(W_x x_skip + W_g g))): the gate
+    multiplies its first argument."""
+
+    def __init__(self, g_c: int, x_c: int, inter_c: Optional[int] = None):
+        super().__init__()
+        if inter_c is None:
+            inter_c = min(x_c, g_c)
+        self.W_x = nn.Conv3d(x_c, inter_c, 1, 1, 0, bias=True)
+        self.W_g = nn.Conv3d(g_c, inter_c, 1, 1, 0, bias=True)
+        self.psi = nn.Conv3d(inter_c, 1, 1, 1, 0, bias=True)
+        nn.init.constant_(self.psi.bias, 0.0)
+        self.relu = nn.ReLU(inplace=True)
+        self.sigmoid = nn.Sigmoid()
+
+
+class ResUNetPP3D_backbone(nn.Module):
+    """Residual-unit encoder (channels base * {1, 2, 4, 8, 16}, MaxPool3d(2)), ASPP
+    bottleneck, SE on the encoder outputs and an attention gate at each concat but the
+    last.  The backbone calls ``ag(u, se(e))``, so the gate scales the up-sampled tensor and
+    the decoder reads cat([u, u * att]).  A parameter container: the engine plan covers
+    backbone and head together, so it runs from LitResUNetPP3D_Published.forward."""
+
+    def __init__(self, in_channels: int = 1, base: int = 16):
+        super().__init__()
+        c = [base, base * 2, base * 4, base * 8, base * 16]
+        self.in_channels, self.base = int(in_channels), int(base)
+        self.e1 = ResidualUnit3D(in_channels, c[0]); self.p1 = nn.MaxPool3d(2)  # noqa: E702
+        self.e2 = ResidualUnit3D(c[0], c[1]); self.p2 = nn.MaxPool3d(2)  # noqa: E702
+        self.e3 = ResidualUnit3D(c[1], c[2]); self.p3 = nn.MaxPool3d(2)  # noqa: E702
+        self.e4 = ResidualUnit3D(c[2], c[3]); self.p4 = nn.MaxPool3d(2)  # noqa: E702
+        self.b_aspp_in = ResidualUnit3D(c[3], c[4])
+        self.b_aspp = ASPP3D(c[4], c[4])
+        self.b_aspp_out = ResidualUnit3D(c[4], c[4])
+        for i in range(4):
+            setattr(self, f"se{i + 1}", SE3D(c[i]))
+        for i, n in ((3, "4"), (2, "3"), (1, "2"), (0, "1")):
+            setattr(self, "up" + n, nn.ConvTranspose3d(c[i + 1], c[i], 2, 2))
+            if i > 0:
+                setattr(self, "ag" + n, AttentionGate3d(g_c=c[i], x_c=c[i], inter_c=c[i] // 2))
+            setattr(self, "d" + n, ResidualUnit3D(c[i] + c[i], c[i]))
+        self.out_ch = c[0]
+
+    def forward(self, x):
+        raise NotImplementedError("ResUNetPP3D_backbone holds parameters only: the engine plan "
+                                  "runs backbone and head together "
+                                  "(LitResUNetPP3D_Published.forward)")
+
+
+class _RUPPFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, plan, flat, grad_hook, *params):
+        logits_cl = plan.forward(x, flat)
+        ctx.plan, ctx.gen, ctx.flat, ctx.grad_hook = plan, plan.generation, flat, grad_hook
+        plan._pending_gen = plan.generation if any(ctx.needs_input_grad) else None
+        ctx.param_ids = tuple(id(p) for p in params)
+        ctx.slices = [(off, n, shape) for (_name, shape, off, n) in plan.params]
+        return logits_cl.permute(0, 4, 1, 2, 3)
+
+    @staticmethod
+    def backward(ctx, g):
+        plan = ctx.plan
+        if plan.generation != ctx.gen:
+            raise E.SpffError("ResUNet++ engine: another forward ran on this model before the "
+                              "backward of this one; the engine keeps one forward's activations")
+        g_cl = g.permute(0, 2, 3, 4, 1).contiguous()
+        dflat = plan.backward(g_cl, ctx.flat, grad_hook=ctx.grad_hook)
+        plan._pending_gen = None
+        _mark_covered(ctx.grad_hook, ctx.param_ids)
+        grads = [dflat[o:o + n].view(s) for (o, n, s) in ctx.slices]
+        return (None, None, None, None, *grads)
+
+
+class _RUPPLoss(torch.autograd.Function):
+    """(loss, out4 = [ce, loss, dice_mean, N_valid]); only the loss carries a gradient."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, K, ignore_index, include_bg, ce_weight, dice_weight):
+        lcl = logits.permute(0, 2, 3, 4, 1).contiguous()
+        out4, dl = E.rupp_loss_forward(lcl, labels, K, ignore_index, include_bg, ce_weight,
+                                       dice_weight)
+        ctx.dl = dl
+        ctx.mark_non_differentiable(out4)
+        return out4[1].clone(), out4
+
+    @staticmethod
+    def backward(ctx, g, _g4=None):
+        dl = ctx.dl
+        E.scale_(dl, g.reshape(1))
+        return dl.permute(0, 4, 1, 2, 3), None, None, None, None, None, None
+
+
+class LitResUNetPP3D_Published(pl.LightningModule):
+    """Registry "ResUNet++": replicate-pad D, H, W to multiples of ``pad_multiple`` ->
+    ResUNetPP3D_backbone -> 1x1x1 head -> centre crop (padding and cropping are torch
+    plumbing, backbone and head one engine plan); batch-pooled soft Dice + CE on the HIP loss
+    kernels; Adam.  ``math`` (attribute) selects the conv arithmetic of new plans."""
+
+    def __init__(self, num_classes: int, in_channels: int = 1, base_features: int = 16,
+                 include_bg_in_dice: bool = False, ignore_index: Optional[int] = None,
+                 ce_weight: float = 0.5, dice_weight: float = 0.5, lr: float = 1e-3,
+                 weight_decay: float = 1e-5, pad_multiple: int = 16):
+        super().__init__()
+        if int(num_classes) == 1:
+            raise NotImplementedError("LitResUNetPP3D_Published: num_classes == 1 is not built "
+                                      "on the engine (the loss kernels take 2..32 classes)")
+        if int(pad_multiple) < 16 or int(pad_multiple) % 16:
+            raise NotImplementedError("LitResUNetPP3D_Published: pad_multiple must be a multiple "
+                                      "of 16 (four poolings whose outputs are concatenated with "
+                                      "the up-convolutions)")
+        self.save_hyperparameters({
+            "num_classes": num_classes, "in_channels": in_channels,
+            "base_features": base_features, "include_bg_in_dice": include_bg_in_dice,
+            "ignore_index": ignore_index, "ce_weight": ce_weight, "dice_weight": dice_weight,
+            "lr": lr, "weight_decay": weight_decay, "pad_multiple": pad_multiple})
+        self.backbone = ResUNetPP3D_backbone(in_channels=in_channels, base=base_features)
+        self.head = nn.Conv3d(self.backbone.out_ch, num_classes, 1)
+        self._flat = None
+
+    def _plan(self, x):
+        B, C, D, H, W = x.shape
+        bb = self.backbone
+        if C != bb.in_channels:
+            raise ValueError(f"expected {bb.in_channels} input channels, got {C}")
+        return E.get_rupp_plan(batch=B, in_ch=C, depth=D, height=H, width=W,
+                               num_classes=int(self.hparams.num_classes), base=bb.base,
+                               device=x.device, math=getattr(self, "math", None), owner=self)
+
+    _engine_params = SwinUNETR._engine_params
+    _ensure_flat = SwinUNETR._ensure_flat
+
+    def forward(self, x):
+        x = _pick_first_if_seq(x)
+        E.require_device(x, "LitResUNetPP3D_Published.forward")
+        if x.ndim == 4:
+            x = x.unsqueeze(1)
+        x_pad, orig = _pad_to_mult16_3d(x.float(), multiple=int(self.hparams.pad_multiple))
+        plan = self._plan(x_pad)
+        params = self._engine_params(plan)
+        flat = self._ensure_flat(plan, params, x_pad.device)
+        if torch.is_grad_enabled() and any(p.requires_grad for p in params):
+            y = _RUPPFunction.apply(x_pad, plan, flat, getattr(self, "grad_hook", None), *params)
+        else:
+            y = plan.forward(x_pad, flat).permute(0, 4, 1, 2, 3)
+        return _center_crop_3d(y, orig)
+
+    def _loss(self, logits, y):
+        """dice_ce_loss_with_metrics: (loss, macro_dice, ce); Dice sums pooled over the batch."""
+        hp = self.hparams
+        if y.ndim == 5 and y.size(1) == 1:
+            y = y[:, 0]
+        loss, out4 = _RUPPLoss.apply(
+            logits, y, int(logits.shape[1]),
+            None if hp.ignore_index is None else int(hp.ignore_index),
+            bool(hp.include_bg_in_dice), float(hp.ce_weight), float(hp.dice_weight))
+        return loss, out4[2], out4[0]
+
+    def _step(self, batch, stage):
+        x, y = batch if isinstance(batch, (list, tuple)) else (batch["image"], batch["label"])
+        logits = self(x)
+        y = torch.as_tensor(y).to(logits.device)
+        loss, macro_dice, _ = self._loss(logits, y)
+        self.log(f"{stage}_loss", loss, on_epoch=True, prog_bar=True, sync_dist=True)
+        self.log(f"{stage}_macro_dice", macro_dice, on_epoch=True, prog_bar=True, sync_dist=True)
+        return loss
+
+    def training_step(self, batch, _):
+        return self._step(batch, "train")
+
+    def validation_step(self, batch, _):
+        return self._step(batch, "val")
+
+    def configure_optimizers(self):
+        return torch.optim.Adam(self.parameters(), lr=self.hparams.lr,
+                                weight_decay=self.hparams.weight_decay)
