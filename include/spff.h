@@ -178,7 +178,9 @@ int spff_prof_collect(spff_plan* plan, double* out, int nclass);
  * gradient, weight gradient) on the stream it runs on, whichever plan or op entry point
  * issues it (the 3DUNet / SwinUNETR plans included).  collect: out[4 c + {0,1,2,3}] =
  * (ms, algorithmic fp32 flops 2 V Cin Cout T, launches, 0) for class c = 0 fwd, 1 dgrad,
- * 2 wgrad; synchronises on the recorded events and resets the record. */
+ * 2 wgrad; synchronises on the recorded events and resets the record.  The UNETR plan also
+ * brackets its token path (class 5: patch embedding, ViT blocks, final norm, forward and
+ * backward) and its resampling passes (class 6), without flops. */
 int spff_conv_prof_enable(int on);
 int spff_conv_prof_collect(double* out, int nclass);
 
@@ -483,6 +485,74 @@ size_t spff_swin_loss_ws_bytes(int batch, int num_classes);
 int spff_swin_loss(const float* logits, const int64_t* labels, int batch, int64_t vox_per_sample,
                    int num_classes, int ignore_index, int include_bg, double ce_weight,
                    float* out4, float* dlogits, void* ws, void* stream);
+
+/* ------------------------------------------------------------------------
+ * UNETR variant (registry "UNETR", config.py:316-339 -> LitUNETR_Published /
+ * UNETR_Published, models.py:984-1115, i.e. MONAI 1.5.2 UNETR: 16^3 conv patch
+ * embedding, learnable position embedding, twelve ViT blocks, InstanceNorm,
+ * res_block).  Replaces the wrapper's resample -> UNETR -> resample (forward steps
+ * 3-5) and its autograd backward; the loss is spff_swin_loss (the reference's
+ * _loss is the Swin one line for line).  Parameters: a flat fp32 buffer in
+ * MONAI's state-dict order / names without the "net.net." prefix
+ * (spff_unetr_param_info); the cross-attention parameters that MONAI >= 1.4
+ * registers in every block and never uses on this path are not part of it.
+ * Parity is unpinned (MONAI is not available offline): every statement about
+ * MONAI's UNETR here is an assumption restated in tests/_unetr_oracle.py.
+ * ------------------------------------------------------------------------ */
+typedef struct spff_unetr_cfg {
+  int batch, in_ch, depth, height, width; /* the padded input [B][Cin][D][H][W], multiples of 16;
+                        Cin = 1, the registry's: no other patch-embedding width is tested */
+  int img[3];        /* the network grid (96, 96, 96), multiples of the 16^3 patch; at most 512
+                        tokens, the attention kernels' two 256-row LDS chunks */
+  int num_classes;   /* K (<= 32: spff_swin_loss) */
+  int feature_size;  /* 16; a multiple of 8 (the conv kernels' channel tiles) */
+  int hidden;        /* 768; <= 768 because the LayerNorm kernels hold a row as 12 channels
+                        in each of a wave's 64 lanes */
+  int mlp_dim;       /* 3072; a multiple of 4 (16-byte row loads of the Linear GEMMs) */
+  int heads;         /* 12; hidden / heads in {16, 32, 64}, the attention kernels' instances */
+  int math;          /* SPFF_MATH_* for the 3x3x3 convolutions */
+  int reserved[6];   /* zero */
+} spff_unetr_cfg;
+
+typedef struct spff_unetr spff_unetr;
+
+int spff_unetr_create(const spff_unetr_cfg* cfg, spff_unetr** out);
+void spff_unetr_destroy(spff_unetr* net);
+int spff_unetr_num_params(const spff_unetr* net);
+int spff_unetr_param_info(const spff_unetr* net, int i, const char** name, int* ndim,
+                          int64_t shape[5], int64_t* offset, int64_t* numel);
+int64_t spff_unetr_param_floats(const spff_unetr* net);
+size_t spff_unetr_workspace_bytes(const spff_unetr* net);
+/* forward: x [B][Cin][D][H][W] -> logits [B][D][H][W][K] (channel-last); when (D, H, W)
+ * differs from img the input is resampled to img and the logits back (trilinear,
+ * align_corners=False) inside */
+int spff_unetr_forward(spff_unetr* net, const float* x, const float* params, float* logits,
+                       void* workspace, void* stream);
+/* backward of the last forward: dlogits [B][D][H][W][K] -> dparams (every entry written) */
+int spff_unetr_backward(spff_unetr* net, const float* dlogits, const float* params,
+                        float* dparams, void* workspace, void* stream);
+/* "tok", "h3", "h6", "h9", "hN", "enc1" .. "enc4", "dec5" .. "dec2", "block<i>.qkv|O|x1|out",
+ * "<residual block>.y1|a1|y2|y3|out" */
+int spff_unetr_saved_tensor(const spff_unetr* net, void* workspace, const char* name,
+                            const float** ptr, int64_t* rows, int* channels);
+
+/* Global multi-head self-attention (vit_attn.hip): qkv [batch tokens][3 hidden] split as
+ * (qkv, head, d), scale d^-0.5, softmax over all tokens of the sample; out [batch tokens]
+ * [hidden], lse [batch][heads][tokens].  hidden / heads in {16, 32, 64}, tokens <= 512,
+ * else SPFF_EINVAL.  The backward writes all of dqkv; ws >= spff_vit_attn_ws_bytes. */
+size_t spff_vit_attn_ws_bytes(int batch, int tokens, int heads);
+int spff_vit_attn_fwd(const float* qkv, int batch, int tokens, int hidden, int heads, float* out,
+                      float* lse, void* stream);
+int spff_vit_attn_bwd(const float* qkv, const float* out, const float* dout, const float* lse,
+                      int batch, int tokens, int hidden, int heads, float* dqkv, void* ws,
+                      void* stream);
+/* ATen upsample_trilinear3d (align_corners=False, output size given) on channel-last rows
+ * x [B][din][hin][win][C] -> y [B][dout][hout][wout][C], and its adjoint dy -> dx (gather
+ * form, fixed order) */
+int spff_resize3d_fwd(const float* x, float* y, int batch, int channels, int din, int hin,
+                      int win, int dout, int hout, int wout, void* stream);
+int spff_resize3d_bwd(const float* dy, float* dx, int batch, int channels, int din, int hin,
+                      int win, int dout, int hout, int wout, void* stream);
 
 /* ------------------------------------------------------------------------
  * Training data path on the device (oracle/data_oracle.py).

@@ -1893,7 +1893,7 @@ std::vector<CProfRec> g_cprof;
 size_t g_cprof_n = 0;
 bool g_cprof_on = false;
 }  // namespace
-CProf::CProf(int cls, double flops, hipStream_t s) {
+CProf::CProf(int cls, double flops, hipStream_t s) : st(s) {
   if (!g_cprof_on) return;
   if (g_cprof_n == g_cprof.size()) {
     CProfRec r;

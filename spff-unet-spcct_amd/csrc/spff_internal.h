@@ -188,13 +188,20 @@ hipError_t conv3d_wgrad(const Src2& x, const float* dy, int lddy, float* dw, Vol
                         const unsigned* xmax = nullptr, const unsigned* ymax = nullptr);
 size_t conv3d_wgrad_x_ws_bytes(Vol vol, int KD, int Cin, int Cout);
 bool debug_split_wgrad();  // SPFF_DEBUG_SPLIT (conv3d_x.hip)
-// Library-wide conv timing (spff_conv_prof_*, conv3d_x.hip): when on, conv3d_run and
+// Library-wide timing (spff_conv_prof_*, conv3d_x.hip): when on, conv3d_run and
 // conv3d_wgrad bracket their launches with HIP events on the stream they run on, whichever
-// plan (SPFF, 3DUNet, SwinUNETR) or the op-level ABI calls them.  Classes: 0 fwd,
-// 1 dgrad, 2 wgrad; flops = 2 V Cin Cout T (algorithmic, fp32).
+// plan or op-level entry point calls them.  Classes: 0 conv fwd, 1 conv dgrad, 2 conv wgrad
+// (flops = 2 V Cin Cout T, algorithmic, fp32); 3, 4 the loss pass and its kernel (loss.hip);
+// 5 the UNETR plan's token path, 6 its resampling passes (unetr.hip; no flops).  A bracket
+// left open (an early error return) is closed by the destructor on the same stream, so a
+// later collect never meets a record without its end event.
 struct CProf {
   int rec = -1;
+  hipStream_t st = nullptr;
   CProf(int cls, double flops, hipStream_t s);
+  CProf(const CProf&) = delete;
+  CProf& operator=(const CProf&) = delete;
+  ~CProf() { end(st); }
   void end(hipStream_t s);
 };
 void conv_prof_enable(bool on);

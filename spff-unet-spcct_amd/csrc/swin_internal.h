@@ -95,4 +95,36 @@ hipError_t swin_attn_bwd(const float* qkv, const float* bqkv, const float* table
                          float* dqkv, float* dtable, float* dbqkv, float* ws, hipStream_t s);
 hipError_t swin_attn_pad_grad(const AttnGeo& g, const float* ws, float* dbqkv, hipStream_t s);
 
+// ------------------------------------------------ ViT global attention --
+// vit_attn.hip: every token of a sample attends to all n tokens (n <= 512), heads of
+// hd in {16, 32, 64} channels, scale hd ** -0.5, no bias; fp32-input MFMA throughout.
+struct VitGeo {
+  int B, n, C, nh, hd;
+  float scale;
+};
+VitGeo vit_geo(int B, int n, int C, int nh);
+// null when the geometry is supported, else the reason
+const char* vit_geo_check(int B, int n, int C, int nh);
+// qkv [B n][3C] split as (qkv, head, d); O [B n][C]; lse [B][nh][n]
+hipError_t vit_attn_fwd(const float* qkv, const VitGeo& g, float* O, float* lse, hipStream_t s);
+size_t vit_attn_ws_bytes(const VitGeo& g);
+// dO [B n][C] -> dqkv [B n][3C], every entry written
+hipError_t vit_attn_bwd(const float* qkv, const float* O, const float* dO, const float* lse,
+                        const VitGeo& g, float* dqkv, float* ws, hipStream_t s);
+
+// ------------------------------------------------ trilinear resampling --
+// resize3d.hip: ATen upsample_trilinear3d (align_corners=False, size given) on channel-last
+// rows x [B][Di][Hi][Wi][C] -> y [B][Do][Ho][Wo][C], and its adjoint dy -> dx in gather form
+hipError_t resize3d_fwd(const float* x, float* y, int B, int C, int Di, int Hi, int Wi, int Do,
+                        int Ho, int Wo, hipStream_t s);
+hipError_t resize3d_bwd(const float* dy, float* dx, int B, int C, int Di, int Hi, int Wi, int Do,
+                        int Ho, int Wo, hipStream_t s);
+// the same forward from an NCDHW input into channel-last rows of ldy >= C floats (rest zero)
+hipError_t resize3d_ncdhw_in(const float* x, float* y, int ldy, int B, int C, int Di, int Hi,
+                             int Wi, int Do, int Ho, int Wo, hipStream_t s);
+// x [B][D][H][W][ldx] -> rows [B D/16 H/16 W/16][cin 4096] in the (c, kd, kh, kw) order of a
+// Conv3d(k = s = 16) weight
+hipError_t patchify16(const float* x, int ldx, int cin, int B, int D, int H, int W, float* rows,
+                      hipStream_t s);
+
 }  // namespace spff

@@ -80,6 +80,16 @@ class spff_swin_cfg(ctypes.Structure):
     ]
 
 
+class spff_unetr_cfg(ctypes.Structure):
+    _fields_ = [
+        ("batch", ctypes.c_int), ("in_ch", ctypes.c_int), ("depth", ctypes.c_int),
+        ("height", ctypes.c_int), ("width", ctypes.c_int), ("img", ctypes.c_int * 3),
+        ("num_classes", ctypes.c_int), ("feature_size", ctypes.c_int), ("hidden", ctypes.c_int),
+        ("mlp_dim", ctypes.c_int), ("heads", ctypes.c_int), ("math", ctypes.c_int),
+        ("reserved", ctypes.c_int * 6),
+    ]
+
+
 # spff_coll (include/spff.h): the shard group's collectives, called back by the engine
 ALLREDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
                                 ctypes.c_int, ctypes.c_void_p)
@@ -230,6 +240,23 @@ _SIGS = {
     "spff_swin_saved_tensor": (_I, [_P, _P, ctypes.c_char_p, ctypes.POINTER(_P),
                                     ctypes.POINTER(_L), ctypes.POINTER(_I)]),
     "spff_swin_loss_ws_bytes": (_S, [_I, _I]),
+    # UNETR variant
+    "spff_unetr_create": (_I, [ctypes.POINTER(spff_unetr_cfg), ctypes.POINTER(_P)]),
+    "spff_unetr_destroy": (None, [_P]),
+    "spff_unetr_num_params": (_I, [_P]),
+    "spff_unetr_param_info": (_I, [_P, _I, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(_I),
+                                   ctypes.POINTER(_L), ctypes.POINTER(_L), ctypes.POINTER(_L)]),
+    "spff_unetr_param_floats": (_L, [_P]),
+    "spff_unetr_workspace_bytes": (_S, [_P]),
+    "spff_unetr_forward": (_I, [_P, _P, _P, _P, _P, _P]),
+    "spff_unetr_backward": (_I, [_P, _P, _P, _P, _P, _P]),
+    "spff_unetr_saved_tensor": (_I, [_P, _P, ctypes.c_char_p, ctypes.POINTER(_P),
+                                     ctypes.POINTER(_L), ctypes.POINTER(_I)]),
+    "spff_vit_attn_ws_bytes": (_S, [_I, _I, _I]),
+    "spff_vit_attn_fwd": (_I, [_P, _I, _I, _I, _I, _P, _P, _P]),
+    "spff_vit_attn_bwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
+    "spff_resize3d_fwd": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "spff_resize3d_bwd": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     # data path
     "spff_rasterize_ellipses": (_I, [_P, _I, _I, _I, _I, _P, _P]),
     "spff_resize_bilinear_aa": (_I, [_P, _I, _I, _I, _P, _I, _I, _P, _P]),
@@ -977,6 +1004,184 @@ def swin_loss_forward(logits_cl: torch.Tensor, labels: torch.Tensor, K: int, ign
     return out4, dl
 
 
+class UNETRPlan:
+    """One spff_unetr plan (UNETR variant) + its workspace.  The plan's input is the padded
+    volume [B, Cin, depth, height, width]; when that differs from ``img`` the engine resamples
+    to ``img`` and the logits back."""
+
+    def __init__(self, batch, in_ch, depth, height, width, num_classes, img=(96, 96, 96),
+                 feature_size=16, hidden=768, mlp_dim=3072, heads=12, device=None, math=None):
+        math = math or default_math()
+        if math not in MATH_NAMES:
+            raise SpffError(f"math={math!r}: expected one of {sorted(MATH_NAMES)}")
+        cfg = spff_unetr_cfg()
+        cfg.batch, cfg.in_ch, cfg.depth, cfg.height, cfg.width = batch, in_ch, depth, height, width
+        for i, v in enumerate(img):
+            cfg.img[i] = int(v)
+        cfg.num_classes, cfg.feature_size = num_classes, feature_size
+        cfg.hidden, cfg.mlp_dim, cfg.heads = hidden, mlp_dim, heads
+        cfg.math = MATH_NAMES[math]
+        self.cfg, self.math, self.device = cfg, math, device
+        L = lib()
+        h = ctypes.c_void_p()
+        check(L.spff_unetr_create(ctypes.byref(cfg), ctypes.byref(h)), "spff_unetr_create")
+        self._h = h
+        self.params: List[Tuple[str, Tuple[int, ...], int, int]] = []
+        for i in range(L.spff_unetr_num_params(h)):
+            name, nd = ctypes.c_char_p(), ctypes.c_int()
+            shape, off, n = (ctypes.c_int64 * 5)(), ctypes.c_int64(), ctypes.c_int64()
+            check(L.spff_unetr_param_info(h, i, ctypes.byref(name), ctypes.byref(nd), shape,
+                                          ctypes.byref(off), ctypes.byref(n)),
+                  "spff_unetr_param_info")
+            self.params.append((name.value.decode(), tuple(shape[k] for k in range(nd.value)),
+                                off.value, n.value))
+        self.nfloats = int(L.spff_unetr_param_floats(h))
+        self.ws_bytes = int(L.spff_unetr_workspace_bytes(h))
+        self._ws: Optional[torch.Tensor] = None
+        self.generation = 0
+
+    def __del__(self):
+        try:
+            if getattr(self, "_h", None) is not None and _lib is not None:
+                _lib.spff_unetr_destroy(self._h)
+        except Exception:
+            pass
+
+    def workspace(self, device) -> torch.Tensor:
+        if self._ws is None or self._ws.device != device:
+            self._ws = _alloc_workspace(self, device)
+        return self._ws
+
+    def forward(self, x: torch.Tensor, flat: torch.Tensor,
+                out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """x [B,Cin,D,H,W] fp32 -> logits channel-last [B,D,H,W,K]."""
+        c = self.cfg
+        require_device(x, "UNETR forward")
+        if tuple(x.shape) != (c.batch, c.in_ch, c.depth, c.height, c.width):
+            raise SpffError(f"input shape {tuple(x.shape)} does not match plan")
+        if x.dtype != torch.float32:
+            raise SpffError("the engine computes in fp32; got " + str(x.dtype))
+        x = x.contiguous()
+        if out is None:
+            out = torch.empty((c.batch, c.depth, c.height, c.width, c.num_classes),
+                              dtype=torch.float32, device=x.device)
+        ws = self.workspace(x.device)
+        self.generation += 1
+        check(lib().spff_unetr_forward(self._h, _ptr(x), _ptr(flat), _ptr(out), _ptr(ws),
+                                       _stream(x.device)), "spff_unetr_forward")
+        return out
+
+    def backward(self, dlogits_cl: torch.Tensor, flat: torch.Tensor,
+                 dflat: Optional[torch.Tensor] = None, grad_hook=None) -> torch.Tensor:
+        """``grad_hook`` as UNet3DPlan.backward: the whole gradient at once."""
+        dlogits_cl = dlogits_cl.contiguous()
+        if dflat is None:
+            dflat = torch.empty(self.nfloats, dtype=torch.float32, device=dlogits_cl.device)
+        ws = self.workspace(dlogits_cl.device)
+        check(lib().spff_unetr_backward(self._h, _ptr(dlogits_cl), _ptr(flat), _ptr(dflat),
+                                        _ptr(ws), _stream(dlogits_cl.device)),
+              "spff_unetr_backward")
+        _whole_buffer_hook(grad_hook, dflat)
+        return dflat
+
+    def saved(self, name: str) -> torch.Tensor:
+        ws = self._ws
+        if ws is None:
+            raise SpffError("no forward has run")
+        ptr, nv, ch = ctypes.c_void_p(), ctypes.c_int64(), ctypes.c_int()
+        check(lib().spff_unetr_saved_tensor(self._h, _ptr(ws), name.encode(), ctypes.byref(ptr),
+                                            ctypes.byref(nv), ctypes.byref(ch)),
+              "spff_unetr_saved_tensor")
+        off = ptr.value - ws.data_ptr()
+        n = nv.value * ch.value
+        return ws[off:off + 4 * n].view(torch.float32).view(nv.value, ch.value).clone()
+
+
+def get_unetr_plan(owner=None, tag: str = "", **kw) -> UNETRPlan:
+    """UNETR plans, owned like get_plan."""
+    key = ("unetr", kw["batch"], kw["in_ch"], kw["depth"], kw["height"], kw["width"],
+           kw["num_classes"], tuple(kw.get("img", (96, 96, 96))), kw.get("feature_size", 16),
+           kw.get("hidden", 768), kw.get("mlp_dim", 3072), kw.get("heads", 12),
+           kw.get("math") or default_math())
+    return _owned_plan(owner, "unetr:" + tag, key, lambda: UNETRPlan(**kw))
+
+
+def _vit_shape(qkv: torch.Tensor, batch: int, heads: int) -> Tuple[int, int]:
+    """(tokens per sample, hidden) of qkv [batch * n, 3 * hidden]."""
+    if qkv.ndim != 2 or qkv.dtype != torch.float32 or batch < 1 or heads < 1 \
+            or qkv.shape[0] % batch or qkv.shape[1] % (3 * heads):
+        raise SpffError(f"qkv must be fp32 [batch * n, 3 * heads * d]; got {qkv.dtype} "
+                        f"{tuple(qkv.shape)} for batch {batch}, heads {heads}")
+    return qkv.shape[0] // batch, qkv.shape[1] // 3
+
+
+def vit_attn_fwd(qkv: torch.Tensor, batch: int, heads: int):
+    """qkv [B*n, 3C] fp32, split as (qkv, head, d) -> (O [B*n, C], lse [B, heads, n])."""
+    require_device(qkv, "vit_attn_fwd")
+    qkv = qkv.contiguous()
+    n, C = _vit_shape(qkv, batch, heads)
+    T = batch * n
+    O = torch.empty((T, C), dtype=torch.float32, device=qkv.device)
+    lse = torch.empty((batch, heads, n), dtype=torch.float32, device=qkv.device)
+    check(lib().spff_vit_attn_fwd(_ptr(qkv), batch, n, C, heads, _ptr(O), _ptr(lse),
+                                  _stream(qkv.device)), "spff_vit_attn_fwd")
+    return O, lse
+
+
+def vit_attn_bwd(qkv: torch.Tensor, O: torch.Tensor, dO: torch.Tensor, lse: torch.Tensor,
+                 batch: int, heads: int) -> torch.Tensor:
+    """-> dqkv [B*n, 3C] (every entry written)."""
+    require_device(qkv, "vit_attn_bwd")
+    qkv, O, dO, lse = qkv.contiguous(), O.contiguous(), dO.contiguous(), lse.contiguous()
+    n, C = _vit_shape(qkv, batch, heads)
+    for what, t, shape in (("O", O, (batch * n, C)), ("dO", dO, (batch * n, C)),
+                           ("lse", lse, (batch, heads, n))):
+        if tuple(t.shape) != shape or t.dtype != torch.float32 or t.device != qkv.device:
+            raise SpffError(f"vit_attn_bwd: {what} must be fp32 {shape} on {qkv.device}; got "
+                            f"{t.dtype} {tuple(t.shape)} on {t.device}")
+    dqkv = torch.empty_like(qkv)
+    ws = torch.empty(max(4, int(lib().spff_vit_attn_ws_bytes(batch, n, heads))), dtype=torch.uint8,
+                     device=qkv.device)
+    check(lib().spff_vit_attn_bwd(_ptr(qkv), _ptr(O), _ptr(dO), _ptr(lse), batch, n, C, heads,
+                                  _ptr(dqkv), _ptr(ws), _stream(qkv.device)), "spff_vit_attn_bwd")
+    return dqkv
+
+
+def resize3d_fwd(x_cl: torch.Tensor, size) -> torch.Tensor:
+    """x [B, D, H, W, C] channel-last fp32 -> [B, *size, C] (F.interpolate trilinear,
+    align_corners=False)."""
+    require_device(x_cl, "resize3d_fwd")
+    if x_cl.ndim != 5 or x_cl.dtype != torch.float32:
+        raise SpffError(f"resize3d_fwd: expected fp32 [B, D, H, W, C]; got {x_cl.dtype} "
+                        f"{tuple(x_cl.shape)}")
+    x_cl = x_cl.contiguous()
+    B, D, H, W, C = x_cl.shape
+    if len(tuple(size)) != 3 or min(int(v) for v in size) < 1:
+        raise SpffError(f"resize3d_fwd: size must be three positive sizes; got {size}")
+    Do, Ho, Wo = (int(v) for v in size)
+    y = torch.empty((B, Do, Ho, Wo, C), dtype=torch.float32, device=x_cl.device)
+    check(lib().spff_resize3d_fwd(_ptr(x_cl), _ptr(y), B, C, D, H, W, Do, Ho, Wo,
+                                  _stream(x_cl.device)), "spff_resize3d_fwd")
+    return y
+
+
+def resize3d_bwd(dy_cl: torch.Tensor, in_size) -> torch.Tensor:
+    """The adjoint of resize3d_fwd: dy [B, Do, Ho, Wo, C] -> dx [B, *in_size, C]."""
+    require_device(dy_cl, "resize3d_bwd")
+    if dy_cl.ndim != 5 or dy_cl.dtype != torch.float32:
+        raise SpffError(f"resize3d_bwd: expected fp32 [B, D, H, W, C]; got {dy_cl.dtype} "
+                        f"{tuple(dy_cl.shape)}")
+    dy_cl = dy_cl.contiguous()
+    B, Do, Ho, Wo, C = dy_cl.shape
+    if len(tuple(in_size)) != 3 or min(int(v) for v in in_size) < 1:
+        raise SpffError(f"resize3d_bwd: in_size must be three positive sizes; got {in_size}")
+    D, H, W = (int(v) for v in in_size)
+    dx = torch.empty((B, D, H, W, C), dtype=torch.float32, device=dy_cl.device)
+    check(lib().spff_resize3d_bwd(_ptr(dy_cl), _ptr(dx), B, C, D, H, W, Do, Ho, Wo,
+                                  _stream(dy_cl.device)), "spff_resize3d_bwd")
+    return dx
+
+
 class R2UPlan:
     """Engine plan of the R2UNet3D variant (include/spff.h spff_r2u_*): the recurrent
     residual U-Net backbone + 1x1x1 head of LitR2UNet3D_Published.  Parameters are one
@@ -1349,7 +1554,8 @@ def to_channels_last(t: torch.Tensor) -> torch.Tensor:
     return t.permute(0, 2, 3, 4, 1).contiguous()
 
 
-CONV_PROF_CLASSES = ("conv_fwd", "conv_dgrad", "conv_wgrad", "loss_pass", "k_loss")
+CONV_PROF_CLASSES = ("conv_fwd", "conv_dgrad", "conv_wgrad", "loss_pass", "k_loss",
+                     "unetr_vit", "unetr_resample")
 
 
 def conv_prof_enable(on: bool = True) -> None:

@@ -9,11 +9,13 @@ engine implements.  Differences, all deliberate:
   and CHECKPOINT_DIR/LOG_DIR at import (config.py:19, 258-259); here
   directories are created by whoever writes to them (train.py);
 * ``INNOVATIVE3D_VARIANT`` actually selects (SURVEY F11): ``selected_variants()``;
-* of the non-SPCT baselines "3DUNet" (BASELINE config 3, SURVEY §8(f) rank 2:
-  Cicek3DUNet + depth adapter), "ResUNet++" (residual units, ASPP, SE and
-  attention gates; Dice + CE), "SwinUNETR" (BASELINE config 5, §8(f) rank 3) and
-  "R2UNet3D" (the recurrent residual U-Net with its Dice-only loss) are
-  registered, all on the engine; only UNETR is not built (SURVEY §8);
+* the non-SPCT baselines "UNETR" (ViT encoder with global attention, resampled to
+  its 96^3 grid), "3DUNet" (BASELINE config 3, SURVEY §8(f) rank 2: Cicek3DUNet +
+  depth adapter), "ResUNet++" (residual units, ASPP, SE and attention gates;
+  Dice + CE), "SwinUNETR" (BASELINE config 5, §8(f) rank 3) and "R2UNet3D" (the
+  recurrent residual U-Net with its Dice-only loss) are registered, all on the
+  engine, so all ten variants of the reference's registry run here; the MONAI
+  bodies of UNETR and SwinUNETR are restated, their parity unpinned offline;
 * the DICOM data module (``MultiDicomDataModule3D``) is the device-resident
   one of innovative3D/datasets.py (resize, ROI rasterisation and TrainGridAug as
   HIP kernels); DICOM files are decoded by pydicom when installed, else by the native
@@ -131,6 +133,17 @@ def make_cicek_depth_adapter_sgd_wce():
         use_bn=True, target_depth=16, include_bg_in_dice=False,
     )
 
+
+# UNETR (config.py:316-339).  build_class drops the kwargs LitUNETR_Published does not
+# take (use_cosine_lr), exactly like the reference.
+_add_variant("UNETR",
+             build_class("LitUNETR_Published", num_classes=NUM_CLASSES, img_size=(96, 96, 96),
+                         in_channels=1, feature_size=16, hidden_size=768, mlp_dim=3072,
+                         num_heads=12, pos_embed="perceptron", norm_name="instance",
+                         res_block=True, dropout_rate=0.0, lr=1e-4, weight_decay=1e-2,
+                         use_cosine_lr=True, warmup_epochs=5, use_ce_alongside_dice=True,
+                         ce_weight=0.5, include_bg_in_dice=False, ignore_index=IGNORE_INDEX),
+             MultiDicomDataModule3D, CHECKPOINT_DIR / "UNETR")
 
 _add_variant("3DUNet", make_cicek_depth_adapter_sgd_wce, MultiDicomDataModule3D,
              CHECKPOINT_DIR / "3DUNet")

@@ -823,6 +823,7 @@ class _SwinFunction(torch.autograd.Function):
     def forward(ctx, x, plan, flat, grad_hook, *params):
         logits_cl = plan.forward(x, flat)
         ctx.plan, ctx.gen, ctx.flat, ctx.grad_hook = plan, plan.generation, flat, grad_hook
+        ctx.plan_name = "UNETR" if isinstance(plan, E.UNETRPlan) else "SwinUNETR"
         # a backward is pending on this workspace (E._alloc_workspace releases other
         # plans' workspaces on OOM, pending ones only as a last resort)
         plan._pending_gen = plan.generation if any(ctx.needs_input_grad) else None
@@ -834,7 +835,7 @@ class _SwinFunction(torch.autograd.Function):
     def backward(ctx, g):
         plan = ctx.plan
         if plan.generation != ctx.gen:
-            raise E.SpffError("SwinUNETR engine: another forward ran on this model before the "
+            raise E.SpffError(f"{ctx.plan_name} engine: another forward ran on this model before the "
                               "backward of this one; the engine keeps one forward's activations")
         g_cl = g.permute(0, 2, 3, 4, 1).contiguous()
         dflat = plan.backward(g_cl, ctx.flat, grad_hook=ctx.grad_hook)
@@ -900,7 +901,39 @@ class _BasicLayerP(nn.Module):
         self.downsample.norm = nn.LayerNorm(8 * dim)
 
 
-class SwinUNETR(nn.Module):
+class _FlatParamModule(nn.Module):
+    """A MONAI-named parameter tree whose Parameters are views into the plan's one flat fp32
+    buffer (SwinUNETR, UNETR)."""
+
+    def _engine_params(self, plan):
+        named = dict(self.named_parameters())
+        out = []
+        for name, shape, _off, _n in plan.params:
+            p = named.get(name)
+            if p is None or tuple(p.shape) != tuple(shape):
+                raise E.SpffError(f"parameter {name} {shape} missing or mis-shaped in the module")
+            out.append(p)
+        return out
+
+    def _ensure_flat(self, plan, params, device):
+        flat = self._flat
+        ok = flat is not None and flat.device == device and flat.numel() == plan.nfloats
+        if ok:
+            base = flat.data_ptr()
+            ok = all(p.data_ptr() == base + 4 * off and p.dtype == torch.float32
+                     for p, (_n, _s, off, _k) in zip(params, plan.params))
+        if not ok:
+            flat = torch.empty(plan.nfloats, dtype=torch.float32, device=device)
+            with torch.no_grad():
+                for p, (_name, shape, off, n) in zip(params, plan.params):
+                    flat[off:off + n].copy_(p.detach().reshape(-1).to(device=device,
+                                                                     dtype=torch.float32))
+                    p.data = flat[off:off + n].view(shape)
+            self._flat = flat
+        return flat
+
+
+class SwinUNETR(_FlatParamModule):
     """MONAI 1.5.2 SwinUNETR (patch_size 2, depths (1,1,1,1) -- the registry's --,
     normalize=True, res_block, InstanceNorm, downsample "merging", use_v2 False)
     with MONAI's parameter names; forward on the HIP engine (D, H, W multiples
@@ -960,33 +993,6 @@ class SwinUNETR(nn.Module):
                                device=x.device, math=getattr(self, "math", None),
                                owner=self)
 
-    def _engine_params(self, plan):
-        named = dict(self.named_parameters())
-        out = []
-        for name, shape, _off, _n in plan.params:
-            p = named.get(name)
-            if p is None or tuple(p.shape) != tuple(shape):
-                raise E.SpffError(f"parameter {name} {shape} missing or mis-shaped in the module")
-            out.append(p)
-        return out
-
-    def _ensure_flat(self, plan, params, device):
-        flat = self._flat
-        ok = flat is not None and flat.device == device and flat.numel() == plan.nfloats
-        if ok:
-            base = flat.data_ptr()
-            ok = all(p.data_ptr() == base + 4 * off and p.dtype == torch.float32
-                     for p, (_n, _s, off, _k) in zip(params, plan.params))
-        if not ok:
-            flat = torch.empty(plan.nfloats, dtype=torch.float32, device=device)
-            with torch.no_grad():
-                for p, (_name, shape, off, n) in zip(params, plan.params):
-                    flat[off:off + n].copy_(p.detach().reshape(-1).to(device=device,
-                                                                     dtype=torch.float32))
-                    p.data = flat[off:off + n].view(shape)
-            self._flat = flat
-        return flat
-
     def forward(self, x_in):
         E.require_device(x_in, "SwinUNETR.forward")
         plan = self._plan(x_in)
@@ -1032,44 +1038,12 @@ class _SwinLoss(torch.autograd.Function):
         return dl.permute(0, 4, 1, 2, 3), None, None, None, None, None
 
 
-class LitSwinUNETR_Published(pl.LightningModule):
-    """models.py:880-982 (registry "SwinUNETR"): pad to a multiple of 32 (replicate,
-    centred) -> SwinUNETR -> crop; loss (1 - w) soft-Dice + w CE(ignore) on the
-    fused HIP loss kernels; AdamW with linear warm-up + cosine decay."""
-
-    def __init__(self, num_classes: int, img_size=(96, 96, 96), in_channels: int = 1,
-                 feature_size: int = 48, depths=(2, 2, 2, 2), num_heads=(3, 6, 12, 24),
-                 mlp_ratio: float = 4.0, drop_rate: float = 0.0, attn_drop_rate: float = 0.0,
-                 dropout_path_rate: float = 0.0, use_checkpoint: bool = False,
-                 norm_name: str = "instance", lr: float = 1e-4, weight_decay: float = 1e-2,
-                 warmup_epochs: int = 5, use_ce_alongside_dice: bool = True,
-                 ce_weight: float = 0.5, ignore_index: Optional[int] = IGNORE_INDEX,
-                 include_bg_in_dice: bool = True):
-        super().__init__()
-        self.save_hyperparameters({
-            "num_classes": num_classes, "img_size": img_size, "in_channels": in_channels,
-            "feature_size": feature_size, "depths": depths, "num_heads": num_heads,
-            "mlp_ratio": mlp_ratio, "drop_rate": drop_rate, "attn_drop_rate": attn_drop_rate,
-            "dropout_path_rate": dropout_path_rate, "use_checkpoint": use_checkpoint,
-            "norm_name": norm_name, "lr": lr, "weight_decay": weight_decay,
-            "warmup_epochs": warmup_epochs, "use_ce_alongside_dice": use_ce_alongside_dice,
-            "ce_weight": ce_weight, "ignore_index": ignore_index,
-            "include_bg_in_dice": include_bg_in_dice})
-        self.model = SwinUNETR_Published(
-            num_classes, img_size=img_size, in_channels=in_channels, feature_size=feature_size,
-            depths=depths, num_heads=num_heads, mlp_ratio=mlp_ratio, drop_rate=drop_rate,
-            attn_drop_rate=attn_drop_rate, dropout_path_rate=dropout_path_rate,
-            use_checkpoint=use_checkpoint, norm_name=norm_name)
-        self._total_train_iters = None
-        self._iters_done = 0
-
-    def forward(self, x):
-        x = _pick_first_if_seq(x)
-        if x.ndim == 4:
-            x = x.unsqueeze(1)
-        x_pad, orig = _pad_to_mult16_3d(x, multiple=32)
-        y_pad = self.model(x_pad)
-        return _center_crop_3d(y_pad, orig)
+class _DiceCEWarmupLit(pl.LightningModule):
+    """What LitSwinUNETR_Published and LitUNETR_Published share in the reference
+    (models.py:906-982 and 1038-1115 are the same code): the (1 - w) soft-Dice + w CE
+    loss on the fused HIP loss kernels, the linear warm-up + cosine learning rate, the
+    step methods and AdamW.  Subclasses set hparams, _total_train_iters / _iters_done
+    and forward."""
 
     def _loss(self, logits, labels):
         if labels.ndim == 5 and labels.shape[1] == 1:
@@ -1125,6 +1099,228 @@ class LitSwinUNETR_Published(pl.LightningModule):
     def configure_optimizers(self):
         return torch.optim.AdamW(self.parameters(), lr=self.hparams.lr,
                                  weight_decay=self.hparams.weight_decay, betas=(0.9, 0.999))
+
+
+class LitSwinUNETR_Published(_DiceCEWarmupLit):
+    """models.py:880-982 (registry "SwinUNETR"): pad to a multiple of 32 (replicate,
+    centred) -> SwinUNETR -> crop; loss (1 - w) soft-Dice + w CE(ignore) on the
+    fused HIP loss kernels; AdamW with linear warm-up + cosine decay."""
+
+    def __init__(self, num_classes: int, img_size=(96, 96, 96), in_channels: int = 1,
+                 feature_size: int = 48, depths=(2, 2, 2, 2), num_heads=(3, 6, 12, 24),
+                 mlp_ratio: float = 4.0, drop_rate: float = 0.0, attn_drop_rate: float = 0.0,
+                 dropout_path_rate: float = 0.0, use_checkpoint: bool = False,
+                 norm_name: str = "instance", lr: float = 1e-4, weight_decay: float = 1e-2,
+                 warmup_epochs: int = 5, use_ce_alongside_dice: bool = True,
+                 ce_weight: float = 0.5, ignore_index: Optional[int] = IGNORE_INDEX,
+                 include_bg_in_dice: bool = True):
+        super().__init__()
+        self.save_hyperparameters({
+            "num_classes": num_classes, "img_size": img_size, "in_channels": in_channels,
+            "feature_size": feature_size, "depths": depths, "num_heads": num_heads,
+            "mlp_ratio": mlp_ratio, "drop_rate": drop_rate, "attn_drop_rate": attn_drop_rate,
+            "dropout_path_rate": dropout_path_rate, "use_checkpoint": use_checkpoint,
+            "norm_name": norm_name, "lr": lr, "weight_decay": weight_decay,
+            "warmup_epochs": warmup_epochs, "use_ce_alongside_dice": use_ce_alongside_dice,
+            "ce_weight": ce_weight, "ignore_index": ignore_index,
+            "include_bg_in_dice": include_bg_in_dice})
+        self.model = SwinUNETR_Published(
+            num_classes, img_size=img_size, in_channels=in_channels, feature_size=feature_size,
+            depths=depths, num_heads=num_heads, mlp_ratio=mlp_ratio, drop_rate=drop_rate,
+            attn_drop_rate=attn_drop_rate, dropout_path_rate=dropout_path_rate,
+            use_checkpoint=use_checkpoint, norm_name=norm_name)
+        self._total_train_iters = None
+        self._iters_done = 0
+
+    def forward(self, x):
+        x = _pick_first_if_seq(x)
+        if x.ndim == 4:
+            x = x.unsqueeze(1)
+        x_pad, orig = _pad_to_mult16_3d(x, multiple=32)
+        y_pad = self.model(x_pad)
+        return _center_crop_3d(y_pad, orig)
+
+
+# ============================================================================
+# UNETR (registry "UNETR", config.py:316-339): LitUNETR_Published (models.py:
+# 1006-1115) around UNETR_Published (987-1004), i.e. MONAI 1.5.2's UNETR, on the
+# engine's spff_unetr plan (csrc/unetr.hip).  PARITY UNPINNED: MONAI is not
+# available offline; its semantics are restated in tests/_unetr_oracle.py.
+# ============================================================================
+_UNETRFunction = _SwinFunction  # the same hand-over: plan.forward / backward / params
+
+
+class _ViTBlockP(nn.Module):
+    """MONAI TransformerBlock's parameters in its registration order.  norm_cross_attn and
+    cross_attn are registered by MONAI >= 1.4 in every block and never used without
+    with_cross_attention: held here so that a MONAI checkpoint loads strictly, outside the
+    engine's flat buffer, their gradients stay None."""
+
+    def __init__(self, hidden: int, mlp_dim: int):
+        super().__init__()
+        self.mlp = _Holder()
+        self.mlp.linear1 = nn.Linear(hidden, mlp_dim)
+        self.mlp.linear2 = nn.Linear(mlp_dim, hidden)
+        self.norm1 = nn.LayerNorm(hidden)
+        self.attn = _Holder()
+        self.attn.out_proj = nn.Linear(hidden, hidden)
+        self.attn.qkv = nn.Linear(hidden, 3 * hidden, bias=False)
+        self.norm2 = nn.LayerNorm(hidden)
+        self.norm_cross_attn = nn.LayerNorm(hidden)
+        self.cross_attn = _Holder()
+        self.cross_attn.out_proj = nn.Linear(hidden, hidden)
+        self.cross_attn.to_q = nn.Linear(hidden, hidden, bias=False)
+        self.cross_attn.to_k = nn.Linear(hidden, hidden, bias=False)
+        self.cross_attn.to_v = nn.Linear(hidden, hidden, bias=False)
+
+
+def _transp_holder(ci: int, co: int) -> nn.Module:
+    return _conv_holder(nn.ConvTranspose3d(ci, co, 2, stride=2, bias=False))
+
+
+def _prup_block(hidden: int, co: int, num_layer: int) -> nn.Module:
+    """MONAI UnetrPrUpBlock (conv_block and res_block on)."""
+    b = _Holder()
+    b.transp_conv_init = _transp_holder(hidden, co)
+    b.blocks = nn.ModuleList([nn.ModuleList([_transp_holder(co, co), _res_block(co, co)])
+                              for _ in range(num_layer)])
+    return b
+
+
+class UNETR(_FlatParamModule):
+    """MONAI 1.5.2 UNETR (conv patch embedding of 16^3, learnable position embedding, twelve
+    ViT blocks, InstanceNorm, conv_block and res_block, no dropout, no qkv bias) with MONAI's
+    parameter names and constructor signature; forward on the HIP engine."""
+
+    def __init__(self, in_channels: int, out_channels: int, img_size=(96, 96, 96),
+                 feature_size: int = 16, hidden_size: int = 768, mlp_dim: int = 3072,
+                 num_heads: int = 12, proj_type: str = "conv", norm_name="instance",
+                 conv_block: bool = True, res_block: bool = True, dropout_rate: float = 0.0,
+                 spatial_dims: int = 3, qkv_bias: bool = False, save_attn: bool = False):
+        super().__init__()
+        if isinstance(img_size, int):
+            img_size = (img_size,) * 3
+        if (proj_type != "conv" or not conv_block or not res_block or qkv_bias or spatial_dims != 3
+                or str(norm_name).lower() != "instance"):
+            raise NotImplementedError("the registry's UNETR settings only (conv patch projection, "
+                                      "conv_block, res_block, instance norm, 3D, no qkv bias)")
+        if dropout_rate:
+            raise NotImplementedError("dropout is 0 on the registry path")
+        if hidden_size % num_heads:
+            raise ValueError("hidden_size should be divisible by num_heads.")
+        if any(int(v) % 16 for v in img_size):
+            raise ValueError("img_size should be divisible by the 16^3 patch")
+        f, hid = int(feature_size), int(hidden_size)
+        self.in_channels, self.num_classes, self.feature_size = int(in_channels), int(out_channels), f
+        self.img_size = tuple(int(v) for v in img_size)
+        self.hidden_size, self.mlp_dim, self.num_heads = hid, int(mlp_dim), int(num_heads)
+        n = (self.img_size[0] // 16) * (self.img_size[1] // 16) * (self.img_size[2] // 16)
+        self.vit = _Holder()
+        self.vit.patch_embedding = _Holder()
+        self.vit.patch_embedding.position_embeddings = nn.Parameter(torch.zeros(1, n, hid))
+        nn.init.trunc_normal_(self.vit.patch_embedding.position_embeddings, std=0.02)
+        self.vit.patch_embedding.patch_embeddings = nn.Conv3d(in_channels, hid, 16, stride=16)
+        self.vit.blocks = nn.ModuleList([_ViTBlockP(hid, self.mlp_dim) for _ in range(12)])
+        self.vit.norm = nn.LayerNorm(hid)
+        self.encoder1 = _Holder(); self.encoder1.layer = _res_block(in_channels, f)  # noqa: E702
+        self.encoder2 = _prup_block(hid, 2 * f, 2)
+        self.encoder3 = _prup_block(hid, 4 * f, 1)
+        self.encoder4 = _prup_block(hid, 8 * f, 0)
+        for name, ci, co in (("decoder5", hid, 8 * f), ("decoder4", 8 * f, 4 * f),
+                             ("decoder3", 4 * f, 2 * f), ("decoder2", 2 * f, f)):
+            d = _Holder()
+            d.transp_conv = _transp_holder(ci, co)
+            d.conv_block = _res_block(2 * co, co)
+            setattr(self, name, d)
+        self.out = _Holder()
+        self.out.conv = _conv_holder(nn.Conv3d(f, out_channels, 1, bias=True))
+        self._flat = None
+
+    def _plan(self, x):
+        B, C, D, H, W = x.shape
+        if C != self.in_channels:
+            raise ValueError(f"expected {self.in_channels} input channels, got {C}")
+        if D % 16 or H % 16 or W % 16:
+            raise ValueError(f"spatial dims {(D, H, W)} must be divisible by 16")
+        return E.get_unetr_plan(batch=B, in_ch=C, depth=D, height=H, width=W,
+                                num_classes=self.num_classes, img=self.img_size,
+                                feature_size=self.feature_size, hidden=self.hidden_size,
+                                mlp_dim=self.mlp_dim, heads=self.num_heads, device=x.device,
+                                math=getattr(self, "math", None), owner=self)
+
+    def run(self, x_in):
+        """x_in [B, Cin, D, H, W], multiples of 16.  Another size than img_size is resampled
+        to img_size and the logits back (trilinear, align_corners=False) inside the engine:
+        steps 3-5 of LitUNETR_Published.forward."""
+        E.require_device(x_in, "UNETR.forward")
+        plan = self._plan(x_in)
+        params = self._engine_params(plan)
+        flat = self._ensure_flat(plan, params, x_in.device)
+        if torch.is_grad_enabled() and any(p.requires_grad for p in params):
+            return _UNETRFunction.apply(x_in.float(), plan, flat, getattr(self, "grad_hook", None),
+                                        *params)
+        return plan.forward(x_in.float(), flat).permute(0, 4, 1, 2, 3)
+
+    def forward(self, x_in):
+        if tuple(x_in.shape[2:]) != self.img_size:
+            raise ValueError(f"UNETR takes inputs of img_size {self.img_size} (the position "
+                             f"embedding is tied to it); got {tuple(x_in.shape[2:])}")
+        return self.run(x_in)
+
+
+class UNETR_Published(nn.Module):
+    """models.py:987-1004: builds UNETR with the kwargs MONAI 1.5.2 accepts (pos_embed is
+    not one of them, so the patch projection is MONAI's default "conv")."""
+
+    def __init__(self, num_classes, img_size=(96, 96, 96), in_channels=1, feature_size=16,
+                 hidden_size=768, mlp_dim=3072, num_heads=12, pos_embed="perceptron",
+                 norm_name="instance", res_block=True, dropout_rate=0.0):
+        super().__init__()
+        self.net = UNETR(img_size=img_size, in_channels=in_channels, out_channels=num_classes,
+                         feature_size=feature_size, hidden_size=hidden_size, mlp_dim=mlp_dim,
+                         num_heads=num_heads, norm_name=norm_name, res_block=res_block,
+                         dropout_rate=dropout_rate, spatial_dims=3)
+
+    def forward(self, x):
+        return self.net(x)
+
+
+class LitUNETR_Published(_DiceCEWarmupLit):
+    """models.py:1006-1115 (registry "UNETR"): pad to a multiple of 16 (replicate, centred)
+    -> resample to img_size when the padded size differs -> UNETR -> resample the logits
+    back -> crop; the loss, learning-rate schedule and AdamW of LitSwinUNETR_Published."""
+
+    def __init__(self, num_classes: int, img_size=(96, 96, 96), in_channels: int = 1,
+                 feature_size: int = 16, hidden_size: int = 768, mlp_dim: int = 3072,
+                 num_heads: int = 12, pos_embed: str = "perceptron", norm_name: str = "instance",
+                 res_block: bool = True, dropout_rate: float = 0.0, lr: float = 1e-4,
+                 weight_decay: float = 1e-2, warmup_epochs: int = 5,
+                 use_ce_alongside_dice: bool = True, ce_weight: float = 0.5,
+                 ignore_index: Optional[int] = None, include_bg_in_dice: bool = True):
+        super().__init__()
+        self.save_hyperparameters({
+            "num_classes": num_classes, "img_size": img_size, "in_channels": in_channels,
+            "feature_size": feature_size, "hidden_size": hidden_size, "mlp_dim": mlp_dim,
+            "num_heads": num_heads, "pos_embed": pos_embed, "norm_name": norm_name,
+            "res_block": res_block, "dropout_rate": dropout_rate, "lr": lr,
+            "weight_decay": weight_decay, "warmup_epochs": warmup_epochs,
+            "use_ce_alongside_dice": use_ce_alongside_dice, "ce_weight": ce_weight,
+            "ignore_index": ignore_index, "include_bg_in_dice": include_bg_in_dice})
+        self.net = UNETR_Published(num_classes=num_classes, img_size=img_size,
+                                   in_channels=in_channels, feature_size=feature_size,
+                                   hidden_size=hidden_size, mlp_dim=mlp_dim, num_heads=num_heads,
+                                   pos_embed=pos_embed, norm_name=norm_name, res_block=res_block,
+                                   dropout_rate=dropout_rate)
+        self._total_train_iters = None
+        self._iters_done = 0
+
+    def forward(self, x):
+        x = _pick_first_if_seq(x)
+        if x.ndim == 4:
+            x = x.unsqueeze(1)
+        x_pad, orig = _pad_to_mult16_3d(x)
+        y_pad = self.net.net.run(x_pad)
+        return _center_crop_3d(y_pad, orig)
 
 
 # ============================================================================
@@ -1257,8 +1453,8 @@ class LitR2UNet3D_Published(pl.LightningModule):
                               num_classes=int(self.hparams.num_classes), base=bb.base, t=bb.t,
                               device=x.device, math=getattr(self, "math", None), owner=self)
 
-    _engine_params = SwinUNETR._engine_params
-    _ensure_flat = SwinUNETR._ensure_flat
+    _engine_params = _FlatParamModule._engine_params
+    _ensure_flat = _FlatParamModule._ensure_flat
 
     def forward(self, x):
         x = _pick_first_if_seq(x)
@@ -1488,8 +1684,8 @@ class LitResUNetPP3D_Published(pl.LightningModule):
                                num_classes=int(self.hparams.num_classes), base=bb.base,
                                device=x.device, math=getattr(self, "math", None), owner=self)
 
-    _engine_params = SwinUNETR._engine_params
-    _ensure_flat = SwinUNETR._ensure_flat
+    _engine_params = _FlatParamModule._engine_params
+    _ensure_flat = _FlatParamModule._ensure_flat
 
     def forward(self, x):
         x = _pick_first_if_seq(x)
