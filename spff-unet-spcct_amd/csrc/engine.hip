@@ -11,7 +11,7 @@
 // with the gate algebra (EFiLM, FourierGate, SpectralSE, SE) folded into the
 // per-(b,c,d) coefficients P, Q (gates.hip).  Saved for backward: y1, a1, y2,
 // out and the (b,c)/(b,c,d) statistics -- everything else is recomputed.
-#include "spff_internal.h"
+#include "plan_base.h"
 
 #ifndef SPFF_OUTFUSE
 // block outputs applied by the GEMMs that read them (ActRows) instead of a stored act_apply
@@ -50,12 +50,7 @@ static int fail(int code, const std::string& m) {
 namespace spff {
 int set_error(int code, const char* msg) { return fail(code, msg); }
 }
-#define HIPCK(expr)                                                                        \
-  do {                                                                                     \
-    hipError_t _e = (expr);                                                                \
-    if (_e != hipSuccess)                                                                  \
-      return fail(SPFF_EHIP, std::string(#expr) + " -> " + hipGetErrorString(_e));         \
-  } while (0)
+#define HIPCK PLAN_HIPCK  // (plan_fail -> set_error -> fail above)
 // PROF: time one launch with HIP events on the plan's stream when enabled.
 // PROFB also records the launch's compulsory HBM bytes (operands read once, result
 // written once) for the roofline's traffic comparison.
@@ -68,21 +63,9 @@ int set_error(int code, const char* msg) { return fail(code, msg); }
     HIPCK(expr);                                                                         \
     if (_r) HIPCK(hipEventRecord(_r->b, _p->st));                                        \
   } while (0)
-#define CK(expr)               \
-  do {                         \
-    int _r = (expr);           \
-    if (_r != SPFF_OK) return _r; \
-  } while (0)
+#define CK PLAN_CK
 
 namespace {
-
-static inline int rup(int a, int b) { return (a + b - 1) / b * b; }
-
-struct PEnt {
-  std::string name;
-  std::vector<int64_t> shape;
-  int64_t off, numel;
-};
 
 struct ConvL {
   int Cin, Cout;
@@ -124,15 +107,13 @@ struct UpL {
 
 }  // namespace
 
-struct spff_plan {
+struct spff_plan : PlanBase {
   spff_cfg cfg;
   Vol vol[4];
   int f, KD, ldx, K;
   int efh = 32, efp = 16, fphase = 0;  // EnergyFiLM3D(hidden, pe_dims), learn_phase
   bool lean = false;  // SPFF_MEM_LEAN layout: a1 / out / up-conv outputs live in the
                       // gradient scratch and are recomputed in the backward
-  std::vector<PEnt> params;
-  int64_t nparam = 0;
   Blk blk[7];
   UpL up[3];  // up3, up2, up1
   int64_t out_w = -1, out_b = -1;
@@ -152,7 +133,6 @@ struct spff_plan {
   bool hsh = false;
   int hmul = 1;  // global / local rows
   size_t hst = 0, gdum = 0;
-  size_t total = 0;
   Coll co;             // sharding group (world 1: unsharded)
   bool coll_set = false;
   spff_grad_ready_fn grad_fn = nullptr;  // data-parallel gradient-ready hook
@@ -169,11 +149,6 @@ struct spff_plan {
   bool keep_out = false;  // debug: store the fused block outputs too (saved views)
   bool pool_fold = SPFF_POOL_FOLD;  // PoolAdd in the encoder backward (debug key 2: off)
   bool bst_fuse = true;  // conv1's IN-backward sums in the dgrad epilogue (debug key 3: off)
-  // per call
-  char* ws = nullptr;
-  const float* prm = nullptr;
-  float* dprm = nullptr;
-  hipStream_t st = nullptr;
   // depth-sharded plans: side stream + events of the halo exchange that overlaps the
   // interior depth tiles of the next convolution (conv_halo)
   hipStream_t st2 = nullptr;
@@ -181,14 +156,6 @@ struct spff_plan {
   // the conv input whose halo exchange halo_begin already put on st2 (ev_halo marks it)
   const float* halo_early = nullptr;
 
-  float* F(size_t off) const { return reinterpret_cast<float*>(ws + off); }
-  const float* P(int64_t off) const { return off < 0 ? nullptr : prm + off; }
-  float* DP(int64_t off) const { return off < 0 ? nullptr : dprm + off; }
-  size_t alloc(size_t bytes) {
-    size_t o = total;
-    total += (bytes + 255) / 256 * 256;
-    return o;
-  }
   // a conv input of a halo'd (depth-sharded) plan: one neighbour slice of up to
   // slice_bytes before and after the interior; returns the interior offset
   size_t alloc_halo(size_t bytes, size_t slice_bytes) {
@@ -196,14 +163,6 @@ struct spff_plan {
     return alloc(bytes + 2 * slice_bytes) + slice_bytes;
   }
   double* D64(size_t off) const { return reinterpret_cast<double*>(ws + off); }
-  int64_t reg(const std::string& name, std::vector<int64_t> shape) {
-    int64_t n = 1;
-    for (auto s : shape) n *= s;
-    params.push_back(PEnt{name, shape, nparam, n});
-    int64_t o = nparam;
-    nparam += n;
-    return o;
-  }
 };
 
 // compulsory HBM bytes of one conv launch: both activations once + the fp32 weights
@@ -1378,15 +1337,8 @@ int spff_num_params(const spff_plan* p) { return p ? (int)p->params.size() : 0; 
 
 int spff_param_info(const spff_plan* p, int i, const char** name, int* ndim, int64_t shape[5],
                     int64_t* offset, int64_t* numel) {
-  if (!p || i < 0 || i >= (int)p->params.size()) return fail(SPFF_EINVAL, "param index");
-  const PEnt& e = p->params[i];
-  if (name) *name = e.name.c_str();
-  if (ndim) *ndim = (int)e.shape.size();
-  if (shape)
-    for (int k = 0; k < 5; ++k) shape[k] = k < (int)e.shape.size() ? e.shape[k] : 1;
-  if (offset) *offset = e.off;
-  if (numel) *numel = e.numel;
-  return SPFF_OK;
+  if (!p) return fail(SPFF_EINVAL, "param index");
+  return plan_param_info(p->params, i, name, ndim, shape, offset, numel);
 }
 
 int64_t spff_param_floats(const spff_plan* p) { return p ? p->nparam : 0; }
@@ -1405,10 +1357,7 @@ static int coll_status(spff_plan* p, int rc, const char* what) {
 int spff_forward(spff_plan* p, const float* x, const float* params, float* logits, void* ws,
                  void* stream) {
   if (!p || !x || !params || !logits || !ws) return fail(SPFF_EINVAL, "null argument");
-  p->ws = static_cast<char*>(ws);
-  p->prm = params;
-  p->dprm = nullptr;
-  p->st = static_cast<hipStream_t>(stream);
+  p->bind(ws, params, nullptr, stream);
   if (p->co.on() && !p->coll_set)
     return fail(SPFF_EINVAL, "depth-sharded plan: call spff_plan_set_coll first");
   CK(ensure_pe(p));
@@ -1422,10 +1371,7 @@ int spff_forward(spff_plan* p, const float* x, const float* params, float* logit
 int spff_backward(spff_plan* p, const float* dlogits, const float* params, float* dparams,
                   void* ws, void* stream) {
   if (!p || !dlogits || !params || !dparams || !ws) return fail(SPFF_EINVAL, "null argument");
-  p->ws = static_cast<char*>(ws);
-  p->prm = params;
-  p->dprm = dparams;
-  p->st = static_cast<hipStream_t>(stream);
+  p->bind(ws, params, dparams, stream);
   if (p->co.on() && !p->coll_set)
     return fail(SPFF_EINVAL, "depth-sharded plan: call spff_plan_set_coll first");
   p->co.failed = nullptr;
@@ -1438,14 +1384,8 @@ int spff_backward(spff_plan* p, const float* dlogits, const float* params, float
 int spff_saved_tensor(const spff_plan* p, void* ws, const char* name, const float** ptr,
                       int64_t* nv, int* ch) {
   if (!p || !ws || !name || !ptr) return fail(SPFF_EINVAL, "null argument");
-  const char* base = static_cast<const char*>(ws);
   const std::string n(name);
-  auto ret = [&](size_t off, const Vol& v, int c) {
-    *ptr = reinterpret_cast<const float*>(base + off);
-    if (nv) *nv = nvox(v);
-    if (ch) *ch = c;
-    return SPFF_OK;
-  };
+  const SavedOut ret{ws, ptr, nv, ch};
   if (n == "x_cl") return ret(p->x_cl, p->vol[0], p->ldx);
   if (n.rfind("grad.", 0) == 0) {  // backward scratch, sized as level-0 [V0][f]
     const size_t off = n == "grad.out" ? p->G_out : n == "grad.dy2" ? p->G_dy2 :

@@ -34,9 +34,8 @@
 // rows past in_ch are zero; no dedicated kernel.
 // Saved for backward per block: x1, y_k (raw conv outputs), a_k, s, o, the statistics and
 // the pool argmax bytes.
-#include "spff_internal.h"
+#include "plan_base.h"
 #include "swin_internal.h"
-#include "spff.h"
 
 #include <algorithm>
 #include <string>
@@ -46,26 +45,7 @@ using namespace spff;
 
 namespace {
 
-int rfail(int code, const std::string& m) { return set_error(code, m.c_str()); }
-#define RHIPCK(expr)                                                                       \
-  do {                                                                                     \
-    hipError_t _e = (expr);                                                                \
-    if (_e != hipSuccess)                                                                  \
-      return rfail(SPFF_EHIP, std::string(#expr) + " -> " + hipGetErrorString(_e));        \
-  } while (0)
-#define RCK(expr)                   \
-  do {                              \
-    int _r = (expr);                \
-    if (_r != SPFF_OK) return _r;   \
-  } while (0)
-
 constexpr int NLVL = 5, NBLK = 9, NUP = 4, NSUB = 8, TMAX = 8;
-
-struct REnt {
-  std::string name;
-  std::vector<int64_t> shape;
-  int64_t off, numel;
-};
 
 struct RStat {
   size_t mean, rstd, al, de;
@@ -131,12 +111,10 @@ hipError_t r2u_acc(float* dst, const float* src, int64_t n, float scale, hipStre
 
 }  // namespace
 
-struct spff_r2u {
+struct spff_r2u : PlanBase {
   spff_r2u_cfg cfg;
   Vol vol[NLVL];
   int f, K, ldx, t;
-  std::vector<REnt> params;
-  int64_t nparam = 0;
   RBlk blk[NBLK];  // e1..e4, b, d4..d1
   RUp up[NUP];     // up4, up3, up2, up1
   int64_t head_w = -1, head_b = -1;
@@ -146,28 +124,6 @@ struct spff_r2u {
   bool pkb = false;
   size_t wsl = 0;  // SPFF_MATH_F16X3 max |w| per block's conv (batched plans)
   size_t G_out = 0, G_s = 0, G_1 = 0, G_2 = 0, G_dx = 0, dskip[4] = {};
-  size_t total = 0;
-  // per call
-  char* ws = nullptr;
-  const float* prm = nullptr;
-  float* dprm = nullptr;
-  hipStream_t st = nullptr;
-
-  float* F(size_t off) const { return reinterpret_cast<float*>(ws + off); }
-  const float* P(int64_t off) const { return prm + off; }
-  float* DP(int64_t off) const { return dprm + off; }
-  size_t alloc(size_t bytes) {
-    size_t o = total;
-    total += (bytes + 255) / 256 * 256;
-    return o;
-  }
-  int64_t reg(const std::string& name, std::vector<int64_t> shape) {
-    int64_t n = 1;
-    for (auto s : shape) n *= s;
-    params.push_back(REnt{name, shape, nparam, n});
-    nparam += n;
-    return nparam - n;
-  }
 };
 
 namespace {
@@ -187,16 +143,16 @@ void reg_block(spff_r2u* p, RBlk& b) {
 int build(spff_r2u* p) {
   const spff_r2u_cfg& c = p->cfg;
   if (c.batch < 1 || c.depth < 1 || c.height < 1 || c.width < 1)
-    return rfail(SPFF_EINVAL, "invalid batch / depth / height / width");
-  if (c.in_ch < 1 || c.in_ch > 8) return rfail(SPFF_EINVAL, "in_ch must be 1..8");
+    return plan_fail(SPFF_EINVAL, "invalid batch / depth / height / width");
+  if (c.in_ch < 1 || c.in_ch > 8) return plan_fail(SPFF_EINVAL, "in_ch must be 1..8");
   if (c.num_classes < 2 || c.num_classes > 32)
-    return rfail(SPFF_EINVAL, "num_classes must be 2..32 (the sigmoid branch, K = 1, is not built)");
-  if (c.base < 8 || c.base % 8) return rfail(SPFF_EINVAL, "base must be a multiple of 8");
-  if (c.t < 1 || c.t > TMAX) return rfail(SPFF_EINVAL, "t must be 1..8");
+    return plan_fail(SPFF_EINVAL, "num_classes must be 2..32 (the sigmoid branch, K = 1, is not built)");
+  if (c.base < 8 || c.base % 8) return plan_fail(SPFF_EINVAL, "base must be a multiple of 8");
+  if (c.t < 1 || c.t > TMAX) return plan_fail(SPFF_EINVAL, "t must be 1..8");
   if (c.math < SPFF_MATH_F32 || c.math > SPFF_MATH_F16X3)
-    return rfail(SPFF_EINVAL, "math must be one of SPFF_MATH_*");
+    return plan_fail(SPFF_EINVAL, "math must be one of SPFF_MATH_*");
   if (c.depth % 16 || c.height % 16 || c.width % 16)
-    return rfail(SPFF_ESHAPE,
+    return plan_fail(SPFF_ESHAPE,
                  "D, H and W must be multiples of 16 (four MaxPool3d(2) whose outputs are "
                  "concatenated with the ConvTranspose3d outputs); the Lit wrapper pads");
   p->f = c.base;
@@ -326,12 +282,12 @@ int prep_weights(spff_r2u* p) {
     float* po = p->F(b.pk_out);
     // (level 0: head_pack zero-fills rows in_ch .. 31 of the forward image, which the
     //  8-channel rows of x_cl meet with zeros of their own)
-    RHIPCK(head_pack(p->P(b.w_inp), pi, pi + head_pack_dgrad_offset(kin, b.C), b.Cin, b.C, p->st));
-    RHIPCK(head_pack(p->P(b.w_out), po, po + head_pack_dgrad_offset(b.C, b.C), b.C, b.C, p->st));
+    PLAN_HIPCK(head_pack(p->P(b.w_inp), pi, pi + head_pack_dgrad_offset(kin, b.C), b.Cin, b.C, p->st));
+    PLAN_HIPCK(head_pack(p->P(b.w_out), po, po + head_pack_dgrad_offset(b.C, b.C), b.C, b.C, p->st));
     if (p->t > 1) {
       hipLaunchKernelGGL(k_r2u_double, dim3((b.C + 255) / 256), dim3(256), 0, p->st,
                          p->P(b.g_ru), p->P(b.b_ru), p->F(b.gb2), b.C);
-      RHIPCK(hipGetLastError());
+      PLAN_HIPCK(hipGetLastError());
     }
   }
   if (!p->pkb) return SPFF_OK;
@@ -339,7 +295,7 @@ int prep_weights(spff_r2u* p) {
   unsigned* sl = reinterpret_cast<unsigned*>(p->ws + p->wsl);
   PrepJobs pj;
   PackJobs kj;
-  if (f16) RHIPCK(spff::zero_async(sl, NBLK * sizeof(unsigned), p->st));
+  if (f16) PLAN_HIPCK(spff::zero_async(sl, NBLK * sizeof(unsigned), p->st));
   for (int i = 0; i < NBLK; ++i) {
     RBlk& b = p->blk[i];
     unsigned* wm = f16 ? sl + i : nullptr;
@@ -347,10 +303,10 @@ int prep_weights(spff_r2u* p) {
     if (f16) ok = ok && prep_absmax(&pj, p->P(b.w_ru), (int64_t)b.C * b.C * 27, wm);
     ok = ok && conv3d_pack_job(&kj, p->P(b.w_ru), p->F(b.pk[0]), 3, b.C, b.C, false, wm);
     ok = ok && conv3d_pack_job(&kj, p->P(b.w_ru), p->F(b.pk[1]), 3, b.C, b.C, true, wm);
-    if (!ok) return rfail(SPFF_EINVAL, "weight preparation table overflow");
+    if (!ok) return plan_fail(SPFF_EINVAL, "weight preparation table overflow");
   }
-  RHIPCK(prep_run(pj, p->st));
-  RHIPCK(conv3d_pack_many(kj, math, p->st));
+  PLAN_HIPCK(prep_run(pj, p->st));
+  PLAN_HIPCK(conv3d_pack_many(kj, math, p->st));
   return SPFF_OK;
 }
 
@@ -364,7 +320,7 @@ int conv_image(spff_r2u* p, const RBlk& b, bool dgrad, const Vol& v, const float
                 : nullptr;
     return SPFF_OK;
   }
-  RHIPCK(conv3d_pack(p->P(b.w_ru), p->F(p->wt), v, 3, b.C, b.C, dgrad, p->cfg.math, p->st));
+  PLAN_HIPCK(conv3d_pack(p->P(b.w_ru), p->F(p->wt), v, 3, b.C, b.C, dgrad, p->cfg.math, p->st));
   *img = p->F(p->wt);
   *wmax = nullptr;
   return SPFF_OK;
@@ -376,11 +332,11 @@ int in_fwd(spff_r2u* p, const Vol& v, int C, const float* y, const RStat& s, con
            const float* beta) {
   RedArgs a{};
   a.y = y;
-  RHIPCK(slab_reduce(RED_SUM, a, v, C, p->F(p->red_out), p->F(p->red_ws), p->st));
-  RHIPCK(in_mean(p->F(p->red_out), p->F(s.mean), v, C, p->st));
+  PLAN_HIPCK(slab_reduce(RED_SUM, a, v, C, p->F(p->red_out), p->F(p->red_ws), p->st));
+  PLAN_HIPCK(in_mean(p->F(p->red_out), p->F(s.mean), v, C, p->st));
   a.mean = p->F(s.mean);
-  RHIPCK(slab_reduce(RED_SQDEV, a, v, C, p->F(p->red_out), p->F(p->red_ws), p->st));
-  RHIPCK(in_rstd(p->F(p->red_out), gamma, beta, p->F(s.mean), p->F(s.rstd), p->F(s.al),
+  PLAN_HIPCK(slab_reduce(RED_SQDEV, a, v, C, p->F(p->red_out), p->F(p->red_ws), p->st));
+  PLAN_HIPCK(in_rstd(p->F(p->red_out), gamma, beta, p->F(s.mean), p->F(s.rstd), p->F(s.al),
                  p->F(s.de), v, C, p->st));
   return SPFF_OK;
 }
@@ -391,10 +347,10 @@ int in_bwd(spff_r2u* p, const Vol& v, int C, const float* y, const float* g, flo
   RedArgs a{};
   a.y = y; a.g = g; a.mean = p->F(s.mean); a.rstd = p->F(s.rstd);
   a.al = p->F(s.al); a.de = p->F(s.de); a.neg = 0.f;
-  RHIPCK(slab_reduce(RED_BWD_IN, a, v, C, p->F(p->red_out), p->F(p->red_ws), p->st));
-  RHIPCK(in_bwd_stats(p->F(p->red_out), gamma, dgamma, dbeta, p->F(p->kk1), p->F(p->kk2), v, C,
+  PLAN_HIPCK(slab_reduce(RED_BWD_IN, a, v, C, p->F(p->red_out), p->F(p->red_ws), p->st));
+  PLAN_HIPCK(in_bwd_stats(p->F(p->red_out), gamma, dgamma, dbeta, p->F(p->kk1), p->F(p->kk2), v, C,
                       p->st));
-  RHIPCK(in_bwd_apply(y, g, dy, p->F(s.mean), p->F(s.rstd), p->F(s.al), p->F(s.de), gamma,
+  PLAN_HIPCK(in_bwd_apply(y, g, dy, p->F(s.mean), p->F(s.rstd), p->F(s.al), p->F(s.de), gamma,
                       nullptr, nullptr, p->F(p->kk1), p->F(p->kk2), v, C, p->st, 0.f));
   return SPFF_OK;
 }
@@ -411,22 +367,22 @@ int fwd_block(spff_r2u* p, RBlk& b, const Src2& in, int kin) {
   const Vol& v = p->vol[b.lvl];
   const int C = b.C, math = p->cfg.math;
   const int64_t M = nvox(v);
-  RHIPCK(linear_fwd2(in, kin, p->F(b.pk_inp), nullptr, p->F(b.x1), C, C, M, p->st));
+  PLAN_HIPCK(linear_fwd2(in, kin, p->F(b.pk_inp), nullptr, p->F(b.x1), C, C, M, p->st));
   const float* cur = p->F(b.x1);
   for (int k = 0; k < p->t; ++k) {
     const float* img;
     const unsigned* wmax;
-    RCK(conv_image(p, b, false, v, &img, &wmax));
-    RHIPCK(conv3d_run(src1(cur, C), img, dst1(p->F(b.y[k]), C), v, 3, C, C, false, math, p->st,
+    PLAN_CK(conv_image(p, b, false, v, &img, &wmax));
+    PLAN_HIPCK(conv3d_run(src1(cur, C), img, dst1(p->F(b.y[k]), C), v, 3, C, C, false, math, p->st,
                       p->F(p->wg_ws), nullptr, 0, wmax));
-    RCK(in_fwd(p, v, C, p->F(b.y[k]), b.st[k], ru_gamma(p, b, k), ru_beta(p, b, k)));
-    RHIPCK(act_apply(p->F(b.y[k]), p->F(b.a[k]), p->F(b.st[k].al), p->F(b.st[k].de), nullptr,
+    PLAN_CK(in_fwd(p, v, C, p->F(b.y[k]), b.st[k], ru_gamma(p, b, k), ru_beta(p, b, k)));
+    PLAN_HIPCK(act_apply(p->F(b.y[k]), p->F(b.a[k]), p->F(b.st[k].al), p->F(b.st[k].de), nullptr,
                      nullptr, v, C, p->st, 0.f));
     cur = p->F(b.a[k]);
   }
-  RHIPCK(linear_fwd(cur, C, C, p->F(b.pk_out), nullptr, p->F(b.s), C, C, M, p->F(b.x1), C, p->st));
-  RCK(in_fwd(p, v, C, p->F(b.s), b.bn, p->P(b.g_bn), p->P(b.b_bn)));
-  RHIPCK(act_apply(p->F(b.s), p->F(b.o), p->F(b.bn.al), p->F(b.bn.de), nullptr, nullptr, v, C,
+  PLAN_HIPCK(linear_fwd(cur, C, C, p->F(b.pk_out), nullptr, p->F(b.s), C, C, M, p->F(b.x1), C, p->st));
+  PLAN_CK(in_fwd(p, v, C, p->F(b.s), b.bn, p->P(b.g_bn), p->P(b.b_bn)));
+  PLAN_HIPCK(act_apply(p->F(b.s), p->F(b.o), p->F(b.bn.al), p->F(b.bn.de), nullptr, nullptr, v, C,
                    p->st, 0.f));
   return SPFF_OK;
 }
@@ -441,38 +397,38 @@ int bwd_block(spff_r2u* p, RBlk& b, const float* dout, const Dst2* dx, const Src
   float* gn = p->F(p->G_2);
   float* wgs = p->F(p->wg_ws);
   // o = relu(IN_bn(s)): ds, which is also the residual branch's share of dx1
-  RCK(in_bwd(p, v, C, p->F(b.s), dout, ds, b.bn, p->P(b.g_bn), p->DP(b.g_bn), p->DP(b.b_bn)));
+  PLAN_CK(in_bwd(p, v, C, p->F(b.s), dout, ds, b.bn, p->P(b.g_bn), p->DP(b.g_bn), p->DP(b.b_bn)));
   // s = x1 + out(a_t)
-  RHIPCK(linear_wgrad(p->F(b.a[T - 1]), C, C, ds, C, C, p->DP(b.w_out), p->F(p->db_scr), M, wgs,
+  PLAN_HIPCK(linear_wgrad(p->F(b.a[T - 1]), C, C, ds, C, C, p->DP(b.w_out), p->F(p->db_scr), M, wgs,
                       p->st));
-  RHIPCK(linear_dgrad(ds, C, C, p->F(b.pk_out) + head_pack_dgrad_offset(C, C), g, C, C, M, nullptr,
+  PLAN_HIPCK(linear_dgrad(ds, C, C, p->F(b.pk_out) + head_pack_dgrad_offset(C, C), g, C, C, M, nullptr,
                       p->st));
   // the recurrence, steps t .. 1: g holds dL/da_k
   for (int k = T - 1; k >= 0; --k) {
     const bool last = k == T - 1;
     float* dgam = last ? p->DP(b.g_ru) : p->F(p->tmp_gb);
     float* dbet = last ? p->DP(b.b_ru) : p->F(p->tmp_gb) + C;
-    RCK(in_bwd(p, v, C, p->F(b.y[k]), g, g, b.st[k], ru_gamma(p, b, k), dgam, dbet));
+    PLAN_CK(in_bwd(p, v, C, p->F(b.y[k]), g, g, b.st[k], ru_gamma(p, b, k), dgam, dbet));
     if (!last) {  // affine (2 gamma, 2 beta): d/dgamma = 2 d/d(2 gamma)
-      RHIPCK(r2u_acc(p->DP(b.g_ru), dgam, C, 2.f, p->st));
-      RHIPCK(r2u_acc(p->DP(b.b_ru), dbet, C, 2.f, p->st));
+      PLAN_HIPCK(r2u_acc(p->DP(b.g_ru), dgam, C, 2.f, p->st));
+      PLAN_HIPCK(r2u_acc(p->DP(b.b_ru), dbet, C, 2.f, p->st));
     }
     const float* xin = k == 0 ? p->F(b.x1) : p->F(b.a[k - 1]);
     float* dw = last ? p->DP(b.w_ru) : p->F(p->tmp_w);
-    RHIPCK(conv3d_wgrad(src1(xin, C), g, C, dw, v, 3, C, C, math, wgs, p->st));
-    if (!last) RHIPCK(r2u_acc(p->DP(b.w_ru), dw, nw, 1.f, p->st));
+    PLAN_HIPCK(conv3d_wgrad(src1(xin, C), g, C, dw, v, 3, C, C, math, wgs, p->st));
+    if (!last) PLAN_HIPCK(r2u_acc(p->DP(b.w_ru), dw, nw, 1.f, p->st));
     const float* img;
     const unsigned* wmax;
-    RCK(conv_image(p, b, true, v, &img, &wmax));
-    RHIPCK(conv3d_run(src1(g, C), img, dst1(gn, C), v, 3, C, C, true, math, p->st, wgs, nullptr, 0,
+    PLAN_CK(conv_image(p, b, true, v, &img, &wmax));
+    PLAN_HIPCK(conv3d_run(src1(g, C), img, dst1(gn, C), v, 3, C, C, true, math, p->st, wgs, nullptr, 0,
                       wmax));
     std::swap(g, gn);
   }
   // x1 feeds the recurrent unit and the residual: dx1 = ds + (the unit's input gradient)
-  RHIPCK(r2u_acc(ds, g, M * C, 1.f, p->st));
-  RHIPCK(linear_wgrad2(in, b.Cin, ds, C, C, p->DP(b.w_inp), p->F(p->db_scr), M, wgs, p->st));
+  PLAN_HIPCK(r2u_acc(ds, g, M * C, 1.f, p->st));
+  PLAN_HIPCK(linear_wgrad2(in, b.Cin, ds, C, C, p->DP(b.w_inp), p->F(p->db_scr), M, wgs, p->st));
   if (dx)
-    RHIPCK(linear_dgrad2(ds, C, C, p->F(b.pk_inp) + head_pack_dgrad_offset(b.Cin, C), *dx, b.Cin,
+    PLAN_HIPCK(linear_dgrad2(ds, C, C, p->F(b.pk_inp) + head_pack_dgrad_offset(b.Cin, C), *dx, b.Cin,
                          M, 0, p->st));
   return SPFF_OK;
 }
@@ -481,36 +437,36 @@ int forward(spff_r2u* p, const float* x, float* logits) {
   const spff_r2u_cfg& c = p->cfg;
   const int f = p->f;
   const Vol& v0 = p->vol[0];
-  RHIPCK(ncdhw_to_ndhwc(x, p->F(p->x_cl), v0, c.in_ch, p->ldx, p->st));
-  RCK(prep_weights(p));
+  PLAN_HIPCK(ncdhw_to_ndhwc(x, p->F(p->x_cl), v0, c.in_ch, p->ldx, p->st));
+  PLAN_CK(prep_weights(p));
   RBlk* B = p->blk;
   Src2 in = src1(p->F(p->x_cl), p->ldx);
   int kin = p->ldx;
   for (int l = 0; l < 4; ++l) {
-    RCK(fwd_block(p, B[l], in, kin));
-    RHIPCK(maxpool3_fwd(p->F(B[l].o), p->F(p->pool[l]),
+    PLAN_CK(fwd_block(p, B[l], in, kin));
+    PLAN_HIPCK(maxpool3_fwd(p->F(B[l].o), p->F(p->pool[l]),
                         reinterpret_cast<uint8_t*>(p->ws + p->pidx[l]), p->vol[l], f << l, p->st));
     in = src1(p->F(p->pool[l]), f << l);
     kin = f << l;
   }
-  RCK(fwd_block(p, B[4], in, kin));
+  PLAN_CK(fwd_block(p, B[4], in, kin));
   const float* prev = p->F(B[4].o);
   for (int u = 0; u < NUP; ++u) {
     RUp& U = p->up[u];
     float* pk = p->F(U.pk);
-    RHIPCK(upconv_pack(p->P(U.w), pk, pk + upconv_pack_dgrad_offset(U.Cin, U.Cout, NSUB), U.Cin,
+    PLAN_HIPCK(upconv_pack(p->P(U.w), pk, pk + upconv_pack_dgrad_offset(U.Cin, U.Cout, NSUB), U.Cin,
                        U.Cout, p->st, NSUB));
-    RHIPCK(upconv_fwd(prev, pk, p->P(U.b), p->F(U.out), p->vol[U.lvl_low], U.Cin, U.Cout, p->st,
+    PLAN_HIPCK(upconv_fwd(prev, pk, p->P(U.b), p->F(U.out), p->vol[U.lvl_low], U.Cin, U.Cout, p->st,
                       NSUB, p->cfg.math));
     RBlk& d = B[5 + u];
     const RBlk& skip = B[3 - u];
     // torch.cat([up(x), skip], dim=1) read in place through the two-source view
-    RCK(fwd_block(p, d, Src2{p->F(U.out), p->F(skip.o), U.Cout, U.Cout, U.Cout}, 2 * U.Cout));
+    PLAN_CK(fwd_block(p, d, Src2{p->F(U.out), p->F(skip.o), U.Cout, U.Cout, U.Cout}, 2 * U.Cout));
     prev = p->F(d.o);
   }
   float* hp = p->F(p->head_pk);
-  RHIPCK(head_pack(p->P(p->head_w), hp, hp + head_pack_dgrad_offset(f, p->K), f, p->K, p->st));
-  RHIPCK(head_fwd(prev, hp, p->P(p->head_b), logits, nvox(v0), f, p->K, p->st, p->cfg.math));
+  PLAN_HIPCK(head_pack(p->P(p->head_w), hp, hp + head_pack_dgrad_offset(f, p->K), f, p->K, p->st));
+  PLAN_HIPCK(head_fwd(prev, hp, p->P(p->head_b), logits, nvox(v0), f, p->K, p->st, p->cfg.math));
   return SPFF_OK;
 }
 
@@ -519,9 +475,9 @@ int backward(spff_r2u* p, const float* dl) {
   const int64_t V0 = nvox(p->vol[0]);
   RBlk* B = p->blk;
   float* hp = p->F(p->head_pk);
-  RHIPCK(head_wgrad(p->F(B[8].o), dl, p->DP(p->head_w), p->DP(p->head_b), V0, f, p->K,
+  PLAN_HIPCK(head_wgrad(p->F(B[8].o), dl, p->DP(p->head_w), p->DP(p->head_b), V0, f, p->K,
                     p->F(p->wg_ws), p->st));
-  RHIPCK(head_dgrad(dl, hp + head_pack_dgrad_offset(f, p->K), p->F(p->G_out), V0, f, p->K, p->st,
+  PLAN_HIPCK(head_dgrad(dl, hp + head_pack_dgrad_offset(f, p->K), p->F(p->G_out), V0, f, p->K, p->st,
                     p->cfg.math));
   for (int k = 0; k < NUP; ++k) {  // d1 <- up1 <- d2 ... <- up4
     const int bi = 8 - k, ui = 3 - k;
@@ -529,27 +485,27 @@ int backward(spff_r2u* p, const float* dl) {
     RUp& U = p->up[ui];
     const int C = d.C, lvl = d.lvl;
     Dst2 dx{p->F(p->G_dx), p->F(p->dskip[lvl]), C, C, C};
-    RCK(bwd_block(p, d, p->F(p->G_out), &dx, Src2{p->F(U.out), p->F(B[lvl].o), C, C, C}));
+    PLAN_CK(bwd_block(p, d, p->F(p->G_out), &dx, Src2{p->F(U.out), p->F(B[lvl].o), C, C, C}));
     const Vol& low = p->vol[U.lvl_low];
-    RHIPCK(upconv_wgrad(p->F(B[bi - 1].o), p->F(p->G_dx), C, p->DP(U.w), p->DP(U.b), low, U.Cin,
+    PLAN_HIPCK(upconv_wgrad(p->F(B[bi - 1].o), p->F(p->G_dx), C, p->DP(U.w), p->DP(U.b), low, U.Cin,
                         U.Cout, p->F(p->wg_ws), p->st, NSUB, p->cfg.math));
     float* pk = p->F(U.pk);
-    RHIPCK(upconv_dgrad(p->F(p->G_dx), C, pk + upconv_pack_dgrad_offset(U.Cin, U.Cout, NSUB),
+    PLAN_HIPCK(upconv_dgrad(p->F(p->G_dx), C, pk + upconv_pack_dgrad_offset(U.Cin, U.Cout, NSUB),
                         p->F(p->G_out), low, U.Cin, U.Cout, p->st, NSUB, p->cfg.math));
   }
   {
     Dst2 dx = dst1(p->F(p->G_dx), 8 * f);
-    RCK(bwd_block(p, B[4], p->F(p->G_out), &dx, src1(p->F(p->pool[3]), 8 * f)));
+    PLAN_CK(bwd_block(p, B[4], p->F(p->G_out), &dx, src1(p->F(p->pool[3]), 8 * f)));
   }
   for (int l = 3; l >= 0; --l) {
     const int C = f << l;
-    RHIPCK(maxpool3_bwd_add(p->F(p->G_dx), reinterpret_cast<const uint8_t*>(p->ws + p->pidx[l]),
+    PLAN_HIPCK(maxpool3_bwd_add(p->F(p->G_dx), reinterpret_cast<const uint8_t*>(p->ws + p->pidx[l]),
                             p->F(p->dskip[l]), C, p->F(p->dskip[l]), p->vol[l], C, p->st));
     if (l > 0) {
       Dst2 dx = dst1(p->F(p->G_dx), C / 2);
-      RCK(bwd_block(p, B[l], p->F(p->dskip[l]), &dx, src1(p->F(p->pool[l - 1]), C / 2)));
+      PLAN_CK(bwd_block(p, B[l], p->F(p->dskip[l]), &dx, src1(p->F(p->pool[l - 1]), C / 2)));
     } else {
-      RCK(bwd_block(p, B[0], p->F(p->dskip[0]), nullptr, src1(p->F(p->x_cl), p->ldx)));
+      PLAN_CK(bwd_block(p, B[0], p->F(p->dskip[0]), nullptr, src1(p->F(p->x_cl), p->ldx)));
     }
   }
   return SPFF_OK;
@@ -561,16 +517,7 @@ int backward(spff_r2u* p, const float* dl) {
 extern "C" {
 
 int spff_r2u_create(const spff_r2u_cfg* cfg, spff_r2u** out) {
-  if (!cfg || !out) return rfail(SPFF_EINVAL, "null argument");
-  spff_r2u* p = new spff_r2u();
-  p->cfg = *cfg;
-  const int r = build(p);
-  if (r != SPFF_OK) {
-    delete p;
-    return r;
-  }
-  *out = p;
-  return SPFF_OK;
+  return plan_create(cfg, out, build);
 }
 
 void spff_r2u_destroy(spff_r2u* p) { delete p; }
@@ -579,15 +526,8 @@ int spff_r2u_num_params(const spff_r2u* p) { return p ? (int)p->params.size() : 
 
 int spff_r2u_param_info(const spff_r2u* p, int i, const char** name, int* ndim, int64_t shape[5],
                         int64_t* offset, int64_t* numel) {
-  if (!p || i < 0 || i >= (int)p->params.size()) return rfail(SPFF_EINVAL, "param index");
-  const REnt& e = p->params[i];
-  if (name) *name = e.name.c_str();
-  if (ndim) *ndim = (int)e.shape.size();
-  if (shape)
-    for (int k = 0; k < 5; ++k) shape[k] = k < (int)e.shape.size() ? e.shape[k] : 1;
-  if (offset) *offset = e.off;
-  if (numel) *numel = e.numel;
-  return SPFF_OK;
+  if (!p) return plan_fail(SPFF_EINVAL, "param index");
+  return plan_param_info(p->params, i, name, ndim, shape, offset, numel);
 }
 
 int64_t spff_r2u_param_floats(const spff_r2u* p) { return p ? p->nparam : 0; }
@@ -595,35 +535,23 @@ size_t spff_r2u_workspace_bytes(const spff_r2u* p) { return p ? p->total : 0; }
 
 int spff_r2u_forward(spff_r2u* p, const float* x, const float* params, float* logits, void* ws,
                      void* stream) {
-  if (!p || !x || !params || !logits || !ws) return rfail(SPFF_EINVAL, "null argument");
-  p->ws = static_cast<char*>(ws);
-  p->prm = params;
-  p->dprm = nullptr;
-  p->st = static_cast<hipStream_t>(stream);
+  if (!p || !x || !params || !logits || !ws) return plan_fail(SPFF_EINVAL, "null argument");
+  p->bind(ws, params, nullptr, stream);
   return forward(p, x, logits);
 }
 
 int spff_r2u_backward(spff_r2u* p, const float* dlogits, const float* params, float* dparams,
                       void* ws, void* stream) {
-  if (!p || !dlogits || !params || !dparams || !ws) return rfail(SPFF_EINVAL, "null argument");
-  p->ws = static_cast<char*>(ws);
-  p->prm = params;
-  p->dprm = dparams;
-  p->st = static_cast<hipStream_t>(stream);
+  if (!p || !dlogits || !params || !dparams || !ws) return plan_fail(SPFF_EINVAL, "null argument");
+  p->bind(ws, params, dparams, stream);
   return backward(p, dlogits);
 }
 
 int spff_r2u_saved_tensor(const spff_r2u* p, void* ws, const char* name, const float** ptr,
                           int64_t* nv, int* ch) {
-  if (!p || !ws || !name || !ptr) return rfail(SPFF_EINVAL, "null argument");
-  const char* base = static_cast<const char*>(ws);
+  if (!p || !ws || !name || !ptr) return plan_fail(SPFF_EINVAL, "null argument");
   const std::string n(name);
-  auto ret = [&](size_t off, const Vol& v, int c) {
-    *ptr = reinterpret_cast<const float*>(base + off);
-    if (nv) *nv = nvox(v);
-    if (ch) *ch = c;
-    return SPFF_OK;
-  };
+  const SavedOut ret{ws, ptr, nv, ch};
   for (int i = 0; i < NBLK; ++i) {
     const RBlk& b = p->blk[i];
     const Vol& v = p->vol[b.lvl];
@@ -632,7 +560,7 @@ int spff_r2u_saved_tensor(const spff_r2u* p, void* ws, const char* name, const f
     for (int k = 0; k < p->t; ++k)
       if (n == b.name + ".ru" + std::to_string(k + 1)) return ret(b.a[k], v, b.C);
   }
-  return rfail(SPFF_EINVAL, "unknown saved tensor " + n);
+  return plan_fail(SPFF_EINVAL, "unknown saved tensor " + n);
 }
 
 size_t spff_r2u_dice_loss_ws_bytes(int batch, int num_classes) {
@@ -642,11 +570,11 @@ size_t spff_r2u_dice_loss_ws_bytes(int batch, int num_classes) {
 int spff_r2u_dice_loss(const float* logits, const int64_t* labels, int batch,
                        int64_t vox_per_sample, int num_classes, int use_ignore, int ignore_index,
                        float* out4, float* dlogits, void* ws, void* stream) {
-  if (!logits || !labels || !out4 || !dlogits || !ws) return rfail(SPFF_EINVAL, "null argument");
-  if (batch < 1 || vox_per_sample < 1) return rfail(SPFF_EINVAL, "invalid batch / vox_per_sample");
+  if (!logits || !labels || !out4 || !dlogits || !ws) return plan_fail(SPFF_EINVAL, "null argument");
+  if (batch < 1 || vox_per_sample < 1) return plan_fail(SPFF_EINVAL, "invalid batch / vox_per_sample");
   if (num_classes < 2 || num_classes > 32)
-    return rfail(SPFF_EINVAL, "num_classes must be 2..32 (the sigmoid branch, K = 1, is not built)");
-  RHIPCK(r2u_dice_loss(logits, labels, batch, vox_per_sample, num_classes, use_ignore,
+    return plan_fail(SPFF_EINVAL, "num_classes must be 2..32 (the sigmoid branch, K = 1, is not built)");
+  PLAN_HIPCK(r2u_dice_loss(logits, labels, batch, vox_per_sample, num_classes, use_ignore,
                        ignore_index, out4, dlogits, ws, static_cast<hipStream_t>(stream)));
   return SPFF_OK;
 }

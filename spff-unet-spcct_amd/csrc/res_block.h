@@ -1,19 +1,16 @@
-// The pieces that the MONAI-style plans (swin.hip, unetr.hip) share: the parameter table
-// entry, packed Linear / 1x1 conv, UnetResBlock and 2x2x2 transposed-conv descriptors, and
-// the UnetResBlock forward / backward schedule on the engine's convs and InstanceNorm
-// kernels.  Everything here is internal to the including translation unit (namespace spff,
-// anonymous).  A plan type P must provide, under these names:
-//   float* F(size_t), const float* P(int64_t), float* DP(int64_t)   workspace / param / grad
-//   reg(name, shape), alloc(bytes)                                   registration (reg_lin, reg_rb)
-//   char* ws; hipStream_t st; cfg.math; Vol vol[]; RB rb[P::kNRB]
+// The pieces that the MONAI-style plans (swin.hip, unetr.hip) share: packed Linear / 1x1
+// conv, UnetResBlock and 2x2x2 transposed-conv descriptors, and the UnetResBlock forward /
+// backward schedule on the engine's convs and InstanceNorm kernels.  Everything here is
+// internal to the including translation unit (namespace spff, anonymous).  A plan type P
+// derives from PlanBase (plan_base.h: F / P / DP, reg, alloc, ws, st, PLAN_HIPCK / PLAN_CK)
+// and provides, under these names:
+//   cfg.math; Vol vol[]; RB rb[P::kNRB]; int maxC
 //   workspace offsets ones, zeros [maxC], dummy [2 maxC], red_ws, red_out, kk1, kk2 [B maxC],
 //   wg_ws, cst, G_dz, G_dy2, G_da1, and pkb ? rb[i].pk[] + wsl [kNRB][2] : wt, sized as
 //   build() of swin.hip / unetr.hip sizes them
-// SHIPCK / SCK return the C ABI's error code from the enclosing function.
 #pragma once
-#include "spff_internal.h"
+#include "plan_base.h"
 #include "swin_internal.h"
-#include "spff.h"
 
 #include <algorithm>
 #include <string>
@@ -21,25 +18,6 @@
 
 namespace spff {
 namespace {
-
-inline int sfail(int code, const std::string& m) { return set_error(code, m.c_str()); }
-#define SHIPCK(expr)                                                                       \
-  do {                                                                                     \
-    hipError_t _e = (expr);                                                                \
-    if (_e != hipSuccess)                                                                  \
-      return sfail(SPFF_EHIP, std::string(#expr) + " -> " + hipGetErrorString(_e));        \
-  } while (0)
-#define SCK(expr)                   \
-  do {                              \
-    int _r = (expr);                \
-    if (_r != SPFF_OK) return _r;   \
-  } while (0)
-
-struct SEnt {
-  std::string name;
-  std::vector<int64_t> shape;
-  int64_t off, numel;
-};
 
 struct Lin {  // nn.Linear / 1x1 conv W [N][K] (+ b)
   int64_t w = -1, b = -1;
@@ -63,9 +41,6 @@ struct Up {
   int64_t w = -1;
   size_t pk, out;
 };
-
-inline int rup(int a, int b) { return (a + b - 1) / b * b; }
-inline size_t fbytes(int64_t n) { return (size_t)n * sizeof(float); }
 
 template <class P>
 void reg_lin(P* p, Lin& l, const std::string& name, int K, int N, bool bias,
@@ -95,11 +70,11 @@ template <class P>
 int in_stats(P* p, const Vol& v, int C, size_t y, const size_t* st4) {
   RedArgs a{};
   a.y = p->F(y);
-  SHIPCK(slab_reduce(RED_SUM, a, v, C, p->F(p->red_out), p->F(p->red_ws), p->st));
-  SHIPCK(in_mean(p->F(p->red_out), p->F(st4[0]), v, C, p->st));
+  PLAN_HIPCK(slab_reduce(RED_SUM, a, v, C, p->F(p->red_out), p->F(p->red_ws), p->st));
+  PLAN_HIPCK(in_mean(p->F(p->red_out), p->F(st4[0]), v, C, p->st));
   a.mean = p->F(st4[0]);
-  SHIPCK(slab_reduce(RED_SQDEV, a, v, C, p->F(p->red_out), p->F(p->red_ws), p->st));
-  SHIPCK(in_rstd(p->F(p->red_out), p->F(p->ones), p->F(p->zeros), p->F(st4[0]), p->F(st4[1]),
+  PLAN_HIPCK(slab_reduce(RED_SQDEV, a, v, C, p->F(p->red_out), p->F(p->red_ws), p->st));
+  PLAN_HIPCK(in_rstd(p->F(p->red_out), p->F(p->ones), p->F(p->zeros), p->F(st4[0]), p->F(st4[1]),
                  p->F(st4[2]), p->F(st4[3]), v, C, p->st));
   return SPFF_OK;
 }
@@ -116,7 +91,7 @@ int prep_weights(P* p) {
   unsigned* sl = reinterpret_cast<unsigned*>(p->ws + p->wsl);
   PrepJobs pj;
   PackJobs kj;
-  if (f16) SHIPCK(spff::zero_async(sl, P::kNRB * 2 * sizeof(unsigned), p->st));
+  if (f16) PLAN_HIPCK(spff::zero_async(sl, P::kNRB * 2 * sizeof(unsigned), p->st));
   for (int i = 0; i < P::kNRB; ++i) {
     RB& r = p->rb[i];
     unsigned* w1 = f16 ? sl + 2 * i : nullptr;
@@ -130,10 +105,10 @@ int prep_weights(P* p) {
     ok = ok && conv3d_pack_job(&kj, p->P(r.w2), p->F(r.pk[1]), 3, r.C, r.C, false, w2);
     ok = ok && conv3d_pack_job(&kj, p->P(r.w2), p->F(r.pk[2]), 3, r.C, r.C, true, w2);
     if (r.pk[3]) ok = ok && conv3d_pack_job(&kj, p->P(r.w1), p->F(r.pk[3]), 3, r.Cin, r.C, true, w1);
-    if (!ok) return sfail(SPFF_EINVAL, "weight preparation table overflow");
+    if (!ok) return plan_fail(SPFF_EINVAL, "weight preparation table overflow");
   }
-  SHIPCK(prep_run(pj, p->st));
-  SHIPCK(conv3d_pack_many(kj, math, p->st));
+  PLAN_HIPCK(prep_run(pj, p->st));
+  PLAN_HIPCK(conv3d_pack_many(kj, math, p->st));
   return SPFF_OK;
 }
 // conv k of residual block r (0: w1 fwd, 1: w2 fwd, 2: w2 dgrad, 3: w1 dgrad): its image
@@ -144,14 +119,14 @@ int conv_image(P* p, const RB& r, int k, const Vol& v, const float** img,
   const bool c1 = k == 0 || k == 3;
   const int ri = (int)(&r - p->rb);
   if (p->pkb) {
-    if (!r.pk[k]) return sfail(SPFF_EINVAL, "no batched image for this conv");
+    if (!r.pk[k]) return plan_fail(SPFF_EINVAL, "no batched image for this conv");
     *img = p->F(r.pk[k]);
     *wmax = p->cfg.math == SPFF_MATH_F16X3
                 ? reinterpret_cast<const unsigned*>(p->ws + p->wsl) + 2 * ri + (c1 ? 0 : 1)
                 : nullptr;
     return SPFF_OK;
   }
-  SHIPCK(conv3d_pack(p->P(c1 ? r.w1 : r.w2), p->F(p->wt), v, 3, c1 ? r.Cin : r.C, r.C, k >= 2,
+  PLAN_HIPCK(conv3d_pack(p->P(c1 ? r.w1 : r.w2), p->F(p->wt), v, 3, c1 ? r.Cin : r.C, r.C, k >= 2,
                      p->cfg.math, p->st));
   *img = p->F(p->wt);
   *wmax = nullptr;
@@ -165,12 +140,12 @@ int conv_in(P* p, const Src2& in, const RB& r, int k, const Vol& v, int Cin, int
   const int math = p->cfg.math;
   const float* img;
   const unsigned* wmax;
-  SCK(conv_image(p, r, k, v, &img, &wmax));
+  PLAN_CK(conv_image(p, r, k, v, &img, &wmax));
   const bool fuse = conv3d_fuses_stats(v, 3, Cin, C, math);
-  SHIPCK(conv3d_run(in, img, dst1(p->F(y), C), v, 3, Cin, C, false, math, p->st,
+  PLAN_HIPCK(conv3d_run(in, img, dst1(p->F(y), C), v, 3, Cin, C, false, math, p->st,
                     p->F(p->wg_ws), fuse ? p->F(p->cst) : nullptr, 0, wmax));
   if (fuse) {
-    SHIPCK(conv3d_in_stats_fin(p->F(p->cst), v, 3, Cin, C, math, p->F(p->ones), p->F(p->zeros),
+    PLAN_HIPCK(conv3d_in_stats_fin(p->F(p->cst), v, 3, Cin, C, math, p->F(p->ones), p->F(p->zeros),
                                p->F(st4[0]), p->F(st4[1]), p->F(st4[2]), p->F(st4[3]), p->st));
     return SPFF_OK;
   }
@@ -181,17 +156,17 @@ template <class P>
 int rb_fwd(P* p, RB& r, const Src2& in, const float* ident) {
   const Vol& v = p->vol[r.L];
   const int C = r.C;
-  SCK(conv_in(p, in, r, 0, v, r.Cin, C, r.y1, r.st[0]));
-  SHIPCK(act_apply(p->F(r.y1), p->F(r.a1), p->F(r.st[0][2]), p->F(r.st[0][3]), nullptr, nullptr, v,
+  PLAN_CK(conv_in(p, in, r, 0, v, r.Cin, C, r.y1, r.st[0]));
+  PLAN_HIPCK(act_apply(p->F(r.y1), p->F(r.a1), p->F(r.st[0][2]), p->F(r.st[0][3]), nullptr, nullptr, v,
                    C, p->st));
-  SCK(conv_in(p, src1(p->F(r.a1), C), r, 1, v, C, C, r.y2, r.st[1]));
+  PLAN_CK(conv_in(p, src1(p->F(r.a1), C), r, 1, v, C, C, r.y2, r.st[1]));
   if (r.has3) {
     float* pk = p->F(r.c3.pk);
-    SHIPCK(head_pack(p->P(r.c3.w), pk, pk + head_pack_dgrad_offset(r.Cin, C), r.Cin, C, p->st));
-    SHIPCK(linear_fwd2(in, r.Cin, pk, nullptr, p->F(r.y3), C, C, nvox(v), p->st));
-    SCK(in_stats(p, v, C, r.y3, r.st[2]));
+    PLAN_HIPCK(head_pack(p->P(r.c3.w), pk, pk + head_pack_dgrad_offset(r.Cin, C), r.Cin, C, p->st));
+    PLAN_HIPCK(linear_fwd2(in, r.Cin, pk, nullptr, p->F(r.y3), C, C, nvox(v), p->st));
+    PLAN_CK(in_stats(p, v, C, r.y3, r.st[2]));
   }
-  SHIPCK(res_act(p->F(r.y2), p->F(r.st[1][2]), p->F(r.st[1][3]), r.has3 ? p->F(r.y3) : nullptr,
+  PLAN_HIPCK(res_act(p->F(r.y2), p->F(r.st[1][2]), p->F(r.st[1][3]), r.has3 ? p->F(r.y3) : nullptr,
                  p->F(r.st[2][2]), p->F(r.st[2][3]), ident, nullptr, p->F(r.out), v, C, p->st));
   return SPFF_OK;
 }
@@ -203,11 +178,11 @@ int in_bwd(P* p, const Vol& v, int C, size_t y, const float* g, float* dy,
   RedArgs a{};
   a.y = p->F(y); a.g = g; a.mean = p->F(st4[0]); a.rstd = p->F(st4[1]);
   a.al = p->F(st4[2]); a.de = p->F(st4[3]); a.neg = neg;
-  SHIPCK(slab_reduce(RED_BWD_IN, a, v, C, p->F(p->red_out), p->F(p->red_ws), p->st));
+  PLAN_HIPCK(slab_reduce(RED_BWD_IN, a, v, C, p->F(p->red_out), p->F(p->red_ws), p->st));
   float* dm = p->F(p->dummy);
-  SHIPCK(in_bwd_stats(p->F(p->red_out), p->F(p->ones), dm, dm + p->maxC, p->F(p->kk1),
+  PLAN_HIPCK(in_bwd_stats(p->F(p->red_out), p->F(p->ones), dm, dm + p->maxC, p->F(p->kk1),
                       p->F(p->kk2), v, C, p->st));
-  SHIPCK(in_bwd_apply(p->F(y), g, dy, p->F(st4[0]), p->F(st4[1]), p->F(st4[2]), p->F(st4[3]),
+  PLAN_HIPCK(in_bwd_apply(p->F(y), g, dy, p->F(st4[0]), p->F(st4[1]), p->F(st4[2]), p->F(st4[3]),
                       p->F(p->ones), nullptr, nullptr, p->F(p->kk1), p->F(p->kk2), v, C, p->st,
                       neg));
   return SPFF_OK;
@@ -223,33 +198,33 @@ int rb_bwd(P* p, RB& r, const float* dout, const Src2& in, const float* ident,
   float* dz = p->F(p->G_dz);
   float* dy2 = p->F(p->G_dy2);
   float* da1 = p->F(p->G_da1);
-  SHIPCK(res_act(p->F(r.y2), p->F(r.st[1][2]), p->F(r.st[1][3]), r.has3 ? p->F(r.y3) : nullptr,
+  PLAN_HIPCK(res_act(p->F(r.y2), p->F(r.st[1][2]), p->F(r.st[1][3]), r.has3 ? p->F(r.y3) : nullptr,
                  p->F(r.st[2][2]), p->F(r.st[2][3]), ident, dout, dz, v, C, p->st));
-  SCK(in_bwd(p, v, C, r.y2, dz, dy2, r.st[1], 1.f));
-  SHIPCK(conv3d_wgrad(src1(p->F(r.a1), C), dy2, C, p->DP(r.w2), v, 3, C, C, math, p->F(p->wg_ws),
+  PLAN_CK(in_bwd(p, v, C, r.y2, dz, dy2, r.st[1], 1.f));
+  PLAN_HIPCK(conv3d_wgrad(src1(p->F(r.a1), C), dy2, C, p->DP(r.w2), v, 3, C, C, math, p->F(p->wg_ws),
                       p->st));
   const float* img;
   const unsigned* wmax;
-  SCK(conv_image(p, r, 2, v, &img, &wmax));
-  SHIPCK(conv3d_run(src1(dy2, C), img, dst1(da1, C), v, 3, C, C, true, math, p->st,
+  PLAN_CK(conv_image(p, r, 2, v, &img, &wmax));
+  PLAN_HIPCK(conv3d_run(src1(dy2, C), img, dst1(da1, C), v, 3, C, C, true, math, p->st,
                     p->F(p->wg_ws), nullptr, 0, wmax));
-  SCK(in_bwd(p, v, C, r.y1, da1, da1, r.st[0], 0.01f));
-  SHIPCK(conv3d_wgrad(in, da1, C, p->DP(r.w1), v, 3, r.Cin, C, math, p->F(p->wg_ws), p->st));
+  PLAN_CK(in_bwd(p, v, C, r.y1, da1, da1, r.st[0], 0.01f));
+  PLAN_HIPCK(conv3d_wgrad(in, da1, C, p->DP(r.w1), v, 3, r.Cin, C, math, p->F(p->wg_ws), p->st));
   if (dsrc) {
-    SCK(conv_image(p, r, 3, v, &img, &wmax));
-    SHIPCK(conv3d_run(src1(da1, C), img, *dsrc, v, 3, r.Cin, C, true, math, p->st,
+    PLAN_CK(conv_image(p, r, 3, v, &img, &wmax));
+    PLAN_HIPCK(conv3d_run(src1(da1, C), img, *dsrc, v, 3, r.Cin, C, true, math, p->st,
                       p->F(p->wg_ws), nullptr, 0, wmax));
   }
   if (r.has3) {
-    SCK(in_bwd(p, v, C, r.y3, dz, dy2, r.st[2], 1.f));
-    SHIPCK(linear_wgrad2(in, r.Cin, dy2, C, C, p->DP(r.c3.w), p->F(p->dummy), V, p->F(p->wg_ws),
+    PLAN_CK(in_bwd(p, v, C, r.y3, dz, dy2, r.st[2], 1.f));
+    PLAN_HIPCK(linear_wgrad2(in, r.Cin, dy2, C, C, p->DP(r.c3.w), p->F(p->dummy), V, p->F(p->wg_ws),
                          p->st));
     if (dsrc) {
       const float* wd = p->F(r.c3.pk) + head_pack_dgrad_offset(r.Cin, C);
-      SHIPCK(linear_dgrad2(dy2, C, C, wd, *dsrc, r.Cin, V, 1, p->st));
+      PLAN_HIPCK(linear_dgrad2(dy2, C, C, wd, *dsrc, r.Cin, V, 1, p->st));
     }
   } else if (dsrc) {
-    SHIPCK(add_inplace(dsrc->p0, dz, V * C, p->st));
+    PLAN_HIPCK(add_inplace(dsrc->p0, dz, V * C, p->st));
   }
   return SPFF_OK;
 }

@@ -36,9 +36,8 @@
 //
 // Order of every accumulation is fixed (single stream, ordered partial sums): two runs give
 // the same bits.
-#include "spff_internal.h"
+#include "plan_base.h"
 #include "swin_internal.h"
-#include "spff.h"
 
 #include <algorithm>
 #include <string>
@@ -47,19 +46,6 @@
 using namespace spff;
 
 namespace {
-
-int pfail(int code, const std::string& m) { return set_error(code, m.c_str()); }
-#define PHIPCK(expr)                                                                       \
-  do {                                                                                     \
-    hipError_t _e = (expr);                                                                \
-    if (_e != hipSuccess)                                                                  \
-      return pfail(SPFF_EHIP, std::string(#expr) + " -> " + hipGetErrorString(_e));        \
-  } while (0)
-#define PCK(expr)                   \
-  do {                              \
-    int _r = (expr);                \
-    if (_r != SPFF_OK) return _r;   \
-  } while (0)
 
 constexpr int NLVL = 5, NUNIT = 10, NUP = 4, NSUB = 8, NBR = 4, NSE = 4, NAG = 3;
 constexpr int AG_NB = 256;  // blocks of the psi weight-gradient partial sums
@@ -579,11 +565,6 @@ __global__ __launch_bounds__(256) void k_ag_dhid(const float* __restrict__ att,
   }
 }
 
-struct PEnt {
-  std::string name;
-  std::vector<int64_t> shape;
-  int64_t off, numel;
-};
 struct PStat {
   size_t mean, rstd, al, de;
 };
@@ -613,12 +594,10 @@ struct PAg {
 
 }  // namespace
 
-struct spff_rupp {
+struct spff_rupp : PlanBase {
   spff_rupp_cfg cfg;
   Vol vol[NLVL];
   int f, K, ldx;
-  std::vector<PEnt> params;
-  int64_t nparam = 0;
   PUnit un[NUNIT];  // e1..e4, b_aspp_in, b_aspp_out, d4..d1
   PUp up[NUP];      // up4..up1
   PSe se[NSE];      // se1..se4
@@ -629,28 +608,6 @@ struct spff_rupp {
   size_t red_ws = 0, red_out = 0, kk1 = 0, kk2 = 0, wg_ws = 0, wt = 0, db_scr = 0;
   size_t ones = 0, zeros = 0, ag_part = 0;
   size_t G_out = 0, G_s = 0, G_1 = 0, G_2 = 0, G_dx = 0, G_ds = 0, dskip[4] = {};
-  size_t total = 0;
-  // per call
-  char* ws = nullptr;
-  const float* prm = nullptr;
-  float* dprm = nullptr;
-  hipStream_t st = nullptr;
-
-  float* F(size_t off) const { return reinterpret_cast<float*>(ws + off); }
-  const float* P(int64_t off) const { return prm + off; }
-  float* DP(int64_t off) const { return dprm + off; }
-  size_t alloc(size_t bytes) {
-    size_t o = total;
-    total += (bytes + 255) / 256 * 256;
-    return o;
-  }
-  int64_t reg(const std::string& name, std::vector<int64_t> shape) {
-    int64_t n = 1;
-    for (auto s : shape) n *= s;
-    params.push_back(PEnt{name, shape, nparam, n});
-    nparam += n;
-    return nparam - n;
-  }
 };
 
 namespace {
@@ -672,19 +629,19 @@ void reg_unit(spff_rupp* p, PUnit& u) {
 int build(spff_rupp* p) {
   const spff_rupp_cfg& c = p->cfg;
   if (c.batch < 1 || c.depth < 1 || c.height < 1 || c.width < 1)
-    return pfail(SPFF_EINVAL, "invalid batch / depth / height / width");
-  if (c.in_ch < 1 || c.in_ch > 8) return pfail(SPFF_EINVAL, "in_ch must be 1..8");
+    return plan_fail(SPFF_EINVAL, "invalid batch / depth / height / width");
+  if (c.in_ch < 1 || c.in_ch > 8) return plan_fail(SPFF_EINVAL, "in_ch must be 1..8");
   if (c.num_classes < 2 || c.num_classes > 32)
-    return pfail(SPFF_EINVAL, "num_classes must be 2..32");
-  if (c.base < 8 || c.base % 8) return pfail(SPFF_EINVAL, "base must be a multiple of 8");
+    return plan_fail(SPFF_EINVAL, "num_classes must be 2..32");
+  if (c.base < 8 || c.base % 8) return plan_fail(SPFF_EINVAL, "base must be a multiple of 8");
   if (c.math < SPFF_MATH_F32 || c.math > SPFF_MATH_F16X3)
-    return pfail(SPFF_EINVAL, "math must be one of SPFF_MATH_*");
+    return plan_fail(SPFF_EINVAL, "math must be one of SPFF_MATH_*");
   if (c.depth % 16 || c.height % 16 || c.width % 16)
-    return pfail(SPFF_ESHAPE,
+    return plan_fail(SPFF_ESHAPE,
                  "D, H and W must be multiples of 16 (four MaxPool3d(2) whose outputs are "
                  "concatenated with the ConvTranspose3d outputs); the Lit wrapper pads");
   if ((int64_t)(c.depth / 16) * (c.height / 16) * (c.width / 16) < 2)
-    return pfail(SPFF_ESHAPE,
+    return plan_fail(SPFF_ESHAPE,
                  "the bottleneck would hold one voxel per sample: InstanceNorm3d needs more "
                  "than one (the reference raises there)");
   p->f = c.base;
@@ -857,7 +814,7 @@ int build(spff_rupp* p) {
 #define EW(kernel, work, ...)                                                              \
   do {                                                                                     \
     hipLaunchKernelGGL(kernel, dim3(ew_grid(work)), dim3(256), 0, p->st, __VA_ARGS__);     \
-    PHIPCK(hipGetLastError());                                                             \
+    PLAN_HIPCK(hipGetLastError());                                                         \
   } while (0)
 
 // InstanceNorm3d statistics of y per (b, c) and the apply coefficients al = gamma rstd,
@@ -866,11 +823,11 @@ int in_fwd(spff_rupp* p, const Vol& v, int C, const float* y, const PStat& s, co
            const float* beta) {
   RedArgs a{};
   a.y = y;
-  PHIPCK(slab_reduce(RED_SUM, a, v, C, p->F(p->red_out), p->F(p->red_ws), p->st));
-  PHIPCK(in_mean(p->F(p->red_out), p->F(s.mean), v, C, p->st));
+  PLAN_HIPCK(slab_reduce(RED_SUM, a, v, C, p->F(p->red_out), p->F(p->red_ws), p->st));
+  PLAN_HIPCK(in_mean(p->F(p->red_out), p->F(s.mean), v, C, p->st));
   a.mean = p->F(s.mean);
-  PHIPCK(slab_reduce(RED_SQDEV, a, v, C, p->F(p->red_out), p->F(p->red_ws), p->st));
-  PHIPCK(in_rstd(p->F(p->red_out), gamma, beta, p->F(s.mean), p->F(s.rstd), p->F(s.al),
+  PLAN_HIPCK(slab_reduce(RED_SQDEV, a, v, C, p->F(p->red_out), p->F(p->red_ws), p->st));
+  PLAN_HIPCK(in_rstd(p->F(p->red_out), gamma, beta, p->F(s.mean), p->F(s.rstd), p->F(s.al),
                  p->F(s.de), v, C, p->st));
   return SPFF_OK;
 }
@@ -883,10 +840,10 @@ int in_bwd(spff_rupp* p, const Vol& v, int C, const float* y, const float* g, fl
   RedArgs a{};
   a.y = y; a.g = g; a.mean = p->F(s.mean); a.rstd = p->F(s.rstd);
   a.al = p->F(s.al); a.de = p->F(s.de); a.neg = neg;
-  PHIPCK(slab_reduce(RED_BWD_IN, a, v, C, p->F(p->red_out), p->F(p->red_ws), p->st));
-  PHIPCK(in_bwd_stats(p->F(p->red_out), gamma, dgamma, dbeta, p->F(p->kk1), p->F(p->kk2), v, C,
+  PLAN_HIPCK(slab_reduce(RED_BWD_IN, a, v, C, p->F(p->red_out), p->F(p->red_ws), p->st));
+  PLAN_HIPCK(in_bwd_stats(p->F(p->red_out), gamma, dgamma, dbeta, p->F(p->kk1), p->F(p->kk2), v, C,
                       p->st));
-  PHIPCK(in_bwd_apply(y, g, dy, p->F(s.mean), p->F(s.rstd), p->F(s.al), p->F(s.de), gamma,
+  PLAN_HIPCK(in_bwd_apply(y, g, dy, p->F(s.mean), p->F(s.rstd), p->F(s.al), p->F(s.de), gamma,
                       nullptr, nullptr, p->F(p->kk1), p->F(p->kk2), v, C, p->st, neg));
   return SPFF_OK;
 }
@@ -895,8 +852,8 @@ int in_bwd(spff_rupp* p, const Vol& v, int C, const float* y, const float* g, fl
 int conv(spff_rupp* p, const Src2& x, int64_t w, const Dst2& y, const Vol& v, int Cin_w,
          int Cout_w, bool dgrad) {
   const int math = p->cfg.math;
-  PHIPCK(conv3d_pack(p->P(w), p->F(p->wt), v, 3, Cin_w, Cout_w, dgrad, math, p->st));
-  PHIPCK(conv3d_run(x, p->F(p->wt), y, v, 3, Cin_w, Cout_w, dgrad, math, p->st, p->F(p->wg_ws)));
+  PLAN_HIPCK(conv3d_pack(p->P(w), p->F(p->wt), v, 3, Cin_w, Cout_w, dgrad, math, p->st));
+  PLAN_HIPCK(conv3d_run(x, p->F(p->wt), y, v, 3, Cin_w, Cout_w, dgrad, math, p->st, p->F(p->wg_ws)));
   return SPFF_OK;
 }
 
@@ -907,16 +864,16 @@ int fwd_unit(spff_rupp* p, PUnit& u, const Src2& in, int kin) {
   const float* sk = in.p0;  // identity skip: cin == C, one source with pitch C
   if (u.skip) {
     float* pk = p->F(u.pk_sk);
-    PHIPCK(head_pack(p->P(u.wsk), pk, pk + head_pack_dgrad_offset(kin, C), u.Cin, C, p->st));
-    PHIPCK(linear_fwd2(in, kin, pk, nullptr, p->F(p->G_s), C, C, M, p->st));
+    PLAN_HIPCK(head_pack(p->P(u.wsk), pk, pk + head_pack_dgrad_offset(kin, C), u.Cin, C, p->st));
+    PLAN_HIPCK(linear_fwd2(in, kin, pk, nullptr, p->F(p->G_s), C, C, M, p->st));
     sk = p->F(p->G_s);
   }
-  PCK(conv(p, in, u.w1, dst1(p->F(u.y1), C), v, u.Cin, C, false));
-  PCK(in_fwd(p, v, C, p->F(u.y1), u.s1, p->P(u.g1), p->P(u.b1)));
-  PHIPCK(act_apply(p->F(u.y1), p->F(u.a1), p->F(u.s1.al), p->F(u.s1.de), nullptr, nullptr, v, C,
+  PLAN_CK(conv(p, in, u.w1, dst1(p->F(u.y1), C), v, u.Cin, C, false));
+  PLAN_CK(in_fwd(p, v, C, p->F(u.y1), u.s1, p->P(u.g1), p->P(u.b1)));
+  PLAN_HIPCK(act_apply(p->F(u.y1), p->F(u.a1), p->F(u.s1.al), p->F(u.s1.de), nullptr, nullptr, v, C,
                    p->st, 0.f));
-  PCK(conv(p, src1(p->F(u.a1), C), u.w2, dst1(p->F(u.y2), C), v, C, C, false));
-  PCK(in_fwd(p, v, C, p->F(u.y2), u.s2, p->P(u.g2), p->P(u.b2)));
+  PLAN_CK(conv(p, src1(p->F(u.a1), C), u.w2, dst1(p->F(u.y2), C), v, C, C, false));
+  PLAN_CK(in_fwd(p, v, C, p->F(u.y2), u.s2, p->P(u.g2), p->P(u.b2)));
   EW(k_rupp_tail, M * C / 4, p->F(u.y2), p->F(u.s2.al), p->F(u.s2.de), sk, p->F(u.out),
      M * C / 4, C / 4, M / v.B);
   return SPFF_OK;
@@ -932,16 +889,16 @@ int bwd_unit(spff_rupp* p, PUnit& u, const float* dout, const Dst2* dx, const Sr
   float* g2 = p->F(p->G_2);
   float* wgs = p->F(p->wg_ws);
   EW(k_rupp_mask, M * C / 4, dout, p->F(u.out), dz, M * C / 4);
-  PCK(in_bwd(p, v, C, p->F(u.y2), dz, g1, u.s2, p->P(u.g2), p->DP(u.g2), p->DP(u.b2), 1.f));
-  PHIPCK(conv3d_wgrad(src1(p->F(u.a1), C), g1, C, p->DP(u.w2), v, 3, C, C, math, wgs, p->st));
-  PCK(conv(p, src1(g1, C), u.w2, dst1(g2, C), v, C, C, true));
-  PCK(in_bwd(p, v, C, p->F(u.y1), g2, g2, u.s1, p->P(u.g1), p->DP(u.g1), p->DP(u.b1), 0.f));
-  PHIPCK(conv3d_wgrad(in, g2, C, p->DP(u.w1), v, 3, u.Cin, C, math, wgs, p->st));
-  if (dx) PCK(conv(p, src1(g2, C), u.w1, *dx, v, u.Cin, C, true));
+  PLAN_CK(in_bwd(p, v, C, p->F(u.y2), dz, g1, u.s2, p->P(u.g2), p->DP(u.g2), p->DP(u.b2), 1.f));
+  PLAN_HIPCK(conv3d_wgrad(src1(p->F(u.a1), C), g1, C, p->DP(u.w2), v, 3, C, C, math, wgs, p->st));
+  PLAN_CK(conv(p, src1(g1, C), u.w2, dst1(g2, C), v, C, C, true));
+  PLAN_CK(in_bwd(p, v, C, p->F(u.y1), g2, g2, u.s1, p->P(u.g1), p->DP(u.g1), p->DP(u.b1), 0.f));
+  PLAN_HIPCK(conv3d_wgrad(in, g2, C, p->DP(u.w1), v, 3, u.Cin, C, math, wgs, p->st));
+  if (dx) PLAN_CK(conv(p, src1(g2, C), u.w1, *dx, v, u.Cin, C, true));
   if (u.skip) {
-    PHIPCK(linear_wgrad2(in, u.Cin, dz, C, C, p->DP(u.wsk), p->F(p->db_scr), M, wgs, p->st));
+    PLAN_HIPCK(linear_wgrad2(in, u.Cin, dz, C, C, p->DP(u.wsk), p->F(p->db_scr), M, wgs, p->st));
     if (dx)
-      PHIPCK(linear_dgrad2(dz, C, C, p->F(u.pk_sk) + head_pack_dgrad_offset(kin, C), *dx, u.Cin,
+      PLAN_HIPCK(linear_dgrad2(dz, C, C, p->F(u.pk_sk) + head_pack_dgrad_offset(kin, C), *dx, u.Cin,
                            M, 1, p->st));
   } else if (dx) {
     EW(k_rupp_acc, M * C / 4, dx->p0, dz, M * C / 4);
@@ -954,12 +911,12 @@ int se_fwd(spff_rupp* p, PSe& s, const float* x) {
   const int64_t M = nvox(v);
   RedArgs a{};
   a.y = x;
-  PHIPCK(slab_reduce(RED_SUM, a, v, s.C, p->F(p->red_out), p->F(p->red_ws), p->st));
-  PHIPCK(in_mean(p->F(p->red_out), p->F(s.mean), v, s.C, p->st));
+  PLAN_HIPCK(slab_reduce(RED_SUM, a, v, s.C, p->F(p->red_out), p->F(p->red_ws), p->st));
+  PLAN_HIPCK(in_mean(p->F(p->red_out), p->F(s.mean), v, s.C, p->st));
   hipLaunchKernelGGL(k_se_gate, dim3(v.B), dim3(256), s.Hd * sizeof(float), p->st, p->F(s.mean),
                      p->P(s.w1), p->P(s.b1), p->P(s.w2), p->P(s.b2), p->F(s.hid), p->F(s.gate),
                      s.C, s.Hd);
-  PHIPCK(hipGetLastError());
+  PLAN_HIPCK(hipGetLastError());
   EW(k_se_scale, M * s.C / 4, x, p->F(s.gate), p->F(s.out), M * s.C / 4, s.C / 4, M / v.B);
   return SPFF_OK;
 }
@@ -970,12 +927,12 @@ int se_bwd(spff_rupp* p, PSe& s, const float* x, float* g) {
   const int64_t M = nvox(v);
   RedArgs a{};
   a.y = x; a.g = g; a.al = p->F(p->ones); a.de = p->F(p->zeros); a.neg = 1.f;
-  PHIPCK(slab_reduce(RED_BWD_TAIL, a, v, s.C, p->F(p->red_out), p->F(p->red_ws), p->st));
+  PLAN_HIPCK(slab_reduce(RED_BWD_TAIL, a, v, s.C, p->F(p->red_out), p->F(p->red_ws), p->st));
   hipLaunchKernelGGL(k_se_bwd, dim3(1), dim3(256), (s.C + s.Hd) * sizeof(float), p->st,
                      p->F(p->red_out), p->F(s.mean), p->F(s.hid), p->F(s.gate), p->P(s.w1),
                      p->P(s.w2), p->DP(s.w1), p->DP(s.b1), p->DP(s.w2), p->DP(s.b2),
                      p->F(s.dmean), v.B, s.C, s.Hd, v.D, 1.f / (float)(M / v.B));
-  PHIPCK(hipGetLastError());
+  PLAN_HIPCK(hipGetLastError());
   EW(k_se_bwd_apply, M * s.C / 4, g, p->F(s.gate), p->F(s.dmean), M * s.C / 4, s.C / 4, M / v.B);
   return SPFF_OK;
 }
@@ -986,8 +943,8 @@ int ag_fwd(spff_rupp* p, PAg& a, const float* u, const float* g) {
   EW(k_ag_cat, (int64_t)I * 2 * C, p->P(a.wx), p->P(a.wg), p->P(a.bx), p->P(a.bg), p->F(a.wcat),
      p->F(a.bcat), I, C);
   float* pk = p->F(a.pk);
-  PHIPCK(head_pack(p->F(a.wcat), pk, pk + head_pack_dgrad_offset(2 * C, I), 2 * C, I, p->st));
-  PHIPCK(linear_fwd2(Src2{u, g, C, C, C}, 2 * C, pk, p->F(a.bcat), p->F(a.att), I, I, M, p->st));
+  PLAN_HIPCK(head_pack(p->F(a.wcat), pk, pk + head_pack_dgrad_offset(2 * C, I), 2 * C, I, p->st));
+  PLAN_HIPCK(linear_fwd2(Src2{u, g, C, C, C}, 2 * C, pk, p->F(a.bcat), p->F(a.att), I, I, M, p->st));
   EW(k_ag_fwd, M, p->F(a.att), p->P(a.wpsi), p->P(a.bpsi), u, p->F(a.psi), p->F(a.s), M, I, C);
   return SPFF_OK;
 }
@@ -1004,17 +961,17 @@ int ag_bwd(spff_rupp* p, PAg& a, const float* u, const float* g, const float* ds
   const int nb = (int)std::min<int64_t>(AG_NB, (M + 255) / 256);
   hipLaunchKernelGGL(k_ag_wpsi_part, dim3(nb), dim3(256), 0, p->st, p->F(a.att), dpp,
                      p->F(p->ag_part), M, I);
-  PHIPCK(hipGetLastError());
+  PLAN_HIPCK(hipGetLastError());
   hipLaunchKernelGGL(k_ag_wpsi_fin, dim3(1), dim3(256), 0, p->st, p->F(p->ag_part), nb,
                      p->DP(a.wpsi), p->DP(a.bpsi), I);
-  PHIPCK(hipGetLastError());
+  PLAN_HIPCK(hipGetLastError());
   EW(k_ag_dhid, M * I / 4, p->F(a.att), dhid, dpp, p->P(a.wpsi), M * I / 4, I / 4);
   const Src2 in{u, g, C, C, C};
-  PHIPCK(linear_wgrad2(in, 2 * C, dhid, I, I, p->F(a.dwcat), p->F(a.dbcat), M, wgs, p->st));
+  PLAN_HIPCK(linear_wgrad2(in, 2 * C, dhid, I, I, p->F(a.dwcat), p->F(a.dbcat), M, wgs, p->st));
   EW(k_ag_split, (int64_t)I * 2 * C, p->F(a.dwcat), p->F(a.dbcat), p->DP(a.wx), p->DP(a.wg),
      p->DP(a.bx), p->DP(a.bg), I, C);
-  PHIPCK(spff::zero_async(dg, M * C * sizeof(float), p->st));
-  PHIPCK(linear_dgrad2(dhid, I, I, p->F(a.pk) + head_pack_dgrad_offset(2 * C, I),
+  PLAN_HIPCK(spff::zero_async(dg, M * C * sizeof(float), p->st));
+  PLAN_HIPCK(linear_dgrad2(dhid, I, I, p->F(a.pk) + head_pack_dgrad_offset(2 * C, I),
                        Dst2{du, dg, C, C, C}, 2 * C, M, 1, p->st));
   return SPFF_OK;
 }
@@ -1025,56 +982,56 @@ int forward(spff_rupp* p, const float* x, float* logits) {
   const Vol& v0 = p->vol[0];
   const Vol& v4 = p->vol[4];
   const int64_t M4 = nvox(v4);
-  PHIPCK(ncdhw_to_ndhwc(x, p->F(p->x_cl), v0, c.in_ch, p->ldx, p->st));
-  PHIPCK(fill32_async(p->F(p->ones), (size_t)c.batch * C4 * sizeof(float), 0x3f800000u, p->st));
-  PHIPCK(spff::zero_async(p->F(p->zeros), (size_t)c.batch * C4 * sizeof(float), p->st));
+  PLAN_HIPCK(ncdhw_to_ndhwc(x, p->F(p->x_cl), v0, c.in_ch, p->ldx, p->st));
+  PLAN_HIPCK(fill32_async(p->F(p->ones), (size_t)c.batch * C4 * sizeof(float), 0x3f800000u, p->st));
+  PLAN_HIPCK(spff::zero_async(p->F(p->zeros), (size_t)c.batch * C4 * sizeof(float), p->st));
   PUnit* U = p->un;
   Src2 in = src1(p->F(p->x_cl), p->ldx);
   int kin = p->ldx;
   for (int l = 0; l < 4; ++l) {
-    PCK(fwd_unit(p, U[l], in, kin));
-    PHIPCK(maxpool3_fwd(p->F(U[l].out), p->F(p->pool[l]),
+    PLAN_CK(fwd_unit(p, U[l], in, kin));
+    PLAN_HIPCK(maxpool3_fwd(p->F(U[l].out), p->F(p->pool[l]),
                         reinterpret_cast<uint8_t*>(p->ws + p->pidx[l]), p->vol[l], f << l, p->st));
-    PCK(se_fwd(p, p->se[l], p->F(U[l].out)));
+    PLAN_CK(se_fwd(p, p->se[l], p->F(U[l].out)));
     in = src1(p->F(p->pool[l]), f << l);
     kin = f << l;
   }
-  PCK(fwd_unit(p, U[4], in, kin));
+  PLAN_CK(fwd_unit(p, U[4], in, kin));
   for (int r = 0; r < NBR; ++r) {
-    PHIPCK(dil_pack(p->P(p->w_br[r]), p->F(p->br_pk[r]), C4, C4, p->st));
-    PHIPCK(dil_run(p->F(U[4].out), C4, p->F(p->br_pk[r]), p->F(p->cat) + r * C4, NBR * C4, v4, C4,
+    PLAN_HIPCK(dil_pack(p->P(p->w_br[r]), p->F(p->br_pk[r]), C4, C4, p->st));
+    PLAN_HIPCK(dil_run(p->F(U[4].out), C4, p->F(p->br_pk[r]), p->F(p->cat) + r * C4, NBR * C4, v4, C4,
                    C4, DIL[r], false, 0, p->st));
   }
   {
     float* pk = p->F(p->proj_pk);
-    PHIPCK(head_pack(p->P(p->w_proj), pk, pk + head_pack_dgrad_offset(NBR * C4, C4), NBR * C4, C4,
+    PLAN_HIPCK(head_pack(p->P(p->w_proj), pk, pk + head_pack_dgrad_offset(NBR * C4, C4), NBR * C4, C4,
                      p->st));
-    PHIPCK(linear_fwd(p->F(p->cat), NBR * C4, NBR * C4, pk, nullptr, p->F(p->aspp_out), C4, C4,
+    PLAN_HIPCK(linear_fwd(p->F(p->cat), NBR * C4, NBR * C4, pk, nullptr, p->F(p->aspp_out), C4, C4,
                       M4, nullptr, 0, p->st));
     EW(k_rupp_relu, M4 * C4 / 4, p->F(p->aspp_out), M4 * C4 / 4);
   }
-  PCK(fwd_unit(p, U[5], src1(p->F(p->aspp_out), C4), C4));
+  PLAN_CK(fwd_unit(p, U[5], src1(p->F(p->aspp_out), C4), C4));
   const float* prev = p->F(U[5].out);
   for (int u = 0; u < NUP; ++u) {
     PUp& Up = p->up[u];
     const int lvl = 3 - u, C = Up.Cout;
     float* pk = p->F(Up.pk);
-    PHIPCK(upconv_pack(p->P(Up.w), pk, pk + upconv_pack_dgrad_offset(Up.Cin, Up.Cout, NSUB),
+    PLAN_HIPCK(upconv_pack(p->P(Up.w), pk, pk + upconv_pack_dgrad_offset(Up.Cin, Up.Cout, NSUB),
                        Up.Cin, Up.Cout, p->st, NSUB));
-    PHIPCK(upconv_fwd(prev, pk, p->P(Up.b), p->F(Up.out), p->vol[Up.lvl_low], Up.Cin, Up.Cout,
+    PLAN_HIPCK(upconv_fwd(prev, pk, p->P(Up.b), p->F(Up.out), p->vol[Up.lvl_low], Up.Cin, Up.Cout,
                       p->st, NSUB, p->cfg.math));
     const float* second = p->F(p->se[lvl].out);
     if (u < NAG) {
-      PCK(ag_fwd(p, p->ag[u], p->F(Up.out), p->F(p->se[lvl].out)));
+      PLAN_CK(ag_fwd(p, p->ag[u], p->F(Up.out), p->F(p->se[lvl].out)));
       second = p->F(p->ag[u].s);
     }
     PUnit& d = U[6 + u];
-    PCK(fwd_unit(p, d, Src2{p->F(Up.out), second, C, C, C}, 2 * C));
+    PLAN_CK(fwd_unit(p, d, Src2{p->F(Up.out), second, C, C, C}, 2 * C));
     prev = p->F(d.out);
   }
   float* hp = p->F(p->head_pk);
-  PHIPCK(head_pack(p->P(p->head_w), hp, hp + head_pack_dgrad_offset(f, p->K), f, p->K, p->st));
-  PHIPCK(head_fwd(prev, hp, p->P(p->head_b), logits, nvox(v0), f, p->K, p->st, p->cfg.math));
+  PLAN_HIPCK(head_pack(p->P(p->head_w), hp, hp + head_pack_dgrad_offset(f, p->K), f, p->K, p->st));
+  PLAN_HIPCK(head_fwd(prev, hp, p->P(p->head_b), logits, nvox(v0), f, p->K, p->st, p->cfg.math));
   return SPFF_OK;
 }
 
@@ -1086,9 +1043,9 @@ int backward(spff_rupp* p, const float* dl) {
   PUnit* U = p->un;
   float* wgs = p->F(p->wg_ws);
   float* hp = p->F(p->head_pk);
-  PHIPCK(head_wgrad(p->F(U[9].out), dl, p->DP(p->head_w), p->DP(p->head_b), V0, f, p->K, wgs,
+  PLAN_HIPCK(head_wgrad(p->F(U[9].out), dl, p->DP(p->head_w), p->DP(p->head_b), V0, f, p->K, wgs,
                     p->st));
-  PHIPCK(head_dgrad(dl, hp + head_pack_dgrad_offset(f, p->K), p->F(p->G_out), V0, f, p->K, p->st,
+  PLAN_HIPCK(head_dgrad(dl, hp + head_pack_dgrad_offset(f, p->K), p->F(p->G_out), V0, f, p->K, p->st,
                     p->cfg.math));
   for (int lvl = 0; lvl < 4; ++lvl) {  // d1 <- up1 <- d2 ... <- up4
     const int u = 3 - lvl;
@@ -1100,59 +1057,59 @@ int backward(spff_rupp* p, const float* dl) {
     // [u | s]: the gradient of u into G_dx; of s into G_ds (gated) or straight into the
     // SE output's gradient
     Dst2 dx{p->F(p->G_dx), gated ? p->F(p->G_ds) : p->F(p->dskip[lvl]), C, C, C};
-    PCK(bwd_unit(p, d, p->F(p->G_out), &dx, Src2{p->F(Up.out), second, C, C, C}, 2 * C));
+    PLAN_CK(bwd_unit(p, d, p->F(p->G_out), &dx, Src2{p->F(Up.out), second, C, C, C}, 2 * C));
     if (gated)
-      PCK(ag_bwd(p, p->ag[u], p->F(Up.out), p->F(p->se[lvl].out), p->F(p->G_ds), p->F(p->G_dx),
+      PLAN_CK(ag_bwd(p, p->ag[u], p->F(Up.out), p->F(p->se[lvl].out), p->F(p->G_ds), p->F(p->G_dx),
                  p->F(p->dskip[lvl])));
-    PCK(se_bwd(p, p->se[lvl], p->F(U[lvl].out), p->F(p->dskip[lvl])));
+    PLAN_CK(se_bwd(p, p->se[lvl], p->F(U[lvl].out), p->F(p->dskip[lvl])));
     const Vol& low = p->vol[Up.lvl_low];
     const float* below = u == 0 ? p->F(U[5].out) : p->F(U[6 + u - 1].out);
-    PHIPCK(upconv_wgrad(below, p->F(p->G_dx), C, p->DP(Up.w), p->DP(Up.b), low, Up.Cin, Up.Cout,
+    PLAN_HIPCK(upconv_wgrad(below, p->F(p->G_dx), C, p->DP(Up.w), p->DP(Up.b), low, Up.Cin, Up.Cout,
                         wgs, p->st, NSUB, p->cfg.math));
     float* pk = p->F(Up.pk);
-    PHIPCK(upconv_dgrad(p->F(p->G_dx), C, pk + upconv_pack_dgrad_offset(Up.Cin, Up.Cout, NSUB),
+    PLAN_HIPCK(upconv_dgrad(p->F(p->G_dx), C, pk + upconv_pack_dgrad_offset(Up.Cin, Up.Cout, NSUB),
                         p->F(p->G_out), low, Up.Cin, Up.Cout, p->st, NSUB, p->cfg.math));
   }
   {  // bottleneck
     Dst2 dx = dst1(p->F(p->G_dx), C4);
-    PCK(bwd_unit(p, U[5], p->F(p->G_out), &dx, src1(p->F(p->aspp_out), C4), C4));
+    PLAN_CK(bwd_unit(p, U[5], p->F(p->G_out), &dx, src1(p->F(p->aspp_out), C4), C4));
     float* dz = p->F(p->G_s);
     EW(k_rupp_mask, M4 * C4 / 4, p->F(p->G_dx), p->F(p->aspp_out), dz, M4 * C4 / 4);
-    PHIPCK(linear_wgrad(p->F(p->cat), NBR * C4, NBR * C4, dz, C4, C4, p->DP(p->w_proj),
+    PLAN_HIPCK(linear_wgrad(p->F(p->cat), NBR * C4, NBR * C4, dz, C4, C4, p->DP(p->w_proj),
                         p->F(p->db_scr), M4, wgs, p->st));
-    PHIPCK(linear_dgrad(dz, C4, C4, p->F(p->proj_pk) + head_pack_dgrad_offset(NBR * C4, C4),
+    PLAN_HIPCK(linear_dgrad(dz, C4, C4, p->F(p->proj_pk) + head_pack_dgrad_offset(NBR * C4, C4),
                         p->F(p->dcat), NBR * C4, NBR * C4, M4, nullptr, p->st));
     for (int r = 0; r < NBR; ++r) {  // input gradients summed in branch order 0..3
       const float* dy = p->F(p->dcat) + r * C4;
-      PHIPCK(dil_wgrad(p->F(U[4].out), C4, dy, NBR * C4, p->DP(p->w_br[r]), v4, C4, C4, DIL[r],
+      PLAN_HIPCK(dil_wgrad(p->F(U[4].out), C4, dy, NBR * C4, p->DP(p->w_br[r]), v4, C4, C4, DIL[r],
                        p->st));
-      PHIPCK(dil_run(dy, NBR * C4, p->F(p->br_pk[r]), p->F(p->G_out), C4, v4, C4, C4, DIL[r], true,
+      PLAN_HIPCK(dil_run(dy, NBR * C4, p->F(p->br_pk[r]), p->F(p->G_out), C4, v4, C4, C4, DIL[r], true,
                      r > 0, p->st));
     }
     Dst2 dxi = dst1(p->F(p->G_dx), 8 * f);
-    PCK(bwd_unit(p, U[4], p->F(p->G_out), &dxi, src1(p->F(p->pool[3]), 8 * f), 8 * f));
+    PLAN_CK(bwd_unit(p, U[4], p->F(p->G_out), &dxi, src1(p->F(p->pool[3]), 8 * f), 8 * f));
   }
   for (int l = 3; l >= 0; --l) {
     const int C = f << l;
-    PHIPCK(maxpool3_bwd_add(p->F(p->G_dx), reinterpret_cast<const uint8_t*>(p->ws + p->pidx[l]),
+    PLAN_HIPCK(maxpool3_bwd_add(p->F(p->G_dx), reinterpret_cast<const uint8_t*>(p->ws + p->pidx[l]),
                             p->F(p->dskip[l]), C, p->F(p->dskip[l]), p->vol[l], C, p->st));
     if (l > 0) {
       Dst2 dx = dst1(p->F(p->G_dx), C / 2);
-      PCK(bwd_unit(p, U[l], p->F(p->dskip[l]), &dx, src1(p->F(p->pool[l - 1]), C / 2), C / 2));
+      PLAN_CK(bwd_unit(p, U[l], p->F(p->dskip[l]), &dx, src1(p->F(p->pool[l - 1]), C / 2), C / 2));
     } else {
-      PCK(bwd_unit(p, U[0], p->F(p->dskip[0]), nullptr, src1(p->F(p->x_cl), p->ldx), p->ldx));
+      PLAN_CK(bwd_unit(p, U[0], p->F(p->dskip[0]), nullptr, src1(p->F(p->x_cl), p->ldx), p->ldx));
     }
   }
   return SPFF_OK;
 }
 
 int dil_args(int ldx, int ldy, int B, int D, int H, int W, int cin, int cout, int r) {
-  if (B < 1 || D < 1 || H < 1 || W < 1) return pfail(SPFF_EINVAL, "invalid B / D / H / W");
+  if (B < 1 || D < 1 || H < 1 || W < 1) return plan_fail(SPFF_EINVAL, "invalid B / D / H / W");
   if (cin < 4 || cout < 4 || cin % 4 || cout % 4)
-    return pfail(SPFF_EINVAL, "cin and cout must be multiples of 4");
+    return plan_fail(SPFF_EINVAL, "cin and cout must be multiples of 4");
   if (ldx % 4 || ldx < cin || ldy % 4 || ldy < cout)
-    return pfail(SPFF_EINVAL, "ldx / ldy must be multiples of 4 covering cin / cout");
-  if (r != 1 && r != 2 && r != 4 && r != 8) return pfail(SPFF_EINVAL, "dilation must be 1, 2, 4 or 8");
+    return plan_fail(SPFF_EINVAL, "ldx / ldy must be multiples of 4 covering cin / cout");
+  if (r != 1 && r != 2 && r != 4 && r != 8) return plan_fail(SPFF_EINVAL, "dilation must be 1, 2, 4 or 8");
   return SPFF_OK;
 }
 
@@ -1162,16 +1119,7 @@ int dil_args(int ldx, int ldy, int B, int D, int H, int W, int cin, int cout, in
 extern "C" {
 
 int spff_rupp_create(const spff_rupp_cfg* cfg, spff_rupp** out) {
-  if (!cfg || !out) return pfail(SPFF_EINVAL, "null argument");
-  spff_rupp* p = new spff_rupp();
-  p->cfg = *cfg;
-  const int r = build(p);
-  if (r != SPFF_OK) {
-    delete p;
-    return r;
-  }
-  *out = p;
-  return SPFF_OK;
+  return plan_create(cfg, out, build);
 }
 
 void spff_rupp_destroy(spff_rupp* p) { delete p; }
@@ -1180,15 +1128,8 @@ int spff_rupp_num_params(const spff_rupp* p) { return p ? (int)p->params.size() 
 
 int spff_rupp_param_info(const spff_rupp* p, int i, const char** name, int* ndim, int64_t shape[5],
                          int64_t* offset, int64_t* numel) {
-  if (!p || i < 0 || i >= (int)p->params.size()) return pfail(SPFF_EINVAL, "param index");
-  const PEnt& e = p->params[i];
-  if (name) *name = e.name.c_str();
-  if (ndim) *ndim = (int)e.shape.size();
-  if (shape)
-    for (int k = 0; k < 5; ++k) shape[k] = k < (int)e.shape.size() ? e.shape[k] : 1;
-  if (offset) *offset = e.off;
-  if (numel) *numel = e.numel;
-  return SPFF_OK;
+  if (!p) return plan_fail(SPFF_EINVAL, "param index");
+  return plan_param_info(p->params, i, name, ndim, shape, offset, numel);
 }
 
 int64_t spff_rupp_param_floats(const spff_rupp* p) { return p ? p->nparam : 0; }
@@ -1196,35 +1137,23 @@ size_t spff_rupp_workspace_bytes(const spff_rupp* p) { return p ? p->total : 0; 
 
 int spff_rupp_forward(spff_rupp* p, const float* x, const float* params, float* logits, void* ws,
                       void* stream) {
-  if (!p || !x || !params || !logits || !ws) return pfail(SPFF_EINVAL, "null argument");
-  p->ws = static_cast<char*>(ws);
-  p->prm = params;
-  p->dprm = nullptr;
-  p->st = static_cast<hipStream_t>(stream);
+  if (!p || !x || !params || !logits || !ws) return plan_fail(SPFF_EINVAL, "null argument");
+  p->bind(ws, params, nullptr, stream);
   return forward(p, x, logits);
 }
 
 int spff_rupp_backward(spff_rupp* p, const float* dlogits, const float* params, float* dparams,
                        void* ws, void* stream) {
-  if (!p || !dlogits || !params || !dparams || !ws) return pfail(SPFF_EINVAL, "null argument");
-  p->ws = static_cast<char*>(ws);
-  p->prm = params;
-  p->dprm = dparams;
-  p->st = static_cast<hipStream_t>(stream);
+  if (!p || !dlogits || !params || !dparams || !ws) return plan_fail(SPFF_EINVAL, "null argument");
+  p->bind(ws, params, dparams, stream);
   return backward(p, dlogits);
 }
 
 int spff_rupp_saved_tensor(const spff_rupp* p, void* ws, const char* name, const float** ptr,
                            int64_t* nv, int* ch) {
-  if (!p || !ws || !name || !ptr) return pfail(SPFF_EINVAL, "null argument");
-  const char* base = static_cast<const char*>(ws);
+  if (!p || !ws || !name || !ptr) return plan_fail(SPFF_EINVAL, "null argument");
   const std::string n(name);
-  auto ret = [&](size_t off, const Vol& v, int c) {
-    *ptr = reinterpret_cast<const float*>(base + off);
-    if (nv) *nv = nvox(v);
-    if (ch) *ch = c;
-    return SPFF_OK;
-  };
+  const SavedOut ret{ws, ptr, nv, ch};
   for (int i = 0; i < NUNIT; ++i) {
     const PUnit& u = p->un[i];
     const Vol& v = p->vol[u.lvl];
@@ -1235,7 +1164,7 @@ int spff_rupp_saved_tensor(const spff_rupp* p, void* ws, const char* name, const
   for (int i = 0; i < NAG; ++i)
     if (n == "ag" + std::to_string(4 - i) + ".att")
       return ret(p->ag[i].att, p->vol[p->ag[i].lvl], p->ag[i].I);
-  return pfail(SPFF_EINVAL, "unknown saved tensor " + n);
+  return plan_fail(SPFF_EINVAL, "unknown saved tensor " + n);
 }
 
 size_t spff_rupp_loss_ws_bytes(int batch, int num_classes) {
@@ -1246,10 +1175,10 @@ int spff_rupp_loss(const float* logits, const int64_t* labels, int batch, int64_
                    int num_classes, int use_ignore, int ignore_index, int include_bg,
                    double ce_weight, double dice_weight, float* out4, float* dlogits, void* ws,
                    void* stream) {
-  if (!logits || !labels || !out4 || !dlogits || !ws) return pfail(SPFF_EINVAL, "null argument");
-  if (batch < 1 || vox_per_sample < 1) return pfail(SPFF_EINVAL, "invalid batch / vox_per_sample");
-  if (num_classes < 2 || num_classes > 32) return pfail(SPFF_EINVAL, "num_classes must be 2..32");
-  PHIPCK(rupp_loss(logits, labels, batch, vox_per_sample, num_classes, use_ignore, ignore_index,
+  if (!logits || !labels || !out4 || !dlogits || !ws) return plan_fail(SPFF_EINVAL, "null argument");
+  if (batch < 1 || vox_per_sample < 1) return plan_fail(SPFF_EINVAL, "invalid batch / vox_per_sample");
+  if (num_classes < 2 || num_classes > 32) return plan_fail(SPFF_EINVAL, "num_classes must be 2..32");
+  PLAN_HIPCK(rupp_loss(logits, labels, batch, vox_per_sample, num_classes, use_ignore, ignore_index,
                    include_bg, ce_weight, dice_weight, out4, dlogits, ws,
                    static_cast<hipStream_t>(stream)));
   return SPFF_OK;
@@ -1261,24 +1190,24 @@ size_t spff_conv3d_dil_ws_bytes(int cin, int cout) {
 
 int spff_conv3d_dil_fwd(const float* x, int ldx, const float* w, float* y, int ldy, int B, int D,
                         int H, int W, int cin, int cout, int dilation, void* ws, void* stream) {
-  if (!x || !w || !y || !ws) return pfail(SPFF_EINVAL, "null argument");
-  PCK(dil_args(ldx, ldy, B, D, H, W, cin, cout, dilation));
+  if (!x || !w || !y || !ws) return plan_fail(SPFF_EINVAL, "null argument");
+  PLAN_CK(dil_args(ldx, ldy, B, D, H, W, cin, cout, dilation));
   hipStream_t s = static_cast<hipStream_t>(stream);
   float* P = static_cast<float*>(ws);
-  PHIPCK(dil_pack(w, P, cin, cout, s));
-  PHIPCK(dil_run(x, ldx, P, y, ldy, Vol{B, D, H, W}, cin, cout, dilation, false, 0, s));
+  PLAN_HIPCK(dil_pack(w, P, cin, cout, s));
+  PLAN_HIPCK(dil_run(x, ldx, P, y, ldy, Vol{B, D, H, W}, cin, cout, dilation, false, 0, s));
   return SPFF_OK;
 }
 
 int spff_conv3d_dil_dgrad(const float* dy, int ldy, const float* w, float* dx, int ldx, int B,
                           int D, int H, int W, int cin, int cout, int dilation, int accumulate,
                           void* ws, void* stream) {
-  if (!dy || !w || !dx || !ws) return pfail(SPFF_EINVAL, "null argument");
-  PCK(dil_args(ldx, ldy, B, D, H, W, cin, cout, dilation));
+  if (!dy || !w || !dx || !ws) return plan_fail(SPFF_EINVAL, "null argument");
+  PLAN_CK(dil_args(ldx, ldy, B, D, H, W, cin, cout, dilation));
   hipStream_t s = static_cast<hipStream_t>(stream);
   float* P = static_cast<float*>(ws);
-  PHIPCK(dil_pack(w, P, cin, cout, s));
-  PHIPCK(dil_run(dy, ldy, P, dx, ldx, Vol{B, D, H, W}, cin, cout, dilation, true,
+  PLAN_HIPCK(dil_pack(w, P, cin, cout, s));
+  PLAN_HIPCK(dil_run(dy, ldy, P, dx, ldx, Vol{B, D, H, W}, cin, cout, dilation, true,
                  accumulate ? 1 : 0, s));
   return SPFF_OK;
 }
@@ -1286,10 +1215,10 @@ int spff_conv3d_dil_dgrad(const float* dy, int ldy, const float* w, float* dx, i
 int spff_conv3d_dil_wgrad(const float* x, int ldx, const float* dy, int ldy, float* dw, int B,
                           int D, int H, int W, int cin, int cout, int dilation, void* ws,
                           void* stream) {
-  if (!x || !dy || !dw) return pfail(SPFF_EINVAL, "null argument");
+  if (!x || !dy || !dw) return plan_fail(SPFF_EINVAL, "null argument");
   (void)ws;
-  PCK(dil_args(ldx, ldy, B, D, H, W, cin, cout, dilation));
-  PHIPCK(dil_wgrad(x, ldx, dy, ldy, dw, Vol{B, D, H, W}, cin, cout, dilation,
+  PLAN_CK(dil_args(ldx, ldy, B, D, H, W, cin, cout, dilation));
+  PLAN_HIPCK(dil_wgrad(x, ldx, dy, ldy, dw, Vol{B, D, H, W}, cin, cout, dilation,
                    static_cast<hipStream_t>(stream)));
   return SPFF_OK;
 }

@@ -41,13 +41,11 @@ struct Stage {
 
 }  // namespace
 
-struct spff_swin {
+struct spff_swin : PlanBase {
   spff_swin_cfg cfg;
   Vol vol[NL];
   int f, K, ldx;
-  std::vector<SEnt> params;
   static constexpr int kNRB = NRB;
-  int64_t nparam = 0;
   int64_t pe_w = -1, pe_b = -1;
   size_t pe_pk = 0;
   Stage stg[NST];
@@ -63,29 +61,7 @@ struct spff_swin {
   size_t G_out = 0, G_dz = 0, G_dy2 = 0, G_da1 = 0, G_up = 0;
   size_t d_enc[4] = {}, d_hs[5] = {}, dT[5] = {};
   size_t S_a = 0, S_b = 0, S_c = 0, S_qkv = 0, S_h = 0;
-  size_t total = 0;
   int maxC = 0;
-  // per call
-  char* ws = nullptr;
-  const float* prm = nullptr;
-  float* dprm = nullptr;
-  hipStream_t st = nullptr;
-
-  float* F(size_t off) const { return reinterpret_cast<float*>(ws + off); }
-  const float* P(int64_t off) const { return off < 0 ? nullptr : prm + off; }
-  float* DP(int64_t off) const { return off < 0 ? nullptr : dprm + off; }
-  size_t alloc(size_t bytes) {
-    size_t o = total;
-    total += (bytes + 255) / 256 * 256;
-    return o;
-  }
-  int64_t reg(const std::string& name, std::vector<int64_t> shape) {
-    int64_t n = 1;
-    for (auto s : shape) n *= s;
-    params.push_back(SEnt{name, shape, nparam, n});
-    nparam += n;
-    return nparam - n;
-  }
 };
 
 namespace {
@@ -93,19 +69,19 @@ namespace {
 int build(spff_swin* p) {
   const spff_swin_cfg& c = p->cfg;
   if (c.batch < 1 || c.in_ch < 1 || c.in_ch > 8 || c.num_classes < 1 || c.num_classes > 32)
-    return sfail(SPFF_EINVAL, "invalid batch / in_ch (1..8) / num_classes (1..32)");
+    return plan_fail(SPFF_EINVAL, "invalid batch / in_ch (1..8) / num_classes (1..32)");
   if (c.depth % 32 || c.height % 32 || c.width % 32 || c.depth < 32 || c.height < 32 ||
       c.width < 32)
-    return sfail(SPFF_ESHAPE, "SwinUNETR needs D, H, W divisible by 2**5 = 32 (MONAI "
+    return plan_fail(SPFF_ESHAPE, "SwinUNETR needs D, H, W divisible by 2**5 = 32 (MONAI "
                               "_check_input_size; LitSwinUNETR pads to a multiple of 32)");
   if ((c.depth / 32) * (c.height / 32) * (c.width / 32) < 2)
-    return sfail(SPFF_ESHAPE, "the 1/32-resolution bottleneck must hold more than one voxel "
+    return plan_fail(SPFF_ESHAPE, "the 1/32-resolution bottleneck must hold more than one voxel "
                               "(InstanceNorm3d: 'Expected more than 1 spatial element')");
   if (c.feature_size < 4 || c.feature_size % 4)
-    return sfail(SPFF_EINVAL, "feature_size must be a positive multiple of 4");
-  if (c.window < 1 || c.window > 7) return sfail(SPFF_EINVAL, "window must be 1..7");
+    return plan_fail(SPFF_EINVAL, "feature_size must be a positive multiple of 4");
+  if (c.window < 1 || c.window > 7) return plan_fail(SPFF_EINVAL, "window must be 1..7");
   if (c.math < SPFF_MATH_F32 || c.math > SPFF_MATH_F16X3)
-    return sfail(SPFF_EINVAL, "math must be one of SPFF_MATH_*");
+    return plan_fail(SPFF_EINVAL, "math must be one of SPFF_MATH_*");
   p->f = c.feature_size;
   p->K = c.num_classes;
   p->ldx = rup(c.in_ch, 8);
@@ -121,12 +97,12 @@ int build(spff_swin* p) {
     S.L = s + 1;
     S.C = f << s;
     S.nh = c.heads[s];
-    if (S.nh < 1 || S.C % S.nh) return sfail(SPFF_EINVAL, "heads must divide the stage width");
+    if (S.nh < 1 || S.C % S.nh) return plan_fail(SPFF_EINVAL, "heads must divide the stage width");
     const int hd = S.C / S.nh;
     if (hd != 4 && hd != 8 && hd != 12 && hd != 16 && hd != 24 && hd != 32)
-      return sfail(SPFF_EINVAL, "head_dim must be one of 4, 8, 12, 16, 24, 32");
+      return plan_fail(SPFF_EINVAL, "head_dim must be one of 4, 8, 12, 16, 24, 32");
     S.hid = (int)(S.C * (double)c.mlp_ratio);
-    if (S.hid < 4 || S.hid % 4) return sfail(SPFF_EINVAL, "mlp hidden width must be a multiple of 4");
+    if (S.hid < 4 || S.hid % 4) return plan_fail(SPFF_EINVAL, "mlp hidden width must be a multiple of 4");
     const std::string b = "swinViT.layers" + std::to_string(s + 1) + ".0.blocks.0.";
     S.n1w = p->reg(b + "norm1.weight", {S.C});
     S.n1b = p->reg(b + "norm1.bias", {S.C});
@@ -293,27 +269,27 @@ int stage_fwd(spff_swin* p, Stage& S, const float* tin, float* tout) {
     float* pk = p->F(l.pk);
     return head_pack(p->P(l.w), pk, pk + head_pack_dgrad_offset(l.K, l.N), l.K, l.N, st);
   };
-  SHIPCK(ln_fwd(tin, C, C, p->P(S.n1w), p->P(S.n1b), p->F(S.n1), C, p->F(S.mu1), p->F(S.rs1), T,
+  PLAN_HIPCK(ln_fwd(tin, C, C, p->P(S.n1w), p->P(S.n1b), p->F(S.n1), C, p->F(S.mu1), p->F(S.rs1), T,
                 st));
-  SHIPCK(pack(S.qkv));
-  SHIPCK(linear_fwd(p->F(S.n1), C, C, p->F(S.qkv.pk), p->P(S.qkv.b), p->F(S.qkvb), 3 * C, 3 * C, T,
+  PLAN_HIPCK(pack(S.qkv));
+  PLAN_HIPCK(linear_fwd(p->F(S.n1), C, C, p->F(S.qkv.pk), p->P(S.qkv.b), p->F(S.qkvb), 3 * C, 3 * C, T,
                     nullptr, 0, st));
-  SHIPCK(swin_attn_fwd(p->F(S.qkvb), p->P(S.qkv.b), p->P(S.tab), S.g, p->F(S.O), p->F(S.lse), st));
-  SHIPCK(pack(S.proj));
-  SHIPCK(linear_fwd(p->F(S.O), C, C, p->F(S.proj.pk), p->P(S.proj.b), p->F(S.x1), C, C, T, tin, C,
+  PLAN_HIPCK(swin_attn_fwd(p->F(S.qkvb), p->P(S.qkv.b), p->P(S.tab), S.g, p->F(S.O), p->F(S.lse), st));
+  PLAN_HIPCK(pack(S.proj));
+  PLAN_HIPCK(linear_fwd(p->F(S.O), C, C, p->F(S.proj.pk), p->P(S.proj.b), p->F(S.x1), C, C, T, tin, C,
                     st));
-  SHIPCK(ln_fwd(p->F(S.x1), C, C, p->P(S.n2w), p->P(S.n2b), p->F(S.n2), C, p->F(S.mu2),
+  PLAN_HIPCK(ln_fwd(p->F(S.x1), C, C, p->P(S.n2w), p->P(S.n2b), p->F(S.n2), C, p->F(S.mu2),
                 p->F(S.rs2), T, st));
-  SHIPCK(pack(S.l1));
-  SHIPCK(linear_fwd_gelu(p->F(S.n2), C, C, p->F(S.l1.pk), p->P(S.l1.b), p->F(S.hpre), p->F(S.hact),
+  PLAN_HIPCK(pack(S.l1));
+  PLAN_HIPCK(linear_fwd_gelu(p->F(S.n2), C, C, p->F(S.l1.pk), p->P(S.l1.b), p->F(S.hpre), p->F(S.hact),
                          S.hid, T, st));
-  SHIPCK(pack(S.l2));
-  SHIPCK(linear_fwd(p->F(S.hact), S.hid, S.hid, p->F(S.l2.pk), p->P(S.l2.b), p->F(S.x2), C, C, T,
+  PLAN_HIPCK(pack(S.l2));
+  PLAN_HIPCK(linear_fwd(p->F(S.hact), S.hid, S.hid, p->F(S.l2.pk), p->P(S.l2.b), p->F(S.x2), C, C, T,
                     p->F(S.x1), C, st));
-  SHIPCK(ln_merge_fwd(p->F(S.x2), C, v.B, v.D, v.H, v.W, p->P(S.mnw), p->P(S.mnb), p->F(S.mn),
+  PLAN_HIPCK(ln_merge_fwd(p->F(S.x2), C, v.B, v.D, v.H, v.W, p->P(S.mnw), p->P(S.mnb), p->F(S.mn),
                       p->F(S.mmu), p->F(S.mrs), st));
-  SHIPCK(pack(S.red));
-  SHIPCK(linear_fwd(p->F(S.mn), 8 * C, 8 * C, p->F(S.red.pk), nullptr, tout, 2 * C, 2 * C, T8,
+  PLAN_HIPCK(pack(S.red));
+  PLAN_HIPCK(linear_fwd(p->F(S.mn), 8 * C, 8 * C, p->F(S.red.pk), nullptr, tout, 2 * C, 2 * C, T8,
                     nullptr, 0, st));
   return SPFF_OK;
 }
@@ -330,38 +306,38 @@ int stage_bwd(spff_swin* p, Stage& S, const float* tin, const float* dtout, floa
   float* Bf = p->F(p->S_b);
   float* Cf = p->F(p->S_c);
   // merge: Linear(8C -> 2C) then LayerNorm(8C) of the gather
-  SHIPCK(linear_wgrad(p->F(S.mn), 8 * C, 8 * C, dtout, 2 * C, 2 * C, p->DP(S.red.w), p->F(p->dummy),
+  PLAN_HIPCK(linear_wgrad(p->F(S.mn), 8 * C, 8 * C, dtout, 2 * C, 2 * C, p->DP(S.red.w), p->F(p->dummy),
                       T8, wg, st));
-  SHIPCK(linear_dgrad(dtout, 2 * C, 2 * C, wd(S.red), A, 8 * C, 8 * C, T8, nullptr, st));
-  SHIPCK(ln_merge_bwd(p->F(S.x2), C, v.B, v.D, v.H, v.W, p->P(S.mnw), p->F(S.mmu), p->F(S.mrs), A,
+  PLAN_HIPCK(linear_dgrad(dtout, 2 * C, 2 * C, wd(S.red), A, 8 * C, 8 * C, T8, nullptr, st));
+  PLAN_HIPCK(ln_merge_bwd(p->F(S.x2), C, v.B, v.D, v.H, v.W, p->P(S.mnw), p->F(S.mmu), p->F(S.mrs), A,
                       Bf, p->DP(S.mnw), wg, st));
-  SHIPCK(unmerge(Bf, C, v.B, v.D, v.H, v.W, A, st));  // A = d x2
+  PLAN_HIPCK(unmerge(Bf, C, v.B, v.D, v.H, v.W, A, st));  // A = d x2
   // MLP: x2 = x1 + L2(gelu(L1(LN2(x1))))
   float* dh = p->F(p->S_h);
-  SHIPCK(linear_wgrad(p->F(S.hact), S.hid, S.hid, A, C, C, p->DP(S.l2.w), p->DP(S.l2.b), T, wg, st));
-  SHIPCK(linear_dgrad(A, C, C, wd(S.l2), dh, S.hid, S.hid, T, p->F(S.hpre), st));
-  SHIPCK(linear_wgrad(p->F(S.n2), C, C, dh, S.hid, S.hid, p->DP(S.l1.w), p->DP(S.l1.b), T, wg, st));
-  SHIPCK(linear_dgrad(dh, S.hid, S.hid, wd(S.l1), Bf, C, C, T, nullptr, st));  // Bf = d n2
+  PLAN_HIPCK(linear_wgrad(p->F(S.hact), S.hid, S.hid, A, C, C, p->DP(S.l2.w), p->DP(S.l2.b), T, wg, st));
+  PLAN_HIPCK(linear_dgrad(A, C, C, wd(S.l2), dh, S.hid, S.hid, T, p->F(S.hpre), st));
+  PLAN_HIPCK(linear_wgrad(p->F(S.n2), C, C, dh, S.hid, S.hid, p->DP(S.l1.w), p->DP(S.l1.b), T, wg, st));
+  PLAN_HIPCK(linear_dgrad(dh, S.hid, S.hid, wd(S.l1), Bf, C, C, T, nullptr, st));  // Bf = d n2
   // d x1 = d x2 + LN2'(d n2)  (into Cf)
-  SHIPCK(ln_bwd(p->F(S.x1), C, C, p->P(S.n2w), p->F(S.mu2), p->F(S.rs2), Bf, C, Cf, C, A, C,
+  PLAN_HIPCK(ln_bwd(p->F(S.x1), C, C, p->P(S.n2w), p->F(S.mu2), p->F(S.rs2), Bf, C, Cf, C, A, C,
                 p->DP(S.n2w), wg, T, st));
   // attention: x1 = t + Proj(O)
-  SHIPCK(linear_wgrad(p->F(S.O), C, C, Cf, C, C, p->DP(S.proj.w), p->DP(S.proj.b), T, wg, st));
-  SHIPCK(linear_dgrad(Cf, C, C, wd(S.proj), A, C, C, T, nullptr, st));  // A = dO
+  PLAN_HIPCK(linear_wgrad(p->F(S.O), C, C, Cf, C, C, p->DP(S.proj.w), p->DP(S.proj.b), T, wg, st));
+  PLAN_HIPCK(linear_dgrad(Cf, C, C, wd(S.proj), A, C, C, T, nullptr, st));  // A = dO
   float* dq = p->F(p->S_qkv);
-  SHIPCK(swin_attn_bwd(p->F(S.qkvb), p->P(S.qkv.b), p->P(S.tab), p->F(S.O), A, p->F(S.lse), S.g,
+  PLAN_HIPCK(swin_attn_bwd(p->F(S.qkvb), p->P(S.qkv.b), p->P(S.tab), p->F(S.O), A, p->F(S.lse), S.g,
                        dq, p->DP(S.tab), nullptr, wg, st));
   // the qkv weight gradient reuses wg: take the padded tokens' bias part first
-  SHIPCK(linear_dgrad(dq, 3 * C, 3 * C, wd(S.qkv), Bf, C, C, T, nullptr, st));  // Bf = d n1
+  PLAN_HIPCK(linear_dgrad(dq, 3 * C, 3 * C, wd(S.qkv), Bf, C, C, T, nullptr, st));  // Bf = d n1
   float* dpad = p->F(p->dummy);  // [3C] padded-token k / v bias grads
-  SHIPCK(spff::zero_async(dpad, fbytes(3 * C), st));
-  SHIPCK(swin_attn_pad_grad(S.g, wg, dpad, st));
-  SHIPCK(hipMemcpyAsync(A, dpad, fbytes(3 * C), hipMemcpyDeviceToDevice, st));  // A free again
-  SHIPCK(linear_wgrad(p->F(S.n1), C, C, dq, 3 * C, 3 * C, p->DP(S.qkv.w), p->DP(S.qkv.b), T, wg,
+  PLAN_HIPCK(spff::zero_async(dpad, fbytes(3 * C), st));
+  PLAN_HIPCK(swin_attn_pad_grad(S.g, wg, dpad, st));
+  PLAN_HIPCK(hipMemcpyAsync(A, dpad, fbytes(3 * C), hipMemcpyDeviceToDevice, st));  // A free again
+  PLAN_HIPCK(linear_wgrad(p->F(S.n1), C, C, dq, 3 * C, 3 * C, p->DP(S.qkv.w), p->DP(S.qkv.b), T, wg,
                       st));
-  SHIPCK(add_inplace(p->DP(S.qkv.b), A, 3 * C, st));
+  PLAN_HIPCK(add_inplace(p->DP(S.qkv.b), A, 3 * C, st));
   // d t = d x1 + LN1'(d n1)
-  SHIPCK(ln_bwd(tin, C, C, p->P(S.n1w), p->F(S.mu1), p->F(S.rs1), Bf, C, dtin, C, Cf, C,
+  PLAN_HIPCK(ln_bwd(tin, C, C, p->P(S.n1w), p->F(S.mu1), p->F(S.rs1), Bf, C, dtin, C, Cf, C,
                 p->DP(S.n1w), wg, T, st));
   return SPFF_OK;
 }
@@ -371,45 +347,45 @@ int forward(spff_swin* p, const float* x, float* logits) {
   const int f = p->f;
   const Vol& v0 = p->vol[0];
   hipStream_t st = p->st;
-  SHIPCK(spff::fill32_async(p->F(p->ones), (size_t)p->maxC * 4, 0x3f800000u, st));
-  SHIPCK(spff::zero_async(p->F(p->zeros), fbytes(p->maxC), st));
-  SHIPCK(ncdhw_to_ndhwc(x, p->F(p->x_cl), v0, c.in_ch, p->ldx, st));
+  PLAN_HIPCK(spff::fill32_async(p->F(p->ones), (size_t)p->maxC * 4, 0x3f800000u, st));
+  PLAN_HIPCK(spff::zero_async(p->F(p->zeros), fbytes(p->maxC), st));
+  PLAN_HIPCK(ncdhw_to_ndhwc(x, p->F(p->x_cl), v0, c.in_ch, p->ldx, st));
   // patch embedding -> t0 (L1, f); hs0 = LN(t0)
   float* pk = p->F(p->pe_pk);
-  SHIPCK(head_pack(p->P(p->pe_w), pk, pk + head_pack_dgrad_offset(8 * c.in_ch, f), 8 * c.in_ch, f,
+  PLAN_HIPCK(head_pack(p->P(p->pe_w), pk, pk + head_pack_dgrad_offset(8 * c.in_ch, f), 8 * c.in_ch, f,
                    st));
-  SHIPCK(patch_embed_fwd(p->F(p->x_cl), p->ldx, c.in_ch, v0.D, v0.H, v0.W, v0.B, pk, p->P(p->pe_b),
+  PLAN_HIPCK(patch_embed_fwd(p->F(p->x_cl), p->ldx, c.in_ch, v0.D, v0.H, v0.W, v0.B, pk, p->P(p->pe_b),
                          p->F(p->t[0]), f, st));
   for (int l = 0; l < 5; ++l) {
-    if (l > 0) SCK(stage_fwd(p, p->stg[l - 1], p->F(p->t[l - 1]), p->F(p->t[l])));
+    if (l > 0) PLAN_CK(stage_fwd(p, p->stg[l - 1], p->F(p->t[l - 1]), p->F(p->t[l])));
     const int C = f << l;
-    SHIPCK(ln_fwd(p->F(p->t[l]), C, C, nullptr, nullptr, p->F(p->hs[l]), C, p->F(p->hmu[l]),
+    PLAN_HIPCK(ln_fwd(p->F(p->t[l]), C, C, nullptr, nullptr, p->F(p->hs[l]), C, p->F(p->hmu[l]),
                   p->F(p->hrs[l]), nvox(p->vol[l + 1]), st));
   }
-  SCK(prep_weights(p));
+  PLAN_CK(prep_weights(p));
   RB* R = p->rb;
-  SCK(rb_fwd(p, R[0], src1(p->F(p->x_cl), p->ldx), nullptr));
+  PLAN_CK(rb_fwd(p, R[0], src1(p->F(p->x_cl), p->ldx), nullptr));
   for (int i = 1; i < 4; ++i) {
     const int C = f << (i - 1);
-    SCK(rb_fwd(p, R[i], src1(p->F(p->hs[i - 1]), C), p->F(p->hs[i - 1])));
+    PLAN_CK(rb_fwd(p, R[i], src1(p->F(p->hs[i - 1]), C), p->F(p->hs[i - 1])));
   }
-  SCK(rb_fwd(p, R[4], src1(p->F(p->hs[4]), 16 * f), p->F(p->hs[4])));
+  PLAN_CK(rb_fwd(p, R[4], src1(p->F(p->hs[4]), 16 * f), p->F(p->hs[4])));
   const float* prev = p->F(R[4].out);
   const float* skip[NUP] = {p->F(p->hs[3]), p->F(R[3].out), p->F(R[2].out), p->F(R[1].out),
                             p->F(R[0].out)};
   for (int u = 0; u < NUP; ++u) {
     Up& U = p->up[u];
     float* upk = p->F(U.pk);
-    SHIPCK(upconv_pack(p->P(U.w), upk, upk + upconv_pack_dgrad_offset(U.Cin, U.Cout, 8), U.Cin,
+    PLAN_HIPCK(upconv_pack(p->P(U.w), upk, upk + upconv_pack_dgrad_offset(U.Cin, U.Cout, 8), U.Cin,
                        U.Cout, st, 8));
-    SHIPCK(upconv_fwd(prev, upk, p->F(p->zeros), p->F(U.out), p->vol[U.Llow], U.Cin, U.Cout, st, 8));
+    PLAN_HIPCK(upconv_fwd(prev, upk, p->F(p->zeros), p->F(U.out), p->vol[U.Llow], U.Cin, U.Cout, st, 8));
     RB& r = R[5 + u];
-    SCK(rb_fwd(p, r, Src2{p->F(U.out), skip[u], U.Cout, U.Cout, U.Cout}, nullptr));
+    PLAN_CK(rb_fwd(p, r, Src2{p->F(U.out), skip[u], U.Cout, U.Cout, U.Cout}, nullptr));
     prev = p->F(r.out);
   }
   float* hp = p->F(p->head.pk);
-  SHIPCK(head_pack(p->P(p->head.w), hp, hp + head_pack_dgrad_offset(f, p->K), f, p->K, st));
-  SHIPCK(linear_fwd(prev, f, f, hp, p->P(p->head.b), logits, p->K, p->K, nvox(v0), nullptr, 0, st));
+  PLAN_HIPCK(head_pack(p->P(p->head.w), hp, hp + head_pack_dgrad_offset(f, p->K), f, p->K, st));
+  PLAN_HIPCK(linear_fwd(prev, f, f, hp, p->P(p->head.b), logits, p->K, p->K, nvox(v0), nullptr, 0, st));
   return SPFF_OK;
 }
 
@@ -422,9 +398,9 @@ int backward(spff_swin* p, const float* dl) {
   float* wg = p->F(p->wg_ws);
   float* Gout = p->F(p->G_out);
   float* hp = p->F(p->head.pk);
-  SHIPCK(linear_wgrad(p->F(R[9].out), f, f, dl, p->K, p->K, p->DP(p->head.w), p->DP(p->head.b),
+  PLAN_HIPCK(linear_wgrad(p->F(R[9].out), f, f, dl, p->K, p->K, p->DP(p->head.w), p->DP(p->head.b),
                       nvox(v0), wg, st));
-  SHIPCK(linear_dgrad(dl, p->K, p->K, hp + head_pack_dgrad_offset(f, p->K), Gout, f, f, nvox(v0),
+  PLAN_HIPCK(linear_dgrad(dl, p->K, p->K, hp + head_pack_dgrad_offset(f, p->K), Gout, f, f, nvox(v0),
                       nullptr, st));
   // decoders: dec1 (R9) <- up1 <- dec2 (R8) ... <- dec5 (R5) <- up5 <- enc10 (R4)
   float* dskip[NUP] = {p->F(p->d_hs[3]), p->F(p->d_enc[3]), p->F(p->d_enc[2]), p->F(p->d_enc[1]),
@@ -436,35 +412,35 @@ int backward(spff_swin* p, const float* dl) {
     RB& r = R[5 + u];
     float* dup = p->F(p->G_up);
     Dst2 dx{dup, dskip[u], U.Cout, U.Cout, U.Cout};
-    SCK(rb_bwd(p, r, Gout, Src2{p->F(U.out), skip[u], U.Cout, U.Cout, U.Cout}, nullptr, &dx));
+    PLAN_CK(rb_bwd(p, r, Gout, Src2{p->F(U.out), skip[u], U.Cout, U.Cout, U.Cout}, nullptr, &dx));
     const float* xlow = p->F(u == 0 ? R[4].out : R[5 + u - 1].out);
-    SHIPCK(upconv_wgrad(xlow, dup, U.Cout, p->DP(U.w), p->F(p->dummy), p->vol[U.Llow], U.Cin, U.Cout,
+    PLAN_HIPCK(upconv_wgrad(xlow, dup, U.Cout, p->DP(U.w), p->F(p->dummy), p->vol[U.Llow], U.Cin, U.Cout,
                         wg, st, 8));
     float* upk = p->F(U.pk);
-    SHIPCK(upconv_dgrad(dup, U.Cout, upk + upconv_pack_dgrad_offset(U.Cin, U.Cout, 8), Gout,
+    PLAN_HIPCK(upconv_dgrad(dup, U.Cout, upk + upconv_pack_dgrad_offset(U.Cin, U.Cout, 8), Gout,
                         p->vol[U.Llow], U.Cin, U.Cout, st, 8));
   }
   // Gout = d enc10.out
   {
     Dst2 dx = dst1(p->F(p->d_hs[4]), 16 * f);
-    SCK(rb_bwd(p, R[4], Gout, src1(p->F(p->hs[4]), 16 * f), p->F(p->hs[4]), &dx));
+    PLAN_CK(rb_bwd(p, R[4], Gout, src1(p->F(p->hs[4]), 16 * f), p->F(p->hs[4]), &dx));
   }
   for (int i = 3; i >= 1; --i) {
     const int C = f << (i - 1);
     Dst2 dx = dst1(p->F(p->d_hs[i - 1]), C);
-    SCK(rb_bwd(p, R[i], p->F(p->d_enc[i]), src1(p->F(p->hs[i - 1]), C), p->F(p->hs[i - 1]), &dx));
+    PLAN_CK(rb_bwd(p, R[i], p->F(p->d_enc[i]), src1(p->F(p->hs[i - 1]), C), p->F(p->hs[i - 1]), &dx));
   }
-  SCK(rb_bwd(p, R[0], p->F(p->d_enc[0]), src1(p->F(p->x_cl), p->ldx), nullptr, nullptr));
+  PLAN_CK(rb_bwd(p, R[0], p->F(p->d_enc[0]), src1(p->F(p->x_cl), p->ldx), nullptr, nullptr));
   // Swin: dT[l] = grad of t l = (stage l backward) + LN'(d hs l)
   for (int l = 4; l >= 0; --l) {
     const int C = f << l;
     const int64_t T = nvox(p->vol[l + 1]);
     float* dTl = p->F(p->dT[l]);
-    if (l < 4) SCK(stage_bwd(p, p->stg[l], p->F(p->t[l]), p->F(p->dT[l + 1]), dTl));
-    SHIPCK(ln_bwd(p->F(p->t[l]), C, C, nullptr, p->F(p->hmu[l]), p->F(p->hrs[l]), p->F(p->d_hs[l]), C,
+    if (l < 4) PLAN_CK(stage_bwd(p, p->stg[l], p->F(p->t[l]), p->F(p->dT[l + 1]), dTl));
+    PLAN_HIPCK(ln_bwd(p->F(p->t[l]), C, C, nullptr, p->F(p->hmu[l]), p->F(p->hrs[l]), p->F(p->d_hs[l]), C,
                   dTl, C, l < 4 ? dTl : nullptr, C, nullptr, wg, T, st));
   }
-  SHIPCK(patch_embed_wgrad(p->F(p->x_cl), p->ldx, c.in_ch, v0.D, v0.H, v0.W, v0.B, p->F(p->dT[0]), f,
+  PLAN_HIPCK(patch_embed_wgrad(p->F(p->x_cl), p->ldx, c.in_ch, v0.D, v0.H, v0.W, v0.B, p->F(p->dT[0]), f,
                            p->DP(p->pe_w), p->DP(p->pe_b), wg, st));
   return SPFF_OK;
 }
@@ -475,16 +451,7 @@ int backward(spff_swin* p, const float* dl) {
 extern "C" {
 
 int spff_swin_create(const spff_swin_cfg* cfg, spff_swin** out) {
-  if (!cfg || !out) return sfail(SPFF_EINVAL, "null argument");
-  spff_swin* p = new spff_swin();
-  p->cfg = *cfg;
-  const int r = build(p);
-  if (r != SPFF_OK) {
-    delete p;
-    return r;
-  }
-  *out = p;
-  return SPFF_OK;
+  return plan_create(cfg, out, build);
 }
 
 void spff_swin_destroy(spff_swin* p) { delete p; }
@@ -493,15 +460,8 @@ int spff_swin_num_params(const spff_swin* p) { return p ? (int)p->params.size() 
 
 int spff_swin_param_info(const spff_swin* p, int i, const char** name, int* ndim,
                          int64_t shape[5], int64_t* offset, int64_t* numel) {
-  if (!p || i < 0 || i >= (int)p->params.size()) return sfail(SPFF_EINVAL, "param index");
-  const SEnt& e = p->params[i];
-  if (name) *name = e.name.c_str();
-  if (ndim) *ndim = (int)e.shape.size();
-  if (shape)
-    for (int k = 0; k < 5; ++k) shape[k] = k < (int)e.shape.size() ? e.shape[k] : 1;
-  if (offset) *offset = e.off;
-  if (numel) *numel = e.numel;
-  return SPFF_OK;
+  if (!p) return plan_fail(SPFF_EINVAL, "param index");
+  return plan_param_info(p->params, i, name, ndim, shape, offset, numel);
 }
 
 int64_t spff_swin_param_floats(const spff_swin* p) { return p ? p->nparam : 0; }
@@ -509,35 +469,23 @@ size_t spff_swin_workspace_bytes(const spff_swin* p) { return p ? p->total : 0; 
 
 int spff_swin_forward(spff_swin* p, const float* x, const float* params, float* logits, void* ws,
                       void* stream) {
-  if (!p || !x || !params || !logits || !ws) return sfail(SPFF_EINVAL, "null argument");
-  p->ws = static_cast<char*>(ws);
-  p->prm = params;
-  p->dprm = nullptr;
-  p->st = static_cast<hipStream_t>(stream);
+  if (!p || !x || !params || !logits || !ws) return plan_fail(SPFF_EINVAL, "null argument");
+  p->bind(ws, params, nullptr, stream);
   return forward(p, x, logits);
 }
 
 int spff_swin_backward(spff_swin* p, const float* dlogits, const float* params, float* dparams,
                        void* ws, void* stream) {
-  if (!p || !dlogits || !params || !dparams || !ws) return sfail(SPFF_EINVAL, "null argument");
-  p->ws = static_cast<char*>(ws);
-  p->prm = params;
-  p->dprm = dparams;
-  p->st = static_cast<hipStream_t>(stream);
+  if (!p || !dlogits || !params || !dparams || !ws) return plan_fail(SPFF_EINVAL, "null argument");
+  p->bind(ws, params, dparams, stream);
   return backward(p, dlogits);
 }
 
 int spff_swin_saved_tensor(const spff_swin* p, void* ws, const char* name, const float** ptr,
                            int64_t* nv, int* ch) {
-  if (!p || !ws || !name || !ptr) return sfail(SPFF_EINVAL, "null argument");
-  const char* base = static_cast<const char*>(ws);
+  if (!p || !ws || !name || !ptr) return plan_fail(SPFF_EINVAL, "null argument");
   const std::string n(name);
-  auto ret = [&](size_t off, int64_t rows, int c) {
-    *ptr = reinterpret_cast<const float*>(base + off);
-    if (nv) *nv = rows;
-    if (ch) *ch = c;
-    return SPFF_OK;
-  };
+  const SavedOut ret{ws, ptr, nv, ch};
   const int f = p->f;
   for (int l = 0; l < 5; ++l) {
     const int64_t T = nvox(p->vol[l + 1]);
@@ -575,7 +523,7 @@ int spff_swin_saved_tensor(const spff_swin* p, void* ws, const char* name, const
   const char* upn[NUP] = {"up5", "up4", "up3", "up2", "up1"};
   for (int u = 0; u < NUP; ++u)
     if (n == upn[u]) return ret(p->up[u].out, nvox(p->vol[p->up[u].Llow - 1]), p->up[u].Cout);
-  return sfail(SPFF_EINVAL, "unknown saved tensor " + n);
+  return plan_fail(SPFF_EINVAL, "unknown saved tensor " + n);
 }
 
 size_t spff_swin_loss_ws_bytes(int batch, int num_classes) {
@@ -585,8 +533,8 @@ size_t spff_swin_loss_ws_bytes(int batch, int num_classes) {
 int spff_swin_loss(const float* logits, const int64_t* labels, int batch, int64_t vox_per_sample,
                    int num_classes, int ignore_index, int include_bg, double ce_weight,
                    float* out4, float* dlogits, void* ws, void* stream) {
-  if (!logits || !labels || !out4 || !dlogits || !ws) return sfail(SPFF_EINVAL, "null argument");
-  SHIPCK(dice_ce_loss(logits, labels, batch, vox_per_sample, num_classes, ignore_index, include_bg,
+  if (!logits || !labels || !out4 || !dlogits || !ws) return plan_fail(SPFF_EINVAL, "null argument");
+  PLAN_HIPCK(dice_ce_loss(logits, labels, batch, vox_per_sample, num_classes, ignore_index, include_bg,
                       ce_weight, out4, dlogits, ws, static_cast<hipStream_t>(stream)));
   return SPFF_OK;
 }

@@ -18,8 +18,7 @@
 // in_bwd_apply with ReLU's zero slope, the ConvTranspose GEMMs of gemm.hip with
 // 8 sub-lattices, and the 2x2x2 max pool of misc.hip.  Saved for backward:
 // y1, a1, y2, out per block, the pool argmax bytes and the statistics.
-#include "spff_internal.h"
-#include "spff.h"
+#include "plan_base.h"
 
 #include <string>
 #include <vector>
@@ -28,27 +27,8 @@ using namespace spff;
 
 namespace {
 
-int ufail(int code, const std::string& m) { return set_error(code, m.c_str()); }
-#define UHIPCK(expr)                                                                       \
-  do {                                                                                     \
-    hipError_t _e = (expr);                                                                \
-    if (_e != hipSuccess)                                                                  \
-      return ufail(SPFF_EHIP, std::string(#expr) + " -> " + hipGetErrorString(_e));        \
-  } while (0)
-#define UCK(expr)                   \
-  do {                              \
-    int _r = (expr);                \
-    if (_r != SPFF_OK) return _r;   \
-  } while (0)
-
 constexpr int NLVL = 5, NBLK = 9, NUP = 4, NSUB = 8;
 constexpr double BN_MOM = 0.1, BN_EPS = 1e-5;  // nn.BatchNorm3d defaults
-
-struct UEnt {
-  std::string name;
-  std::vector<int64_t> shape;
-  int64_t off, numel;
-};
 
 struct UBlk {
   std::string name;
@@ -66,16 +46,14 @@ struct UUp {
   size_t pk, out;
 };
 
-inline int rup(int a, int b) { return (a + b - 1) / b * b; }
-
 }  // namespace
 
-struct spff_unet3d {
+struct spff_unet3d : PlanBase {
   spff_unet3d_cfg cfg;
   Vol vol[NLVL];
   int f, K, ldx, Dt;
-  std::vector<UEnt> params, bufs;
-  int64_t nparam = 0, nbuf = 0;
+  std::vector<ParamEnt> bufs;  // BatchNorm running statistics: the second flat buffer
+  int64_t nbuf = 0;
   UBlk blk[NBLK];  // enc1..enc4, bott, dec4..dec1
   UUp up[NUP];     // up4, up3, up2, up1
   int64_t out_w = -1, out_b = -1;
@@ -84,7 +62,6 @@ struct spff_unet3d {
   bool pkb = false;  // conv images packed in one batch at the forward start (b.pk)
   size_t wsl = 0;    // SPFF_MATH_F16X3 max |w| per conv, [NBLK][2] (batched plans)
   size_t G_out = 0, G_dy2 = 0, G_da1 = 0, G_dx = 0, dskip[4] = {}, logit_t = 0, dl_t = 0;
-  size_t total = 0;
   bool last_training = true;
   // synchronised BatchNorm (spff_unet3d_set_sync_bn): the per-channel batch moments and the
   // backward's two per-channel sums are all-reduced (fp64) over the data-parallel group, so
@@ -92,31 +69,11 @@ struct spff_unet3d {
   // 1 or no table: per-replica statistics, as DDP without SyncBN
   Coll co;
   size_t bnp = 0;  // fp64 per-channel partials [2][16 f]
-  // per call
-  char* ws = nullptr;
-  const float* prm = nullptr;
-  float* dprm = nullptr;
-  float* buf = nullptr;
-  hipStream_t st = nullptr;
+  float* buf = nullptr;  // per call, beside PlanBase's
 
-  float* F(size_t off) const { return reinterpret_cast<float*>(ws + off); }
-  const float* P(int64_t off) const { return off < 0 ? nullptr : prm + off; }
-  float* DP(int64_t off) const { return off < 0 ? nullptr : dprm + off; }
   float* BF(int64_t off) const { return off < 0 || !buf ? nullptr : buf + off; }
-  size_t alloc(size_t bytes) {
-    size_t o = total;
-    total += (bytes + 255) / 256 * 256;
-    return o;
-  }
-  int64_t reg(const std::string& name, std::vector<int64_t> shape) {
-    int64_t n = 1;
-    for (auto s : shape) n *= s;
-    params.push_back(UEnt{name, shape, nparam, n});
-    nparam += n;
-    return nparam - n;
-  }
   int64_t regb(const std::string& name, int64_t n) {
-    bufs.push_back(UEnt{name, {n}, nbuf, n});
+    bufs.push_back(ParamEnt{name, {n}, nbuf, n});
     nbuf += n;
     return nbuf - n;
   }
@@ -143,15 +100,15 @@ int build(spff_unet3d* p) {
   const spff_unet3d_cfg& c = p->cfg;
   if (c.batch < 1 || c.in_ch < 1 || c.depth < 1 || c.num_classes < 1 ||
       c.num_classes > SPFF_MAX_CLASSES)
-    return ufail(SPFF_EINVAL, "invalid batch/in_ch/depth/num_classes (K must be 1..SPFF_MAX_CLASSES)");
-  if (c.base < 8 || c.base % 8) return ufail(SPFF_EINVAL, "base must be a multiple of 8");
-  if (c.in_ch > 64) return ufail(SPFF_EINVAL, "in_ch > 64 not supported");
+    return plan_fail(SPFF_EINVAL, "invalid batch/in_ch/depth/num_classes (K must be 1..SPFF_MAX_CLASSES)");
+  if (c.base < 8 || c.base % 8) return plan_fail(SPFF_EINVAL, "base must be a multiple of 8");
+  if (c.in_ch > 64) return plan_fail(SPFF_EINVAL, "in_ch > 64 not supported");
   if (c.math < SPFF_MATH_F32 || c.math > SPFF_MATH_F16X3)
-    return ufail(SPFF_EINVAL, "math must be one of SPFF_MATH_*");
-  if (c.target_depth < 0) return ufail(SPFF_EINVAL, "target_depth must be >= 0");
+    return plan_fail(SPFF_EINVAL, "math must be one of SPFF_MATH_*");
+  if (c.target_depth < 0) return plan_fail(SPFF_EINVAL, "target_depth must be >= 0");
   p->Dt = c.target_depth > 0 ? c.target_depth : c.depth;
   if (p->Dt % 16 || c.height % 16 || c.width % 16 || c.height < 16 || c.width < 16)
-    return ufail(SPFF_ESHAPE,
+    return plan_fail(SPFF_ESHAPE,
                  "backbone D, H and W must be multiples of 16 (four MaxPool3d(2) whose outputs "
                  "torch.cat with the ConvTranspose3d outputs, models.py:743-752)");
   p->f = c.base;
@@ -267,31 +224,31 @@ int build(spff_unet3d* p) {
 int bn_fwd(spff_unet3d* p, const Vol& v, int C, size_t y, size_t mean, size_t rstd, size_t al,
            size_t de, int64_t g, int64_t b, int64_t rm, int64_t rv, bool training) {
   if (!training) {
-    UHIPCK(bn_eval(p->BF(rm), p->BF(rv), p->P(g), p->P(b), p->F(mean), p->F(rstd), p->F(al),
+    PLAN_HIPCK(bn_eval(p->BF(rm), p->BF(rv), p->P(g), p->P(b), p->F(mean), p->F(rstd), p->F(al),
                    p->F(de), BN_EPS, v.B, C, p->st));
     return SPFF_OK;
   }
   RedArgs a{};
   a.y = p->F(y);
-  UHIPCK(slab_reduce(RED_SUM, a, v, C, p->F(p->red_out), p->F(p->red_ws), p->st));
+  PLAN_HIPCK(slab_reduce(RED_SUM, a, v, C, p->F(p->red_out), p->F(p->red_ws), p->st));
   if (p->co.on()) {  // SyncBN: global moments (same fp64 per-channel sums, then the group's)
     double* part = reinterpret_cast<double*>(p->ws + p->bnp);
     const double N = (double)nvox(v) * p->co.world;  // every rank runs the plan's shape
-    UHIPCK(bn_partial(p->F(p->red_out), part, v, C, 1, p->st));
-    UHIPCK(p->co.sum_f64(part, C, p->st));
-    UHIPCK(bn_mean_fin(part, p->F(mean), v.B, C, N, p->st));
+    PLAN_HIPCK(bn_partial(p->F(p->red_out), part, v, C, 1, p->st));
+    PLAN_HIPCK(p->co.sum_f64(part, C, p->st));
+    PLAN_HIPCK(bn_mean_fin(part, p->F(mean), v.B, C, N, p->st));
     a.mean = p->F(mean);
-    UHIPCK(slab_reduce(RED_SQDEV, a, v, C, p->F(p->red_out), p->F(p->red_ws), p->st));
-    UHIPCK(bn_partial(p->F(p->red_out), part, v, C, 1, p->st));
-    UHIPCK(p->co.sum_f64(part, C, p->st));
-    UHIPCK(bn_rstd_fin(part, p->P(g), p->P(b), p->F(mean), p->F(rstd), p->F(al), p->F(de),
+    PLAN_HIPCK(slab_reduce(RED_SQDEV, a, v, C, p->F(p->red_out), p->F(p->red_ws), p->st));
+    PLAN_HIPCK(bn_partial(p->F(p->red_out), part, v, C, 1, p->st));
+    PLAN_HIPCK(p->co.sum_f64(part, C, p->st));
+    PLAN_HIPCK(bn_rstd_fin(part, p->P(g), p->P(b), p->F(mean), p->F(rstd), p->F(al), p->F(de),
                        p->BF(rm), p->BF(rv), BN_MOM, BN_EPS, v.B, C, N, p->st));
     return SPFF_OK;
   }
-  UHIPCK(bn_mean(p->F(p->red_out), p->F(mean), v, C, p->st));
+  PLAN_HIPCK(bn_mean(p->F(p->red_out), p->F(mean), v, C, p->st));
   a.mean = p->F(mean);
-  UHIPCK(slab_reduce(RED_SQDEV, a, v, C, p->F(p->red_out), p->F(p->red_ws), p->st));
-  UHIPCK(bn_rstd(p->F(p->red_out), p->P(g), p->P(b), p->F(mean), p->F(rstd), p->F(al), p->F(de),
+  PLAN_HIPCK(slab_reduce(RED_SQDEV, a, v, C, p->F(p->red_out), p->F(p->red_ws), p->st));
+  PLAN_HIPCK(bn_rstd(p->F(p->red_out), p->P(g), p->P(b), p->F(mean), p->F(rstd), p->F(al), p->F(de),
                  p->BF(rm), p->BF(rv), BN_MOM, BN_EPS, v, C, p->st));
   return SPFF_OK;
 }
@@ -307,7 +264,7 @@ int prep_weights(spff_unet3d* p) {
   unsigned* sl = reinterpret_cast<unsigned*>(p->ws + p->wsl);
   PrepJobs pj;
   PackJobs kj;
-  if (f16) UHIPCK(spff::zero_async(sl, NBLK * 2 * sizeof(unsigned), p->st));
+  if (f16) PLAN_HIPCK(spff::zero_async(sl, NBLK * 2 * sizeof(unsigned), p->st));
   for (int i = 0; i < NBLK; ++i) {
     UBlk& b = p->blk[i];
     unsigned* w1 = f16 ? sl + 2 * i : nullptr;
@@ -321,10 +278,10 @@ int prep_weights(spff_unet3d* p) {
     ok = ok && conv3d_pack_job(&kj, p->P(b.w2), p->F(b.pk[1]), 3, b.C, b.C, false, w2);
     ok = ok && conv3d_pack_job(&kj, p->P(b.w2), p->F(b.pk[2]), 3, b.C, b.C, true, w2);
     if (b.pk[3]) ok = ok && conv3d_pack_job(&kj, p->P(b.w1), p->F(b.pk[3]), 3, b.Cin, b.C, true, w1);
-    if (!ok) return ufail(SPFF_EINVAL, "weight preparation table overflow");
+    if (!ok) return plan_fail(SPFF_EINVAL, "weight preparation table overflow");
   }
-  UHIPCK(prep_run(pj, p->st));
-  UHIPCK(conv3d_pack_many(kj, math, p->st));
+  PLAN_HIPCK(prep_run(pj, p->st));
+  PLAN_HIPCK(conv3d_pack_many(kj, math, p->st));
   return SPFF_OK;
 }
 // conv k of block b (0: w1 fwd, 1: w2 fwd, 2: w2 dgrad, 3: w1 dgrad): its image (the
@@ -334,14 +291,14 @@ int conv_image(spff_unet3d* p, const UBlk& b, int k, const Vol& v, const float**
   const bool c1 = k == 0 || k == 3;
   const int bi = (int)(&b - p->blk);
   if (p->pkb) {
-    if (!b.pk[k]) return ufail(SPFF_EINVAL, "no batched image for this conv");
+    if (!b.pk[k]) return plan_fail(SPFF_EINVAL, "no batched image for this conv");
     *img = p->F(b.pk[k]);
     *wmax = p->cfg.math == SPFF_MATH_F16X3
                 ? reinterpret_cast<const unsigned*>(p->ws + p->wsl) + 2 * bi + (c1 ? 0 : 1)
                 : nullptr;
     return SPFF_OK;
   }
-  UHIPCK(conv3d_pack(p->P(c1 ? b.w1 : b.w2), p->F(p->wt), v, 3, c1 ? b.Cin : b.C, b.C, k >= 2,
+  PLAN_HIPCK(conv3d_pack(p->P(c1 ? b.w1 : b.w2), p->F(p->wt), v, 3, c1 ? b.Cin : b.C, b.C, k >= 2,
                      p->cfg.math, p->st));
   *img = p->F(p->wt);
   *wmax = nullptr;
@@ -353,17 +310,17 @@ int fwd_block(spff_unet3d* p, UBlk& b, const Src2& in, bool training) {
   const int C = b.C, math = p->cfg.math;
   const float* img;
   const unsigned* wmax;
-  UCK(conv_image(p, b, 0, v, &img, &wmax));
-  UHIPCK(conv3d_run(in, img, dst1(p->F(b.y1), C), v, 3, b.Cin, C, false, math, p->st,
+  PLAN_CK(conv_image(p, b, 0, v, &img, &wmax));
+  PLAN_HIPCK(conv3d_run(in, img, dst1(p->F(b.y1), C), v, 3, b.Cin, C, false, math, p->st,
                     p->F(p->wg_ws), nullptr, 0, wmax));
-  UCK(bn_fwd(p, v, C, b.y1, b.mean1, b.rstd1, b.al1, b.de1, b.g1, b.b1, b.rm1, b.rv1, training));
-  UHIPCK(act_apply(p->F(b.y1), p->F(b.a1), p->F(b.al1), p->F(b.de1), nullptr, nullptr, v, C,
+  PLAN_CK(bn_fwd(p, v, C, b.y1, b.mean1, b.rstd1, b.al1, b.de1, b.g1, b.b1, b.rm1, b.rv1, training));
+  PLAN_HIPCK(act_apply(p->F(b.y1), p->F(b.a1), p->F(b.al1), p->F(b.de1), nullptr, nullptr, v, C,
                    p->st, 0.f));
-  UCK(conv_image(p, b, 1, v, &img, &wmax));
-  UHIPCK(conv3d_run(src1(p->F(b.a1), C), img, dst1(p->F(b.y2), C), v, 3, C, C, false, math,
+  PLAN_CK(conv_image(p, b, 1, v, &img, &wmax));
+  PLAN_HIPCK(conv3d_run(src1(p->F(b.a1), C), img, dst1(p->F(b.y2), C), v, 3, C, C, false, math,
                     p->st, p->F(p->wg_ws), nullptr, 0, wmax));
-  UCK(bn_fwd(p, v, C, b.y2, b.mean2, b.rstd2, b.al2, b.de2, b.g2, b.b2, b.rm2, b.rv2, training));
-  UHIPCK(act_apply(p->F(b.y2), p->F(b.out), p->F(b.al2), p->F(b.de2), nullptr, nullptr, v, C,
+  PLAN_CK(bn_fwd(p, v, C, b.y2, b.mean2, b.rstd2, b.al2, b.de2, b.g2, b.b2, b.rm2, b.rv2, training));
+  PLAN_HIPCK(act_apply(p->F(b.y2), p->F(b.out), p->F(b.al2), p->F(b.de2), nullptr, nullptr, v, C,
                    p->st, 0.f));
   return SPFF_OK;
 }
@@ -374,21 +331,21 @@ int bn_bwd(spff_unet3d* p, const Vol& v, int C, size_t y, const float* g, float*
   RedArgs a{};
   a.y = p->F(y); a.g = g; a.mean = p->F(mean); a.rstd = p->F(rstd);
   a.al = p->F(al); a.de = p->F(de); a.neg = 0.f;
-  UHIPCK(slab_reduce(RED_BWD_IN, a, v, C, p->F(p->red_out), p->F(p->red_ws), p->st));
+  PLAN_HIPCK(slab_reduce(RED_BWD_IN, a, v, C, p->F(p->red_out), p->F(p->red_ws), p->st));
   if (p->co.on() && p->last_training) {
     // SyncBN: k1, k2 from the group's sums; dgamma / dbeta are this rank's partial sums
     // (the flat gradient is SUM-all-reduced afterwards, like every other parameter's)
     double* part = reinterpret_cast<double*>(p->ws + p->bnp);
-    UHIPCK(bn_partial(p->F(p->red_out), part, v, C, 2, p->st));
-    UHIPCK(bn_bwd_dgb_part(part, p->DP(gamma), p->DP(beta), C, p->st));
-    UHIPCK(p->co.sum_f64(part, 2 * (int64_t)C, p->st));
-    UHIPCK(bn_bwd_fin(part, p->F(p->kk1), p->F(p->kk2), v.B, C, (double)nvox(v) * p->co.world,
+    PLAN_HIPCK(bn_partial(p->F(p->red_out), part, v, C, 2, p->st));
+    PLAN_HIPCK(bn_bwd_dgb_part(part, p->DP(gamma), p->DP(beta), C, p->st));
+    PLAN_HIPCK(p->co.sum_f64(part, 2 * (int64_t)C, p->st));
+    PLAN_HIPCK(bn_bwd_fin(part, p->F(p->kk1), p->F(p->kk2), v.B, C, (double)nvox(v) * p->co.world,
                       p->st));
   } else {
-    UHIPCK(bn_bwd_stats(p->F(p->red_out), p->DP(gamma), p->DP(beta), p->F(p->kk1), p->F(p->kk2),
+    PLAN_HIPCK(bn_bwd_stats(p->F(p->red_out), p->DP(gamma), p->DP(beta), p->F(p->kk1), p->F(p->kk2),
                         v, C, p->st, p->last_training ? 0 : 1));
   }
-  UHIPCK(in_bwd_apply(p->F(y), g, dy, p->F(mean), p->F(rstd), p->F(al), p->F(de), p->P(gamma),
+  PLAN_HIPCK(in_bwd_apply(p->F(y), g, dy, p->F(mean), p->F(rstd), p->F(al), p->F(de), p->P(gamma),
                       nullptr, nullptr, p->F(p->kk1), p->F(p->kk2), v, C, p->st, 0.f));
   return SPFF_OK;
 }
@@ -398,19 +355,19 @@ int bwd_block(spff_unet3d* p, UBlk& b, const float* dout, const Dst2* dx, const 
   const int C = b.C, math = p->cfg.math;
   float* dy2 = p->F(p->G_dy2);
   float* da1 = p->F(p->G_da1);
-  UCK(bn_bwd(p, v, C, b.y2, dout, dy2, b.mean2, b.rstd2, b.al2, b.de2, b.g2, b.b2));
-  UHIPCK(conv3d_wgrad(src1(p->F(b.a1), C), dy2, C, p->DP(b.w2), v, 3, C, C, math,
+  PLAN_CK(bn_bwd(p, v, C, b.y2, dout, dy2, b.mean2, b.rstd2, b.al2, b.de2, b.g2, b.b2));
+  PLAN_HIPCK(conv3d_wgrad(src1(p->F(b.a1), C), dy2, C, p->DP(b.w2), v, 3, C, C, math,
                       p->F(p->wg_ws), p->st));
   const float* img;
   const unsigned* wmax;
-  UCK(conv_image(p, b, 2, v, &img, &wmax));
-  UHIPCK(conv3d_run(src1(dy2, C), img, dst1(da1, C), v, 3, C, C, true, math, p->st,
+  PLAN_CK(conv_image(p, b, 2, v, &img, &wmax));
+  PLAN_HIPCK(conv3d_run(src1(dy2, C), img, dst1(da1, C), v, 3, C, C, true, math, p->st,
                     p->F(p->wg_ws), nullptr, 0, wmax));
-  UCK(bn_bwd(p, v, C, b.y1, da1, da1, b.mean1, b.rstd1, b.al1, b.de1, b.g1, b.b1));
-  UHIPCK(conv3d_wgrad(in, da1, C, p->DP(b.w1), v, 3, b.Cin, C, math, p->F(p->wg_ws), p->st));
+  PLAN_CK(bn_bwd(p, v, C, b.y1, da1, da1, b.mean1, b.rstd1, b.al1, b.de1, b.g1, b.b1));
+  PLAN_HIPCK(conv3d_wgrad(in, da1, C, p->DP(b.w1), v, 3, b.Cin, C, math, p->F(p->wg_ws), p->st));
   if (dx) {
-    UCK(conv_image(p, b, 3, v, &img, &wmax));
-    UHIPCK(conv3d_run(src1(da1, C), img, *dx, v, 3, b.Cin, C, true, math, p->st,
+    PLAN_CK(conv_image(p, b, 3, v, &img, &wmax));
+    PLAN_HIPCK(conv3d_run(src1(da1, C), img, *dx, v, 3, b.Cin, C, true, math, p->st,
                       p->F(p->wg_ws), nullptr, 0, wmax));
   }
   return SPFF_OK;
@@ -421,40 +378,40 @@ int forward(spff_unet3d* p, const float* x, float* logits, bool training) {
   const int f = p->f;
   const Vol& v0 = p->vol[0];
   if (p->Dt != c.depth)  // _resize_depth_like (models.py:153-157)
-    UHIPCK(resize_d_ncdhw_to_ndhwc(x, p->F(p->x_cl), c.batch, c.in_ch, c.depth, p->Dt, c.height,
+    PLAN_HIPCK(resize_d_ncdhw_to_ndhwc(x, p->F(p->x_cl), c.batch, c.in_ch, c.depth, p->Dt, c.height,
                                    c.width, p->ldx, p->st));
   else
-    UHIPCK(ncdhw_to_ndhwc(x, p->F(p->x_cl), v0, c.in_ch, p->ldx, p->st));
-  UCK(prep_weights(p));
+    PLAN_HIPCK(ncdhw_to_ndhwc(x, p->F(p->x_cl), v0, c.in_ch, p->ldx, p->st));
+  PLAN_CK(prep_weights(p));
   UBlk* B = p->blk;
   Src2 in = src1(p->F(p->x_cl), p->ldx);
   for (int l = 0; l < 4; ++l) {
-    UCK(fwd_block(p, B[l], in, training));
-    UHIPCK(maxpool3_fwd(p->F(B[l].out), p->F(p->pool[l]),
+    PLAN_CK(fwd_block(p, B[l], in, training));
+    PLAN_HIPCK(maxpool3_fwd(p->F(B[l].out), p->F(p->pool[l]),
                         reinterpret_cast<uint8_t*>(p->ws + p->pidx[l]), p->vol[l], f << l, p->st));
     in = src1(p->F(p->pool[l]), f << l);
   }
-  UCK(fwd_block(p, B[4], in, training));
+  PLAN_CK(fwd_block(p, B[4], in, training));
   const float* prev = p->F(B[4].out);
   for (int u = 0; u < NUP; ++u) {
     UUp& U = p->up[u];
     float* pk = p->F(U.pk);
-    UHIPCK(upconv_pack(p->P(U.w), pk, pk + upconv_pack_dgrad_offset(U.Cin, U.Cout, NSUB), U.Cin,
+    PLAN_HIPCK(upconv_pack(p->P(U.w), pk, pk + upconv_pack_dgrad_offset(U.Cin, U.Cout, NSUB), U.Cin,
                        U.Cout, p->st, NSUB));
-    UHIPCK(upconv_fwd(prev, pk, p->P(U.b), p->F(U.out), p->vol[U.lvl_low], U.Cin, U.Cout, p->st,
+    PLAN_HIPCK(upconv_fwd(prev, pk, p->P(U.b), p->F(U.out), p->vol[U.lvl_low], U.Cin, U.Cout, p->st,
                       NSUB, p->cfg.math));
     UBlk& d = B[5 + u];
     const UBlk& skip = B[3 - u];
     // torch.cat([up(x), skip], dim=1) read in place through the two-source view
-    UCK(fwd_block(p, d, Src2{p->F(U.out), p->F(skip.out), U.Cout, U.Cout, U.Cout}, training));
+    PLAN_CK(fwd_block(p, d, Src2{p->F(U.out), p->F(skip.out), U.Cout, U.Cout, U.Cout}, training));
     prev = p->F(d.out);
   }
   float* hp = p->F(p->head_pk);
-  UHIPCK(head_pack(p->P(p->out_w), hp, hp + head_pack_dgrad_offset(f, p->K), f, p->K, p->st));
+  PLAN_HIPCK(head_pack(p->P(p->out_w), hp, hp + head_pack_dgrad_offset(f, p->K), f, p->K, p->st));
   float* lt = p->Dt != c.depth ? p->F(p->logit_t) : logits;
-  UHIPCK(head_fwd(prev, hp, p->P(p->out_b), lt, nvox(v0), f, p->K, p->st, p->cfg.math));
+  PLAN_HIPCK(head_fwd(prev, hp, p->P(p->out_b), lt, nvox(v0), f, p->K, p->st, p->cfg.math));
   if (p->Dt != c.depth)  // _resize_logits_depth_like (models.py:159-163)
-    UHIPCK(resize_d_rows(lt, logits, c.batch, p->K, p->Dt, c.depth, c.height, c.width, p->st));
+    PLAN_HIPCK(resize_d_rows(lt, logits, c.batch, p->K, p->Dt, c.depth, c.height, c.width, p->st));
   p->last_training = training;
   return SPFF_OK;
 }
@@ -466,14 +423,14 @@ int backward(spff_unet3d* p, const float* dl) {
   UBlk* B = p->blk;
   const float* d16 = dl;
   if (p->Dt != c.depth) {
-    UHIPCK(resize_d_rows_bwd(dl, p->F(p->dl_t), c.batch, p->K, p->Dt, c.depth, c.height,
+    PLAN_HIPCK(resize_d_rows_bwd(dl, p->F(p->dl_t), c.batch, p->K, p->Dt, c.depth, c.height,
                              c.width, p->st));
     d16 = p->F(p->dl_t);
   }
   float* hp = p->F(p->head_pk);
-  UHIPCK(head_wgrad(p->F(B[8].out), d16, p->DP(p->out_w), p->DP(p->out_b), V0, f, p->K,
+  PLAN_HIPCK(head_wgrad(p->F(B[8].out), d16, p->DP(p->out_w), p->DP(p->out_b), V0, f, p->K,
                     p->F(p->wg_ws), p->st));
-  UHIPCK(head_dgrad(d16, hp + head_pack_dgrad_offset(f, p->K), p->F(p->G_out), V0, f, p->K,
+  PLAN_HIPCK(head_dgrad(d16, hp + head_pack_dgrad_offset(f, p->K), p->F(p->G_out), V0, f, p->K,
                     p->st, p->cfg.math));
   for (int k = 0; k < NUP; ++k) {  // dec1 <- up1 <- dec2 ... <- up4
     const int bi = 8 - k, ui = 3 - k;
@@ -481,28 +438,28 @@ int backward(spff_unet3d* p, const float* dl) {
     UUp& U = p->up[ui];
     const int C = d.C, lvl = d.lvl;
     Dst2 dx{p->F(p->G_dx), p->F(p->dskip[lvl]), C, C, C};
-    UCK(bwd_block(p, d, p->F(p->G_out), &dx,
+    PLAN_CK(bwd_block(p, d, p->F(p->G_out), &dx,
                   Src2{p->F(U.out), p->F(B[lvl].out), C, C, C}));
     const Vol& low = p->vol[U.lvl_low];
-    UHIPCK(upconv_wgrad(p->F(B[bi - 1].out), p->F(p->G_dx), C, p->DP(U.w), p->DP(U.b), low, U.Cin,
+    PLAN_HIPCK(upconv_wgrad(p->F(B[bi - 1].out), p->F(p->G_dx), C, p->DP(U.w), p->DP(U.b), low, U.Cin,
                         U.Cout, p->F(p->wg_ws), p->st, NSUB, p->cfg.math));
     float* pk = p->F(U.pk);
-    UHIPCK(upconv_dgrad(p->F(p->G_dx), C, pk + upconv_pack_dgrad_offset(U.Cin, U.Cout, NSUB),
+    PLAN_HIPCK(upconv_dgrad(p->F(p->G_dx), C, pk + upconv_pack_dgrad_offset(U.Cin, U.Cout, NSUB),
                         p->F(p->G_out), low, U.Cin, U.Cout, p->st, NSUB, p->cfg.math));
   }
   {
     Dst2 dx = dst1(p->F(p->G_dx), 8 * f);
-    UCK(bwd_block(p, B[4], p->F(p->G_out), &dx, src1(p->F(p->pool[3]), 8 * f)));
+    PLAN_CK(bwd_block(p, B[4], p->F(p->G_out), &dx, src1(p->F(p->pool[3]), 8 * f)));
   }
   for (int l = 3; l >= 0; --l) {
     const int C = f << l;
-    UHIPCK(maxpool3_bwd_add(p->F(p->G_dx), reinterpret_cast<const uint8_t*>(p->ws + p->pidx[l]),
+    PLAN_HIPCK(maxpool3_bwd_add(p->F(p->G_dx), reinterpret_cast<const uint8_t*>(p->ws + p->pidx[l]),
                             p->F(p->dskip[l]), C, p->F(p->dskip[l]), p->vol[l], C, p->st));
     if (l > 0) {
       Dst2 dx = dst1(p->F(p->G_dx), C / 2);
-      UCK(bwd_block(p, B[l], p->F(p->dskip[l]), &dx, src1(p->F(p->pool[l - 1]), C / 2)));
+      PLAN_CK(bwd_block(p, B[l], p->F(p->dskip[l]), &dx, src1(p->F(p->pool[l - 1]), C / 2)));
     } else {
-      UCK(bwd_block(p, B[0], p->F(p->dskip[0]), nullptr, src1(p->F(p->x_cl), p->ldx)));
+      PLAN_CK(bwd_block(p, B[0], p->F(p->dskip[0]), nullptr, src1(p->F(p->x_cl), p->ldx)));
     }
   }
   return SPFF_OK;
@@ -514,16 +471,7 @@ int backward(spff_unet3d* p, const float* dl) {
 extern "C" {
 
 int spff_unet3d_create(const spff_unet3d_cfg* cfg, spff_unet3d** out) {
-  if (!cfg || !out) return ufail(SPFF_EINVAL, "null argument");
-  spff_unet3d* p = new spff_unet3d();
-  p->cfg = *cfg;
-  const int r = build(p);
-  if (r != SPFF_OK) {
-    delete p;
-    return r;
-  }
-  *out = p;
-  return SPFF_OK;
+  return plan_create(cfg, out, build);
 }
 
 void spff_unet3d_destroy(spff_unet3d* p) { delete p; }
@@ -532,15 +480,8 @@ int spff_unet3d_num_params(const spff_unet3d* p) { return p ? (int)p->params.siz
 
 int spff_unet3d_param_info(const spff_unet3d* p, int i, const char** name, int* ndim,
                            int64_t shape[5], int64_t* offset, int64_t* numel) {
-  if (!p || i < 0 || i >= (int)p->params.size()) return ufail(SPFF_EINVAL, "param index");
-  const UEnt& e = p->params[i];
-  if (name) *name = e.name.c_str();
-  if (ndim) *ndim = (int)e.shape.size();
-  if (shape)
-    for (int k = 0; k < 5; ++k) shape[k] = k < (int)e.shape.size() ? e.shape[k] : 1;
-  if (offset) *offset = e.off;
-  if (numel) *numel = e.numel;
-  return SPFF_OK;
+  if (!p) return plan_fail(SPFF_EINVAL, "param index");
+  return plan_param_info(p->params, i, name, ndim, shape, offset, numel);
 }
 
 int64_t spff_unet3d_param_floats(const spff_unet3d* p) { return p ? p->nparam : 0; }
@@ -548,12 +489,8 @@ int spff_unet3d_num_buffers(const spff_unet3d* p) { return p ? (int)p->bufs.size
 
 int spff_unet3d_buffer_info(const spff_unet3d* p, int i, const char** name, int64_t* offset,
                             int64_t* numel) {
-  if (!p || i < 0 || i >= (int)p->bufs.size()) return ufail(SPFF_EINVAL, "buffer index");
-  const UEnt& e = p->bufs[i];
-  if (name) *name = e.name.c_str();
-  if (offset) *offset = e.off;
-  if (numel) *numel = e.numel;
-  return SPFF_OK;
+  if (!p) return plan_fail(SPFF_EINVAL, "buffer index");
+  return plan_param_info(p->bufs, i, name, nullptr, nullptr, offset, numel, "buffer index");
 }
 
 int64_t spff_unet3d_buffer_floats(const spff_unet3d* p) { return p ? p->nbuf : 0; }
@@ -561,25 +498,22 @@ size_t spff_unet3d_workspace_bytes(const spff_unet3d* p) { return p ? p->total :
 
 int spff_unet3d_forward(spff_unet3d* p, const float* x, const float* params, float* buffers,
                         int training, float* logits, void* ws, void* stream) {
-  if (!p || !x || !params || !buffers || !logits || !ws) return ufail(SPFF_EINVAL, "null argument");
-  p->ws = static_cast<char*>(ws);
-  p->prm = params;
-  p->dprm = nullptr;
+  if (!p || !x || !params || !buffers || !logits || !ws) return plan_fail(SPFF_EINVAL, "null argument");
+  p->bind(ws, params, nullptr, stream);
   p->buf = buffers;
-  p->st = static_cast<hipStream_t>(stream);
   p->co.failed = nullptr;
   const int rc = forward(p, x, logits, training != 0);
-  if (p->co.failed) return ufail(SPFF_ECOLL, std::string("SyncBN ") + p->co.failed + " failed");
+  if (p->co.failed) return plan_fail(SPFF_ECOLL, std::string("SyncBN ") + p->co.failed + " failed");
   return rc;
 }
 
 int spff_unet3d_set_sync_bn(spff_unet3d* p, const spff_coll* coll, int world) {
-  if (!p) return ufail(SPFF_EINVAL, "null plan");
+  if (!p) return plan_fail(SPFF_EINVAL, "null plan");
   if (!coll || world <= 1) {
     p->co = Coll{};
     return SPFF_OK;
   }
-  if (!coll->allreduce) return ufail(SPFF_EINVAL, "spff_coll needs allreduce");
+  if (!coll->allreduce) return plan_fail(SPFF_EINVAL, "spff_coll needs allreduce");
   p->co = Coll{};
   p->co.world = world;
   p->co.ctx = coll->ctx;
@@ -590,28 +524,19 @@ int spff_unet3d_set_sync_bn(spff_unet3d* p, const spff_coll* coll, int world) {
 
 int spff_unet3d_backward(spff_unet3d* p, const float* dlogits, const float* params,
                          float* dparams, void* ws, void* stream) {
-  if (!p || !dlogits || !params || !dparams || !ws) return ufail(SPFF_EINVAL, "null argument");
-  p->ws = static_cast<char*>(ws);
-  p->prm = params;
-  p->dprm = dparams;
-  p->st = static_cast<hipStream_t>(stream);
+  if (!p || !dlogits || !params || !dparams || !ws) return plan_fail(SPFF_EINVAL, "null argument");
+  p->bind(ws, params, dparams, stream);
   p->co.failed = nullptr;
   const int rc = backward(p, dlogits);
-  if (p->co.failed) return ufail(SPFF_ECOLL, std::string("SyncBN ") + p->co.failed + " failed");
+  if (p->co.failed) return plan_fail(SPFF_ECOLL, std::string("SyncBN ") + p->co.failed + " failed");
   return rc;
 }
 
 int spff_unet3d_saved_tensor(const spff_unet3d* p, void* ws, const char* name, const float** ptr,
                              int64_t* nv, int* ch) {
-  if (!p || !ws || !name || !ptr) return ufail(SPFF_EINVAL, "null argument");
-  const char* base = static_cast<const char*>(ws);
+  if (!p || !ws || !name || !ptr) return plan_fail(SPFF_EINVAL, "null argument");
   const std::string n(name);
-  auto ret = [&](size_t off, const Vol& v, int c) {
-    *ptr = reinterpret_cast<const float*>(base + off);
-    if (nv) *nv = nvox(v);
-    if (ch) *ch = c;
-    return SPFF_OK;
-  };
+  const SavedOut ret{ws, ptr, nv, ch};
   if (n == "x_cl") return ret(p->x_cl, p->vol[0], p->ldx);
   for (int i = 0; i < NBLK; ++i) {
     const UBlk& b = p->blk[i];
@@ -626,7 +551,7 @@ int spff_unet3d_saved_tensor(const spff_unet3d* p, void* ws, const char* name, c
   const char* upn[NUP] = {"up4", "up3", "up2", "up1"};
   for (int u = 0; u < NUP; ++u)
     if (n == upn[u]) return ret(p->up[u].out, p->vol[p->up[u].lvl_low - 1], p->up[u].Cout);
-  return ufail(SPFF_EINVAL, "unknown saved tensor " + n);
+  return plan_fail(SPFF_EINVAL, "unknown saved tensor " + n);
 }
 
 int spff_loss_ex(const float* logits, const int64_t* labels, int64_t nv, int K, int ignore,
@@ -634,10 +559,10 @@ int spff_loss_ex(const float* logits, const int64_t* labels, int64_t nv, int K, 
                  int clamp_denominator, float* out4, float* dlogits, int64_t* conf, void* ws,
                  void* stream) {
   if (!logits || !labels || !out4 || !dlogits || !conf || !ws)
-    return ufail(SPFF_EINVAL, "null argument");
+    return plan_fail(SPFF_EINVAL, "null argument");
   if (K < 1 || K > SPFF_MAX_CLASSES)
-    return ufail(SPFF_EINVAL, "num_classes must be 1..SPFF_MAX_CLASSES");
-  UHIPCK(loss_fwd(logits, labels, nv, K, ignore, smooth, count_override, out4, dlogits, conf,
+    return plan_fail(SPFF_EINVAL, "num_classes must be 1..SPFF_MAX_CLASSES");
+  PLAN_HIPCK(loss_fwd(logits, labels, nv, K, ignore, smooth, count_override, out4, dlogits, conf,
                   static_cast<float*>(ws), static_cast<hipStream_t>(stream), class_weights,
                   clamp_denominator));
   return SPFF_OK;

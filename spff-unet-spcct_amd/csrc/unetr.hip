@@ -39,15 +39,13 @@ struct Blk {
 
 }  // namespace
 
-struct spff_unetr {
+struct spff_unetr : PlanBase {
   static constexpr int kNRB = NRB;
   spff_unetr_cfg cfg;
   Vol vol[NLV];
   int f, K, ldx, hid, mlp, nh, n;  // n: tokens per sample
   bool resample = false;
   VitGeo geo;
-  std::vector<SEnt> params;
-  int64_t nparam = 0;
   int64_t pos = -1, nfw = -1, nfb = -1;
   Lin pe;
   Blk blk[NBLK];
@@ -64,28 +62,7 @@ struct spff_unetr {
   size_t G_out = 0, G_dz = 0, G_dy2 = 0, G_da1 = 0, G_up = 0;
   size_t d_enc[4] = {}, d_tap[3] = {}, d_hN = 0, d_lg = 0;
   size_t S_a = 0, S_b = 0, S_c = 0, S_qkv = 0, S_h = 0;
-  size_t total = 0;
   int maxC = 0;
-  char* ws = nullptr;
-  const float* prm = nullptr;
-  float* dprm = nullptr;
-  hipStream_t st = nullptr;
-
-  float* F(size_t off) const { return reinterpret_cast<float*>(ws + off); }
-  const float* P(int64_t off) const { return off < 0 ? nullptr : prm + off; }
-  float* DP(int64_t off) const { return off < 0 ? nullptr : dprm + off; }
-  size_t alloc(size_t bytes) {
-    size_t o = total;
-    total += (bytes + 255) / 256 * 256;
-    return o;
-  }
-  int64_t reg(const std::string& name, std::vector<int64_t> shape) {
-    int64_t c = 1;
-    for (auto s : shape) c *= s;
-    params.push_back(SEnt{name, shape, nparam, c});
-    nparam += c;
-    return nparam - c;
-  }
 };
 
 namespace {
@@ -100,25 +77,25 @@ void reg_up(spff_unetr* p, Up& U, const std::string& name, int Cin, int Cout, in
 int build(spff_unetr* p) {
   const spff_unetr_cfg& c = p->cfg;
   if (c.batch < 1 || c.in_ch != 1 || c.num_classes < 1 || c.num_classes > 32)
-    return sfail(SPFF_EINVAL, "invalid batch / in_ch (1: the registry's) / num_classes (1..32)");
+    return plan_fail(SPFF_EINVAL, "invalid batch / in_ch (1: the registry's) / num_classes (1..32)");
   if (c.depth < 16 || c.height < 16 || c.width < 16 || c.depth % 16 || c.height % 16 ||
       c.width % 16)
-    return sfail(SPFF_EINVAL, "UNETR: the padded input's D, H, W must be multiples of 16 "
+    return plan_fail(SPFF_EINVAL, "UNETR: the padded input's D, H, W must be multiples of 16 "
                               "(LitUNETR_Published pads to a multiple of 16)");
   for (int k = 0; k < 3; ++k)
     if (c.img[k] < 16 || c.img[k] % 16)
-      return sfail(SPFF_EINVAL, "UNETR: img must be multiples of the 16^3 patch");
+      return plan_fail(SPFF_EINVAL, "UNETR: img must be multiples of the 16^3 patch");
   if (c.feature_size < 8 || c.feature_size % 8)
-    return sfail(SPFF_EINVAL, "feature_size must be a positive multiple of 8");
+    return plan_fail(SPFF_EINVAL, "feature_size must be a positive multiple of 8");
   if (c.hidden < 16 || c.hidden > 768 || c.heads < 1 || c.hidden % c.heads)
-    return sfail(SPFF_EINVAL, "UNETR: hidden (<= 768) must be a multiple of heads");
-  if (c.mlp_dim < 4 || c.mlp_dim % 4) return sfail(SPFF_EINVAL, "mlp_dim must be a multiple of 4");
+    return plan_fail(SPFF_EINVAL, "UNETR: hidden (<= 768) must be a multiple of heads");
+  if (c.mlp_dim < 4 || c.mlp_dim % 4) return plan_fail(SPFF_EINVAL, "mlp_dim must be a multiple of 4");
   if (c.math < SPFF_MATH_F32 || c.math > SPFF_MATH_F16X3)
-    return sfail(SPFF_EINVAL, "math must be one of SPFF_MATH_*");
+    return plan_fail(SPFF_EINVAL, "math must be one of SPFF_MATH_*");
   const int B = c.batch;
   for (int l = 0; l < NLV; ++l) p->vol[l] = Vol{B, c.img[0] >> l, c.img[1] >> l, c.img[2] >> l};
   p->n = p->vol[4].D * p->vol[4].H * p->vol[4].W;
-  if (const char* m = vit_geo_check(B, p->n, c.hidden, c.heads)) return sfail(SPFF_EINVAL, m);
+  if (const char* m = vit_geo_check(B, p->n, c.hidden, c.heads)) return plan_fail(SPFF_EINVAL, m);
   p->geo = vit_geo(B, p->n, c.hidden, c.heads);
   p->resample = c.depth != c.img[0] || c.height != c.img[1] || c.width != c.img[2];
   p->f = c.feature_size;
@@ -285,7 +262,7 @@ int build(spff_unetr* p) {
 
 int pack_lin(spff_unetr* p, const Lin& l) {
   float* pk = p->F(l.pk);
-  SHIPCK(head_pack(p->P(l.w), pk, pk + head_pack_dgrad_offset(l.K, l.N), l.K, l.N, p->st));
+  PLAN_HIPCK(head_pack(p->P(l.w), pk, pk + head_pack_dgrad_offset(l.K, l.N), l.K, l.N, p->st));
   return SPFF_OK;
 }
 const float* wd_of(spff_unetr* p, const Lin& l) {
@@ -294,18 +271,18 @@ const float* wd_of(spff_unetr* p, const Lin& l) {
 
 int up_fwd(spff_unetr* p, Up& U, const float* x) {
   float* upk = p->F(U.pk);
-  SHIPCK(upconv_pack(p->P(U.w), upk, upk + upconv_pack_dgrad_offset(U.Cin, U.Cout, 8), U.Cin,
+  PLAN_HIPCK(upconv_pack(p->P(U.w), upk, upk + upconv_pack_dgrad_offset(U.Cin, U.Cout, 8), U.Cin,
                      U.Cout, p->st, 8));
-  SHIPCK(upconv_fwd(x, upk, p->F(p->zeros), p->F(U.out), p->vol[U.Llow], U.Cin, U.Cout, p->st, 8));
+  PLAN_HIPCK(upconv_fwd(x, upk, p->F(p->zeros), p->F(U.out), p->vol[U.Llow], U.Cin, U.Cout, p->st, 8));
   return SPFF_OK;
 }
 // dout [high][Cout] -> the weight gradient and (dx non-null) dx [low][Cin], written
 int up_bwd(spff_unetr* p, Up& U, const float* x, const float* dout, float* dx) {
-  SHIPCK(upconv_wgrad(x, dout, U.Cout, p->DP(U.w), p->F(p->dummy), p->vol[U.Llow], U.Cin, U.Cout,
+  PLAN_HIPCK(upconv_wgrad(x, dout, U.Cout, p->DP(U.w), p->F(p->dummy), p->vol[U.Llow], U.Cin, U.Cout,
                       p->F(p->wg_ws), p->st, 8));
   if (dx) {
     const float* wd = p->F(U.pk) + upconv_pack_dgrad_offset(U.Cin, U.Cout, 8);
-    SHIPCK(upconv_dgrad(dout, U.Cout, wd, dx, p->vol[U.Llow], U.Cin, U.Cout, p->st, 8));
+    PLAN_HIPCK(upconv_dgrad(dout, U.Cout, wd, dx, p->vol[U.Llow], U.Cin, U.Cout, p->st, 8));
   }
   return SPFF_OK;
 }
@@ -314,22 +291,22 @@ int block_fwd(spff_unetr* p, Blk& b, const float* tin) {
   const int64_t T = (int64_t)p->cfg.batch * p->n;
   const int C = p->hid, M = p->mlp;
   hipStream_t st = p->st;
-  SHIPCK(ln_fwd(tin, C, C, p->P(b.n1w), p->P(b.n1b), p->F(b.n1), C, p->F(b.mu1), p->F(b.rs1), T,
+  PLAN_HIPCK(ln_fwd(tin, C, C, p->P(b.n1w), p->P(b.n1b), p->F(b.n1), C, p->F(b.mu1), p->F(b.rs1), T,
                 st));
-  SCK(pack_lin(p, b.qkv));
-  SHIPCK(linear_fwd(p->F(b.n1), C, C, p->F(b.qkv.pk), nullptr, p->F(b.qkvb), 3 * C, 3 * C, T,
+  PLAN_CK(pack_lin(p, b.qkv));
+  PLAN_HIPCK(linear_fwd(p->F(b.n1), C, C, p->F(b.qkv.pk), nullptr, p->F(b.qkvb), 3 * C, 3 * C, T,
                     nullptr, 0, st));
-  SHIPCK(vit_attn_fwd(p->F(b.qkvb), p->geo, p->F(b.O), p->F(b.lse), st));
-  SCK(pack_lin(p, b.proj));
-  SHIPCK(linear_fwd(p->F(b.O), C, C, p->F(b.proj.pk), p->P(b.proj.b), p->F(b.x1), C, C, T, tin, C,
+  PLAN_HIPCK(vit_attn_fwd(p->F(b.qkvb), p->geo, p->F(b.O), p->F(b.lse), st));
+  PLAN_CK(pack_lin(p, b.proj));
+  PLAN_HIPCK(linear_fwd(p->F(b.O), C, C, p->F(b.proj.pk), p->P(b.proj.b), p->F(b.x1), C, C, T, tin, C,
                     st));
-  SHIPCK(ln_fwd(p->F(b.x1), C, C, p->P(b.n2w), p->P(b.n2b), p->F(b.n2), C, p->F(b.mu2),
+  PLAN_HIPCK(ln_fwd(p->F(b.x1), C, C, p->P(b.n2w), p->P(b.n2b), p->F(b.n2), C, p->F(b.mu2),
                 p->F(b.rs2), T, st));
-  SCK(pack_lin(p, b.l1));
-  SHIPCK(linear_fwd_gelu(p->F(b.n2), C, C, p->F(b.l1.pk), p->P(b.l1.b), p->F(b.hpre), p->F(b.hact),
+  PLAN_CK(pack_lin(p, b.l1));
+  PLAN_HIPCK(linear_fwd_gelu(p->F(b.n2), C, C, p->F(b.l1.pk), p->P(b.l1.b), p->F(b.hpre), p->F(b.hact),
                          M, T, st));
-  SCK(pack_lin(p, b.l2));
-  SHIPCK(linear_fwd(p->F(b.hact), M, M, p->F(b.l2.pk), p->P(b.l2.b), p->F(b.x2), C, C, T,
+  PLAN_CK(pack_lin(p, b.l2));
+  PLAN_HIPCK(linear_fwd(p->F(b.hact), M, M, p->F(b.l2.pk), p->P(b.l2.b), p->F(b.x2), C, C, T,
                     p->F(b.x1), C, st));
   return SPFF_OK;
 }
@@ -345,22 +322,22 @@ int block_bwd(spff_unetr* p, Blk& b, const float* tin, float* A, float* dtin) {
   float* dh = p->F(p->S_h);
   float* dq = p->F(p->S_qkv);
   // MLP: x2 = x1 + L2(gelu(L1(LN2(x1))))
-  SHIPCK(linear_wgrad(p->F(b.hact), M, M, A, C, C, p->DP(b.l2.w), p->DP(b.l2.b), T, wg, st));
-  SHIPCK(linear_dgrad(A, C, C, wd_of(p, b.l2), dh, M, M, T, p->F(b.hpre), st));
-  SHIPCK(linear_wgrad(p->F(b.n2), C, C, dh, M, M, p->DP(b.l1.w), p->DP(b.l1.b), T, wg, st));
-  SHIPCK(linear_dgrad(dh, M, M, wd_of(p, b.l1), Bf, C, C, T, nullptr, st));  // Bf = d n2
+  PLAN_HIPCK(linear_wgrad(p->F(b.hact), M, M, A, C, C, p->DP(b.l2.w), p->DP(b.l2.b), T, wg, st));
+  PLAN_HIPCK(linear_dgrad(A, C, C, wd_of(p, b.l2), dh, M, M, T, p->F(b.hpre), st));
+  PLAN_HIPCK(linear_wgrad(p->F(b.n2), C, C, dh, M, M, p->DP(b.l1.w), p->DP(b.l1.b), T, wg, st));
+  PLAN_HIPCK(linear_dgrad(dh, M, M, wd_of(p, b.l1), Bf, C, C, T, nullptr, st));  // Bf = d n2
   // d x1 = d x2 + LN2'(d n2)  (into Cf)
-  SHIPCK(ln_bwd(p->F(b.x1), C, C, p->P(b.n2w), p->F(b.mu2), p->F(b.rs2), Bf, C, Cf, C, A, C,
+  PLAN_HIPCK(ln_bwd(p->F(b.x1), C, C, p->P(b.n2w), p->F(b.mu2), p->F(b.rs2), Bf, C, Cf, C, A, C,
                 p->DP(b.n2w), wg, T, st));
   // attention: x1 = t + OutProj(O)
-  SHIPCK(linear_wgrad(p->F(b.O), C, C, Cf, C, C, p->DP(b.proj.w), p->DP(b.proj.b), T, wg, st));
-  SHIPCK(linear_dgrad(Cf, C, C, wd_of(p, b.proj), A, C, C, T, nullptr, st));  // A = dO
-  SHIPCK(vit_attn_bwd(p->F(b.qkvb), p->F(b.O), A, p->F(b.lse), p->geo, dq, wg, st));
-  SHIPCK(linear_dgrad(dq, 3 * C, 3 * C, wd_of(p, b.qkv), Bf, C, C, T, nullptr, st));  // d n1
-  SHIPCK(linear_wgrad(p->F(b.n1), C, C, dq, 3 * C, 3 * C, p->DP(b.qkv.w), p->F(p->dummy), T, wg,
+  PLAN_HIPCK(linear_wgrad(p->F(b.O), C, C, Cf, C, C, p->DP(b.proj.w), p->DP(b.proj.b), T, wg, st));
+  PLAN_HIPCK(linear_dgrad(Cf, C, C, wd_of(p, b.proj), A, C, C, T, nullptr, st));  // A = dO
+  PLAN_HIPCK(vit_attn_bwd(p->F(b.qkvb), p->F(b.O), A, p->F(b.lse), p->geo, dq, wg, st));
+  PLAN_HIPCK(linear_dgrad(dq, 3 * C, 3 * C, wd_of(p, b.qkv), Bf, C, C, T, nullptr, st));  // d n1
+  PLAN_HIPCK(linear_wgrad(p->F(b.n1), C, C, dq, 3 * C, 3 * C, p->DP(b.qkv.w), p->F(p->dummy), T, wg,
                       st));
   // d t = d x1 + LN1'(d n1)
-  SHIPCK(ln_bwd(tin, C, C, p->P(b.n1w), p->F(b.mu1), p->F(b.rs1), Bf, C, dtin, C, Cf, C,
+  PLAN_HIPCK(ln_bwd(tin, C, C, p->P(b.n1w), p->F(b.mu1), p->F(b.rs1), Bf, C, dtin, C, Cf, C,
                 p->DP(b.n1w), wg, T, st));
   return SPFF_OK;
 }
@@ -373,60 +350,60 @@ int forward(spff_unetr* p, const float* x, float* logits) {
   const Vol& v0 = p->vol[0];
   const int64_t T = (int64_t)B * n;
   hipStream_t st = p->st;
-  SHIPCK(spff::fill32_async(p->F(p->ones), (size_t)p->maxC * 4, 0x3f800000u, st));
-  SHIPCK(spff::zero_async(p->F(p->zeros), fbytes(p->maxC), st));
+  PLAN_HIPCK(spff::fill32_async(p->F(p->ones), (size_t)p->maxC * 4, 0x3f800000u, st));
+  PLAN_HIPCK(spff::zero_async(p->F(p->zeros), fbytes(p->maxC), st));
   if (p->resample) {
     CProf pr(PROF_RESAMPLE, 0.0, st);
-    SHIPCK(resize3d_ncdhw_in(x, p->F(p->x_cl), p->ldx, B, c.in_ch, c.depth, c.height, c.width,
+    PLAN_HIPCK(resize3d_ncdhw_in(x, p->F(p->x_cl), p->ldx, B, c.in_ch, c.depth, c.height, c.width,
                              v0.D, v0.H, v0.W, st));
     pr.end(st);
   } else {
-    SHIPCK(ncdhw_to_ndhwc(x, p->F(p->x_cl), v0, c.in_ch, p->ldx, st));
+    PLAN_HIPCK(ncdhw_to_ndhwc(x, p->F(p->x_cl), v0, c.in_ch, p->ldx, st));
   }
   CProf pv(PROF_VIT, 0.0, st);
   // patch embedding: rows of 16^3 patches through the Linear GEMM, + bias + position
   const int pk = p->pe.K;
-  SHIPCK(patchify16(p->F(p->x_cl), p->ldx, c.in_ch, B, v0.D, v0.H, v0.W, p->F(p->rows), st));
-  SCK(pack_lin(p, p->pe));
+  PLAN_HIPCK(patchify16(p->F(p->x_cl), p->ldx, c.in_ch, B, v0.D, v0.H, v0.W, p->F(p->rows), st));
+  PLAN_CK(pack_lin(p, p->pe));
   for (int b = 0; b < B; ++b)
-    SHIPCK(linear_fwd(p->F(p->rows) + (int64_t)b * n * pk, pk, pk, p->F(p->pe.pk), p->P(p->pe.b),
+    PLAN_HIPCK(linear_fwd(p->F(p->rows) + (int64_t)b * n * pk, pk, pk, p->F(p->pe.pk), p->P(p->pe.b),
                       p->F(p->tok) + (int64_t)b * n * Hd, Hd, Hd, n, p->P(p->pos), Hd, st));
-  for (int i = 0; i < NBLK; ++i) SCK(block_fwd(p, p->blk[i], block_in(p, i)));
-  SHIPCK(ln_fwd(p->F(p->blk[NBLK - 1].x2), Hd, Hd, p->P(p->nfw), p->P(p->nfb), p->F(p->hN), Hd,
+  for (int i = 0; i < NBLK; ++i) PLAN_CK(block_fwd(p, p->blk[i], block_in(p, i)));
+  PLAN_HIPCK(ln_fwd(p->F(p->blk[NBLK - 1].x2), Hd, Hd, p->P(p->nfw), p->P(p->nfb), p->F(p->hN), Hd,
                 p->F(p->nmu), p->F(p->nrs), T, st));
   pv.end(st);
-  SCK(prep_weights(p));
+  PLAN_CK(prep_weights(p));
   RB* R = p->rb;
   Up* U = p->up;
-  SCK(rb_fwd(p, R[0], src1(p->F(p->x_cl), p->ldx), nullptr));
+  PLAN_CK(rb_fwd(p, R[0], src1(p->F(p->x_cl), p->ldx), nullptr));
   // encoder2: hs[3] -> T -> (T, RB) -> (T, RB)
-  SCK(up_fwd(p, U[0], p->F(p->blk[3].x2)));
-  SCK(up_fwd(p, U[1], p->F(U[0].out)));
-  SCK(rb_fwd(p, R[1], src1(p->F(U[1].out), 2 * f), p->F(U[1].out)));
-  SCK(up_fwd(p, U[2], p->F(R[1].out)));
-  SCK(rb_fwd(p, R[2], src1(p->F(U[2].out), 2 * f), p->F(U[2].out)));
+  PLAN_CK(up_fwd(p, U[0], p->F(p->blk[3].x2)));
+  PLAN_CK(up_fwd(p, U[1], p->F(U[0].out)));
+  PLAN_CK(rb_fwd(p, R[1], src1(p->F(U[1].out), 2 * f), p->F(U[1].out)));
+  PLAN_CK(up_fwd(p, U[2], p->F(R[1].out)));
+  PLAN_CK(rb_fwd(p, R[2], src1(p->F(U[2].out), 2 * f), p->F(U[2].out)));
   // encoder3: hs[6] -> T -> (T, RB)
-  SCK(up_fwd(p, U[3], p->F(p->blk[6].x2)));
-  SCK(up_fwd(p, U[4], p->F(U[3].out)));
-  SCK(rb_fwd(p, R[3], src1(p->F(U[4].out), 4 * f), p->F(U[4].out)));
+  PLAN_CK(up_fwd(p, U[3], p->F(p->blk[6].x2)));
+  PLAN_CK(up_fwd(p, U[4], p->F(U[3].out)));
+  PLAN_CK(rb_fwd(p, R[3], src1(p->F(U[4].out), 4 * f), p->F(U[4].out)));
   // encoder4: hs[9] -> T
-  SCK(up_fwd(p, U[5], p->F(p->blk[9].x2)));
+  PLAN_CK(up_fwd(p, U[5], p->F(p->blk[9].x2)));
   const float* prev = p->F(p->hN);
   const float* skip[4] = {p->F(U[5].out), p->F(R[3].out), p->F(R[2].out), p->F(R[0].out)};
   for (int u = 0; u < 4; ++u) {
     Up& X = U[6 + u];
-    SCK(up_fwd(p, X, prev));
+    PLAN_CK(up_fwd(p, X, prev));
     RB& r = R[4 + u];
-    SCK(rb_fwd(p, r, Src2{p->F(X.out), skip[u], X.Cout, X.Cout, X.Cout}, nullptr));
+    PLAN_CK(rb_fwd(p, r, Src2{p->F(X.out), skip[u], X.Cout, X.Cout, X.Cout}, nullptr));
     prev = p->F(r.out);
   }
-  SCK(pack_lin(p, p->head));
+  PLAN_CK(pack_lin(p, p->head));
   float* net = p->resample ? p->F(p->lg) : logits;
-  SHIPCK(linear_fwd(prev, f, f, p->F(p->head.pk), p->P(p->head.b), net, p->K, p->K, nvox(v0),
+  PLAN_HIPCK(linear_fwd(prev, f, f, p->F(p->head.pk), p->P(p->head.b), net, p->K, p->K, nvox(v0),
                     nullptr, 0, st));
   if (p->resample) {
     CProf pr(PROF_RESAMPLE, 0.0, st);
-    SHIPCK(resize3d_fwd(net, logits, B, p->K, v0.D, v0.H, v0.W, c.depth, c.height, c.width, st));
+    PLAN_HIPCK(resize3d_fwd(net, logits, B, p->K, v0.D, v0.H, v0.W, c.depth, c.height, c.width, st));
     pr.end(st);
   }
   return SPFF_OK;
@@ -445,14 +422,14 @@ int backward(spff_unetr* p, const float* dl) {
   float* dup = p->F(p->G_up);
   if (p->resample) {
     CProf pr(PROF_RESAMPLE, 0.0, st);
-    SHIPCK(resize3d_bwd(dl, p->F(p->d_lg), B, p->K, v0.D, v0.H, v0.W, c.depth, c.height, c.width,
+    PLAN_HIPCK(resize3d_bwd(dl, p->F(p->d_lg), B, p->K, v0.D, v0.H, v0.W, c.depth, c.height, c.width,
                         st));
     pr.end(st);
     dl = p->F(p->d_lg);
   }
-  SHIPCK(linear_wgrad(p->F(R[7].out), f, f, dl, p->K, p->K, p->DP(p->head.w), p->DP(p->head.b),
+  PLAN_HIPCK(linear_wgrad(p->F(R[7].out), f, f, dl, p->K, p->K, p->DP(p->head.w), p->DP(p->head.b),
                       nvox(v0), wg, st));
-  SHIPCK(linear_dgrad(dl, p->K, p->K, wd_of(p, p->head), Gout, f, f, nvox(v0), nullptr, st));
+  PLAN_HIPCK(linear_dgrad(dl, p->K, p->K, wd_of(p, p->head), Gout, f, f, nvox(v0), nullptr, st));
   // decoders: dec2 (R7) <- up <- dec3 (R6) <- up <- dec4 (R5) <- up <- dec5 (R4) <- up <- hN
   float* dskip[4] = {p->F(p->d_enc[3]), p->F(p->d_enc[2]), p->F(p->d_enc[1]), p->F(p->d_enc[0])};
   const float* skip[4] = {p->F(U[5].out), p->F(R[3].out), p->F(R[2].out), p->F(R[0].out)};
@@ -460,47 +437,47 @@ int backward(spff_unetr* p, const float* dl) {
     Up& X = U[6 + u];
     RB& r = R[4 + u];
     Dst2 dx{dup, dskip[u], X.Cout, X.Cout, X.Cout};
-    SCK(rb_bwd(p, r, Gout, Src2{p->F(X.out), skip[u], X.Cout, X.Cout, X.Cout}, nullptr, &dx));
+    PLAN_CK(rb_bwd(p, r, Gout, Src2{p->F(X.out), skip[u], X.Cout, X.Cout, X.Cout}, nullptr, &dx));
     const float* xlow = u == 0 ? p->F(p->hN) : p->F(R[4 + u - 1].out);
-    SCK(up_bwd(p, X, xlow, dup, u == 0 ? p->F(p->d_hN) : Gout));
+    PLAN_CK(up_bwd(p, X, xlow, dup, u == 0 ? p->F(p->d_hN) : Gout));
   }
   // encoder4: d enc4 -> d hs[9]
-  SCK(up_bwd(p, U[5], p->F(p->blk[9].x2), p->F(p->d_enc[3]), p->F(p->d_tap[2])));
+  PLAN_CK(up_bwd(p, U[5], p->F(p->blk[9].x2), p->F(p->d_enc[3]), p->F(p->d_tap[2])));
   // encoder3: d enc3 -> RB -> T -> T -> d hs[6]
   {
     Dst2 dx = dst1(dup, 4 * f);
-    SCK(rb_bwd(p, R[3], p->F(p->d_enc[2]), src1(p->F(U[4].out), 4 * f), p->F(U[4].out), &dx));
-    SCK(up_bwd(p, U[4], p->F(U[3].out), dup, Gout));
-    SCK(up_bwd(p, U[3], p->F(p->blk[6].x2), Gout, p->F(p->d_tap[1])));
+    PLAN_CK(rb_bwd(p, R[3], p->F(p->d_enc[2]), src1(p->F(U[4].out), 4 * f), p->F(U[4].out), &dx));
+    PLAN_CK(up_bwd(p, U[4], p->F(U[3].out), dup, Gout));
+    PLAN_CK(up_bwd(p, U[3], p->F(p->blk[6].x2), Gout, p->F(p->d_tap[1])));
   }
   // encoder2: d enc2 -> RB -> T -> RB -> T -> T -> d hs[3]
   {
     Dst2 dx = dst1(dup, 2 * f);
-    SCK(rb_bwd(p, R[2], p->F(p->d_enc[1]), src1(p->F(U[2].out), 2 * f), p->F(U[2].out), &dx));
-    SCK(up_bwd(p, U[2], p->F(R[1].out), dup, Gout));
-    SCK(rb_bwd(p, R[1], Gout, src1(p->F(U[1].out), 2 * f), p->F(U[1].out), &dx));
-    SCK(up_bwd(p, U[1], p->F(U[0].out), dup, Gout));
-    SCK(up_bwd(p, U[0], p->F(p->blk[3].x2), Gout, p->F(p->d_tap[0])));
+    PLAN_CK(rb_bwd(p, R[2], p->F(p->d_enc[1]), src1(p->F(U[2].out), 2 * f), p->F(U[2].out), &dx));
+    PLAN_CK(up_bwd(p, U[2], p->F(R[1].out), dup, Gout));
+    PLAN_CK(rb_bwd(p, R[1], Gout, src1(p->F(U[1].out), 2 * f), p->F(U[1].out), &dx));
+    PLAN_CK(up_bwd(p, U[1], p->F(U[0].out), dup, Gout));
+    PLAN_CK(up_bwd(p, U[0], p->F(p->blk[3].x2), Gout, p->F(p->d_tap[0])));
   }
-  SCK(rb_bwd(p, R[0], p->F(p->d_enc[0]), src1(p->F(p->x_cl), p->ldx), nullptr, nullptr));
+  PLAN_CK(rb_bwd(p, R[0], p->F(p->d_enc[0]), src1(p->F(p->x_cl), p->ldx), nullptr, nullptr));
   // ViT: A = gradient of the residual stream; the taps join at blocks 9, 6, 3
   float* A = p->F(p->S_a);
   CProf pv(PROF_VIT, 0.0, st);
-  SHIPCK(ln_bwd(p->F(p->blk[NBLK - 1].x2), Hd, Hd, p->P(p->nfw), p->F(p->nmu), p->F(p->nrs),
+  PLAN_HIPCK(ln_bwd(p->F(p->blk[NBLK - 1].x2), Hd, Hd, p->P(p->nfw), p->F(p->nmu), p->F(p->nrs),
                 p->F(p->d_hN), Hd, A, Hd, nullptr, 0, p->DP(p->nfw), wg, T, st));
   float* dtin = p->F(p->d_hN);  // free from here on
   for (int i = NBLK - 1; i >= 0; --i) {
-    if (i == 9) SHIPCK(add_inplace(A, p->F(p->d_tap[2]), T * Hd, st));
-    if (i == 6) SHIPCK(add_inplace(A, p->F(p->d_tap[1]), T * Hd, st));
-    if (i == 3) SHIPCK(add_inplace(A, p->F(p->d_tap[0]), T * Hd, st));
-    SCK(block_bwd(p, p->blk[i], block_in(p, i), A, dtin));
+    if (i == 9) PLAN_HIPCK(add_inplace(A, p->F(p->d_tap[2]), T * Hd, st));
+    if (i == 6) PLAN_HIPCK(add_inplace(A, p->F(p->d_tap[1]), T * Hd, st));
+    if (i == 3) PLAN_HIPCK(add_inplace(A, p->F(p->d_tap[0]), T * Hd, st));
+    PLAN_CK(block_bwd(p, p->blk[i], block_in(p, i), A, dtin));
     std::swap(A, dtin);
   }
   // A = d tok: patch-embedding weight / bias, and the position embedding summed over the
   // batch in sample order
-  SHIPCK(linear_wgrad(p->F(p->rows), p->pe.K, p->pe.K, A, Hd, Hd, p->DP(p->pe.w), p->DP(p->pe.b),
+  PLAN_HIPCK(linear_wgrad(p->F(p->rows), p->pe.K, p->pe.K, A, Hd, Hd, p->DP(p->pe.w), p->DP(p->pe.b),
                       T, wg, st));
-  SHIPCK(col_reduce(A, B, (int64_t)n * Hd, n * Hd, p->DP(p->pos), 0, st));
+  PLAN_HIPCK(col_reduce(A, B, (int64_t)n * Hd, n * Hd, p->DP(p->pos), 0, st));
   pv.end(st);
   return SPFF_OK;
 }
@@ -511,16 +488,7 @@ int backward(spff_unetr* p, const float* dl) {
 extern "C" {
 
 int spff_unetr_create(const spff_unetr_cfg* cfg, spff_unetr** out) {
-  if (!cfg || !out) return sfail(SPFF_EINVAL, "null argument");
-  spff_unetr* p = new spff_unetr();
-  p->cfg = *cfg;
-  const int r = build(p);
-  if (r != SPFF_OK) {
-    delete p;
-    return r;
-  }
-  *out = p;
-  return SPFF_OK;
+  return plan_create(cfg, out, build);
 }
 
 void spff_unetr_destroy(spff_unetr* p) { delete p; }
@@ -529,15 +497,8 @@ int spff_unetr_num_params(const spff_unetr* p) { return p ? (int)p->params.size(
 
 int spff_unetr_param_info(const spff_unetr* p, int i, const char** name, int* ndim,
                           int64_t shape[5], int64_t* offset, int64_t* numel) {
-  if (!p || i < 0 || i >= (int)p->params.size()) return sfail(SPFF_EINVAL, "param index");
-  const SEnt& e = p->params[i];
-  if (name) *name = e.name.c_str();
-  if (ndim) *ndim = (int)e.shape.size();
-  if (shape)
-    for (int k = 0; k < 5; ++k) shape[k] = k < (int)e.shape.size() ? e.shape[k] : 1;
-  if (offset) *offset = e.off;
-  if (numel) *numel = e.numel;
-  return SPFF_OK;
+  if (!p) return plan_fail(SPFF_EINVAL, "param index");
+  return plan_param_info(p->params, i, name, ndim, shape, offset, numel);
 }
 
 int64_t spff_unetr_param_floats(const spff_unetr* p) { return p ? p->nparam : 0; }
@@ -545,35 +506,23 @@ size_t spff_unetr_workspace_bytes(const spff_unetr* p) { return p ? p->total : 0
 
 int spff_unetr_forward(spff_unetr* p, const float* x, const float* params, float* logits,
                        void* ws, void* stream) {
-  if (!p || !x || !params || !logits || !ws) return sfail(SPFF_EINVAL, "null argument");
-  p->ws = static_cast<char*>(ws);
-  p->prm = params;
-  p->dprm = nullptr;
-  p->st = static_cast<hipStream_t>(stream);
+  if (!p || !x || !params || !logits || !ws) return plan_fail(SPFF_EINVAL, "null argument");
+  p->bind(ws, params, nullptr, stream);
   return forward(p, x, logits);
 }
 
 int spff_unetr_backward(spff_unetr* p, const float* dlogits, const float* params, float* dparams,
                         void* ws, void* stream) {
-  if (!p || !dlogits || !params || !dparams || !ws) return sfail(SPFF_EINVAL, "null argument");
-  p->ws = static_cast<char*>(ws);
-  p->prm = params;
-  p->dprm = dparams;
-  p->st = static_cast<hipStream_t>(stream);
+  if (!p || !dlogits || !params || !dparams || !ws) return plan_fail(SPFF_EINVAL, "null argument");
+  p->bind(ws, params, dparams, stream);
   return backward(p, dlogits);
 }
 
 int spff_unetr_saved_tensor(const spff_unetr* p, void* ws, const char* name, const float** ptr,
                             int64_t* nv, int* ch) {
-  if (!p || !ws || !name || !ptr) return sfail(SPFF_EINVAL, "null argument");
-  const char* base = static_cast<const char*>(ws);
+  if (!p || !ws || !name || !ptr) return plan_fail(SPFF_EINVAL, "null argument");
   const std::string s(name);
-  auto ret = [&](size_t off, int64_t rows, int c) {
-    *ptr = reinterpret_cast<const float*>(base + off);
-    if (nv) *nv = rows;
-    if (ch) *ch = c;
-    return SPFF_OK;
-  };
+  const SavedOut ret{ws, ptr, nv, ch};
   const int64_t T = (int64_t)p->cfg.batch * p->n;
   if (s == "tok") return ret(p->tok, T, p->hid);
   if (s == "h3") return ret(p->blk[3].x2, T, p->hid);
@@ -608,7 +557,7 @@ int spff_unetr_saved_tensor(const spff_unetr* p, void* ws, const char* name, con
     if (r.has3 && s == r.name + ".y3") return ret(r.y3, V, r.C);
     if (s == r.name + ".out") return rbout(r);
   }
-  return sfail(SPFF_EINVAL, "unknown saved tensor " + s);
+  return plan_fail(SPFF_EINVAL, "unknown saved tensor " + s);
 }
 
 }  // extern "C"

@@ -7,6 +7,7 @@ from __future__ import annotations
 
 import collections
 import ctypes
+import inspect
 import os
 import pathlib
 import threading
@@ -139,21 +140,47 @@ _I = ctypes.c_int
 _L = ctypes.c_int64
 _S = ctypes.c_size_t
 
+_ENTRIES = ("create", "destroy", "num_params", "param_info", "param_floats", "workspace_bytes",
+            "forward", "backward", "saved_tensor")
+
+
+def _entry_names(prefix: str) -> Dict[str, str]:
+    """The symbols of the nine entry points every plan has (include/spff.h)."""
+    return {k: f"{prefix}_{k}" for k in _ENTRIES}
+
+
+# the main plan's symbols predate the per-plan prefixes
+_MAIN_NAMES = {**_entry_names("spff"), "create": "spff_plan_create",
+               "destroy": "spff_plan_destroy"}
+
+
+def _plan_sigs(names: Dict[str, str], cfg) -> Dict[str, tuple]:
+    sigs = {
+        "create": (_I, [ctypes.POINTER(cfg), ctypes.POINTER(_P)]),
+        "destroy": (None, [_P]),
+        "num_params": (_I, [_P]),
+        "param_info": (_I, [_P, _I, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(_I),
+                            ctypes.POINTER(_L), ctypes.POINTER(_L), ctypes.POINTER(_L)]),
+        "param_floats": (_L, [_P]),
+        "workspace_bytes": (_S, [_P]),
+        "forward": (_I, [_P, _P, _P, _P, _P, _P]),
+        "backward": (_I, [_P, _P, _P, _P, _P, _P]),
+        "saved_tensor": (_I, [_P, _P, ctypes.c_char_p, ctypes.POINTER(_P), ctypes.POINTER(_L),
+                              ctypes.POINTER(_I)]),
+    }
+    return {names[k]: sigs[k] for k in _ENTRIES}
+
+
 _SIGS = {
-    "spff_plan_create": (_I, [ctypes.POINTER(spff_cfg), ctypes.POINTER(_P)]),
+    **_plan_sigs(_MAIN_NAMES, spff_cfg),
+    **_plan_sigs(_entry_names("spff_unet3d"), spff_unet3d_cfg),
+    **_plan_sigs(_entry_names("spff_r2u"), spff_r2u_cfg),
+    **_plan_sigs(_entry_names("spff_rupp"), spff_rupp_cfg),
+    **_plan_sigs(_entry_names("spff_swin"), spff_swin_cfg),
+    **_plan_sigs(_entry_names("spff_unetr"), spff_unetr_cfg),
     "spff_plan_set_coll": (_I, [_P, ctypes.POINTER(spff_coll)]),
-    "spff_plan_destroy": (None, [_P]),
     "spff_plan_set_grad_hook": (_I, [_P, GRAD_READY_FN, _P]),
     "spff_last_error": (ctypes.c_char_p, []),
-    "spff_num_params": (_I, [_P]),
-    "spff_param_info": (_I, [_P, _I, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(_I),
-                             ctypes.POINTER(_L), ctypes.POINTER(_L), ctypes.POINTER(_L)]),
-    "spff_param_floats": (_L, [_P]),
-    "spff_workspace_bytes": (_S, [_P]),
-    "spff_forward": (_I, [_P, _P, _P, _P, _P, _P]),
-    "spff_backward": (_I, [_P, _P, _P, _P, _P, _P]),
-    "spff_saved_tensor": (_I, [_P, _P, ctypes.c_char_p, ctypes.POINTER(_P), ctypes.POINTER(_L),
-                               ctypes.POINTER(_I)]),
     "spff_debug_set": (_I, [_P, _I, _I]),
     "spff_prof_enable": (_I, [_P, _I]),
     "spff_prof_collect": (_I, [_P, ctypes.POINTER(ctypes.c_double), _I]),
@@ -179,47 +206,16 @@ _SIGS = {
     "spff_conv3d_wgrad_ex": (_I, [_P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
     "spff_conv3d_wgrad": (_I, [_P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
     # 3DUNet baseline variant (BASELINE config 3)
-    "spff_unet3d_create": (_I, [ctypes.POINTER(spff_unet3d_cfg), ctypes.POINTER(_P)]),
-    "spff_unet3d_destroy": (None, [_P]),
-    "spff_unet3d_num_params": (_I, [_P]),
-    "spff_unet3d_param_info": (_I, [_P, _I, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(_I),
-                                    ctypes.POINTER(_L), ctypes.POINTER(_L), ctypes.POINTER(_L)]),
-    "spff_unet3d_param_floats": (_L, [_P]),
     "spff_unet3d_num_buffers": (_I, [_P]),
     "spff_unet3d_buffer_info": (_I, [_P, _I, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(_L),
                                      ctypes.POINTER(_L)]),
     "spff_unet3d_buffer_floats": (_L, [_P]),
-    "spff_unet3d_workspace_bytes": (_S, [_P]),
+    # (replaces the standard forward above: buffers and training between params and logits)
     "spff_unet3d_forward": (_I, [_P, _P, _P, _P, _I, _P, _P, _P]),
-    "spff_unet3d_backward": (_I, [_P, _P, _P, _P, _P, _P]),
-    "spff_unet3d_saved_tensor": (_I, [_P, _P, ctypes.c_char_p, ctypes.POINTER(_P),
-                                      ctypes.POINTER(_L), ctypes.POINTER(_I)]),
     # R2UNet3D variant
-    "spff_r2u_create": (_I, [ctypes.POINTER(spff_r2u_cfg), ctypes.POINTER(_P)]),
-    "spff_r2u_destroy": (None, [_P]),
-    "spff_r2u_num_params": (_I, [_P]),
-    "spff_r2u_param_info": (_I, [_P, _I, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(_I),
-                                 ctypes.POINTER(_L), ctypes.POINTER(_L), ctypes.POINTER(_L)]),
-    "spff_r2u_param_floats": (_L, [_P]),
-    "spff_r2u_workspace_bytes": (_S, [_P]),
-    "spff_r2u_forward": (_I, [_P, _P, _P, _P, _P, _P]),
-    "spff_r2u_backward": (_I, [_P, _P, _P, _P, _P, _P]),
-    "spff_r2u_saved_tensor": (_I, [_P, _P, ctypes.c_char_p, ctypes.POINTER(_P),
-                                   ctypes.POINTER(_L), ctypes.POINTER(_I)]),
     "spff_r2u_dice_loss_ws_bytes": (_S, [_I, _I]),
     "spff_r2u_dice_loss": (_I, [_P, _P, _I, _L, _I, _I, _I, _P, _P, _P, _P]),
     # ResUNet++ variant
-    "spff_rupp_create": (_I, [ctypes.POINTER(spff_rupp_cfg), ctypes.POINTER(_P)]),
-    "spff_rupp_destroy": (None, [_P]),
-    "spff_rupp_num_params": (_I, [_P]),
-    "spff_rupp_param_info": (_I, [_P, _I, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(_I),
-                                  ctypes.POINTER(_L), ctypes.POINTER(_L), ctypes.POINTER(_L)]),
-    "spff_rupp_param_floats": (_L, [_P]),
-    "spff_rupp_workspace_bytes": (_S, [_P]),
-    "spff_rupp_forward": (_I, [_P, _P, _P, _P, _P, _P]),
-    "spff_rupp_backward": (_I, [_P, _P, _P, _P, _P, _P]),
-    "spff_rupp_saved_tensor": (_I, [_P, _P, ctypes.c_char_p, ctypes.POINTER(_P),
-                                    ctypes.POINTER(_L), ctypes.POINTER(_I)]),
     "spff_rupp_loss_ws_bytes": (_S, [_I, _I]),
     "spff_rupp_loss": (_I, [_P, _P, _I, _L, _I, _I, _I, _I, ctypes.c_double, ctypes.c_double,
                             _P, _P, _P, _P]),
@@ -228,30 +224,8 @@ _SIGS = {
     "spff_conv3d_dil_dgrad": (_I, [_P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
     "spff_conv3d_dil_wgrad": (_I, [_P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
     # SwinUNETR variant (BASELINE config 5)
-    "spff_swin_create": (_I, [ctypes.POINTER(spff_swin_cfg), ctypes.POINTER(_P)]),
-    "spff_swin_destroy": (None, [_P]),
-    "spff_swin_num_params": (_I, [_P]),
-    "spff_swin_param_info": (_I, [_P, _I, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(_I),
-                                  ctypes.POINTER(_L), ctypes.POINTER(_L), ctypes.POINTER(_L)]),
-    "spff_swin_param_floats": (_L, [_P]),
-    "spff_swin_workspace_bytes": (_S, [_P]),
-    "spff_swin_forward": (_I, [_P, _P, _P, _P, _P, _P]),
-    "spff_swin_backward": (_I, [_P, _P, _P, _P, _P, _P]),
-    "spff_swin_saved_tensor": (_I, [_P, _P, ctypes.c_char_p, ctypes.POINTER(_P),
-                                    ctypes.POINTER(_L), ctypes.POINTER(_I)]),
     "spff_swin_loss_ws_bytes": (_S, [_I, _I]),
     # UNETR variant
-    "spff_unetr_create": (_I, [ctypes.POINTER(spff_unetr_cfg), ctypes.POINTER(_P)]),
-    "spff_unetr_destroy": (None, [_P]),
-    "spff_unetr_num_params": (_I, [_P]),
-    "spff_unetr_param_info": (_I, [_P, _I, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(_I),
-                                   ctypes.POINTER(_L), ctypes.POINTER(_L), ctypes.POINTER(_L)]),
-    "spff_unetr_param_floats": (_L, [_P]),
-    "spff_unetr_workspace_bytes": (_S, [_P]),
-    "spff_unetr_forward": (_I, [_P, _P, _P, _P, _P, _P]),
-    "spff_unetr_backward": (_I, [_P, _P, _P, _P, _P, _P]),
-    "spff_unetr_saved_tensor": (_I, [_P, _P, ctypes.c_char_p, ctypes.POINTER(_P),
-                                     ctypes.POINTER(_L), ctypes.POINTER(_I)]),
     "spff_vit_attn_ws_bytes": (_S, [_I, _I, _I]),
     "spff_vit_attn_fwd": (_I, [_P, _I, _I, _I, _I, _P, _P, _P]),
     "spff_vit_attn_bwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
@@ -313,73 +287,169 @@ def require_device(t: torch.Tensor, what: str):
                         f"on {t.device}. There is no CPU fallback.")
 
 
-class Plan:
-    """One engine plan (shape + flags) and its device workspace.
+class _PlanBase:
+    """What every engine plan shares (DESIGN "Plan scaffolding"): the handle, the parameter
+    table, the workspace and forward / backward / saved on the plan's nine entry points.
 
-    The workspace holds the saved activations of the most recent forward until
-    the matching backward (``generation`` guards against interleaving)."""
+    A plan class sets PREFIX (its C symbols are ``{PREFIX}_create`` ...), CFG (the ctypes
+    struct), NAME (used in messages) and ``_fill_cfg``; its ``__init__`` keeps the keyword
+    signature and passes what is its own through.  The workspace holds the saved
+    activations of the most recent forward until the matching backward (``generation``
+    guards against interleaving)."""
+
+    PREFIX = CFG = NAME = None
+    ENTRY_NAMES: Optional[Dict[str, str]] = None  # only where the symbols are irregular
+
+    def __init__(self, batch, in_ch, depth, height, width, num_classes, device, math, **own):
+        math = math or default_math()
+        if math not in MATH_NAMES:
+            raise SpffError(f"math={math!r}: expected one of {sorted(MATH_NAMES)}")
+        cfg = self.CFG()
+        cfg.batch, cfg.in_ch, cfg.depth, cfg.height, cfg.width = batch, in_ch, depth, height, width
+        cfg.num_classes, cfg.math = num_classes, MATH_NAMES[math]
+        self.cfg, self.math, self.device = cfg, math, device
+        self._fill_cfg(cfg, **own)
+        h = ctypes.c_void_p()
+        self._check(self._fn("create")(ctypes.byref(cfg), ctypes.byref(h)), self._sym("create"))
+        self._h = h
+        self.params: List[Tuple[str, Tuple[int, ...], int, int]] = []
+        info = self._fn("param_info")
+        for i in range(self._fn("num_params")(h)):
+            name, nd = ctypes.c_char_p(), ctypes.c_int()
+            shape, off, n = (ctypes.c_int64 * 5)(), ctypes.c_int64(), ctypes.c_int64()
+            self._check(info(h, i, ctypes.byref(name), ctypes.byref(nd), shape, ctypes.byref(off),
+                             ctypes.byref(n)), self._sym("param_info"))
+            self.params.append((name.value.decode(), tuple(shape[k] for k in range(nd.value)),
+                                off.value, n.value))
+        self.nfloats = int(self._fn("param_floats")(h))
+        self.ws_bytes = int(self._fn("workspace_bytes")(h))
+        self._ws: Optional[torch.Tensor] = None
+        self.generation = 0
+
+    def _fill_cfg(self, cfg) -> None:
+        """Set the cfg fields beyond batch .. num_classes and math."""
+
+    @classmethod
+    def _sym(cls, entry: str) -> str:
+        return cls.ENTRY_NAMES[entry] if cls.ENTRY_NAMES else f"{cls.PREFIX}_{entry}"
+
+    def _fn(self, entry: str):
+        return getattr(lib(), self._sym(entry))
+
+    _check = staticmethod(check)
+
+    def __del__(self):
+        try:
+            if getattr(self, "_h", None) is not None and _lib is not None:
+                getattr(_lib, self._sym("destroy"))(self._h)
+        except Exception:
+            pass
+
+    def workspace(self, device) -> torch.Tensor:
+        if self._ws is None or self._ws.device != device:
+            self._ws = _alloc_workspace(self, device)
+        return self._ws
+
+    def forward(self, x: torch.Tensor, flat: torch.Tensor,
+                out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """x [B,Cin,D,H,W] fp32 -> logits channel-last [B,D,H,W,K]."""
+        return self._forward(x, flat, out)
+
+    def _forward(self, x, flat, out, *extra):
+        """``extra``: the plan's own arguments between params and logits"""
+        c = self.cfg
+        require_device(x, f"{self.NAME} forward")
+        if tuple(x.shape) != (c.batch, c.in_ch, c.depth, c.height, c.width):
+            raise SpffError(f"input shape {tuple(x.shape)} does not match plan")
+        if x.dtype != torch.float32:
+            raise SpffError("the engine computes in fp32; got " + str(x.dtype))
+        x = x.contiguous()
+        if out is None:
+            out = torch.empty((c.batch, c.depth, c.height, c.width, c.num_classes),
+                              dtype=torch.float32, device=x.device)
+        ws = self.workspace(x.device)
+        self.generation += 1
+        self._check(self._fn("forward")(self._h, _ptr(x), _ptr(flat), *extra, _ptr(out), _ptr(ws),
+                                        _stream(x.device)), self._sym("forward"))
+        return out
+
+    def backward(self, dlogits_cl: torch.Tensor, flat: torch.Tensor,
+                 dflat: Optional[torch.Tensor] = None, grad_hook=None) -> torch.Tensor:
+        """``grad_hook`` (GradBucketer protocol): the whole gradient is reported as ready
+        once the backward is enqueued (no per-block hook)."""
+        dlogits_cl = dlogits_cl.contiguous()
+        if dflat is None:
+            dflat = torch.empty(self.nfloats, dtype=torch.float32, device=dlogits_cl.device)
+        ws = self.workspace(dlogits_cl.device)
+        self._check(self._fn("backward")(self._h, _ptr(dlogits_cl), _ptr(flat), _ptr(dflat),
+                                         _ptr(ws), _stream(dlogits_cl.device)),
+                    self._sym("backward"))
+        _whole_buffer_hook(grad_hook, dflat)
+        return dflat
+
+    def _saved_view(self, name: str) -> Tuple[torch.Tensor, int, int]:
+        """(bytes of the workspace from the saved tensor on, rows, channels)"""
+        ws = self._ws
+        if ws is None:
+            raise SpffError("no forward has run")
+        ptr, nv, ch = ctypes.c_void_p(), ctypes.c_int64(), ctypes.c_int()
+        self._check(self._fn("saved_tensor")(self._h, _ptr(ws), name.encode(), ctypes.byref(ptr),
+                                             ctypes.byref(nv), ctypes.byref(ch)),
+                    self._sym("saved_tensor"))
+        return ws[ptr.value - ws.data_ptr():], nv.value, ch.value
+
+    def saved(self, name: str) -> torch.Tensor:
+        """Copy of a saved intermediate as a channel-last fp32 [V, C] tensor (debug/tests)."""
+        b, nv, ch = self._saved_view(name)
+        return b[:4 * nv * ch].view(torch.float32).view(nv, ch).clone()
+
+
+def _whole_buffer_hook(grad_hook, dflat: torch.Tensor) -> None:
+    if grad_hook is None:
+        return
+    grad_hook.begin(dflat)
+    grad_hook.ready(0, int(dflat.numel()))
+    grad_hook.finish()
+
+
+class Plan(_PlanBase):
+    """One plan of the main SPFF engine (shape + flags) and its device workspace; beyond
+    _PlanBase: sharding, the memory mode, per-block gradient hooks, profiling and debug keys."""
+
+    CFG, NAME, ENTRY_NAMES = spff_cfg, "SPFF", _MAIN_NAMES
 
     def __init__(self, batch, in_ch, depth, height, width, num_classes, base=32, ksd=3,
                  efilm=True, fgate=True, se=True, specse=True, device=None, math=None,
                  shard_world=1, shard_rank=0, memory=None, shard_axis=0, efilm_hidden=32,
                  efilm_pe_dims=16, fgate_learn_phase=False):
-        math = default_math() if math is None else math
-        if math not in MATH_NAMES:
-            raise SpffError(f"math={math!r}: expected one of {sorted(MATH_NAMES)}")
+        super().__init__(batch, in_ch, depth, height, width, num_classes, device, math,
+                         base=base, ksd=ksd, efilm=efilm, fgate=fgate, se=se, specse=specse,
+                         shard=(int(shard_world), int(shard_rank), int(shard_axis)),
+                         memory=memory, efilm_hidden=efilm_hidden, efilm_pe_dims=efilm_pe_dims,
+                         fgate_learn_phase=fgate_learn_phase)
+        self.key = (batch, in_ch, depth, height, width, num_classes, base, ksd, bool(efilm),
+                    bool(fgate), bool(se), bool(specse), self.math, self.shard, self.memory,
+                    int(efilm_hidden), int(efilm_pe_dims), bool(fgate_learn_phase))
+
+    def _fill_cfg(self, cfg, base, ksd, efilm, fgate, se, specse, shard, memory, efilm_hidden,
+                  efilm_pe_dims, fgate_learn_phase):
         memory = default_memory() if memory is None else memory
         if memory not in MEMORY_MODES:
             raise SpffError(f"memory={memory!r}: expected one of {sorted(MEMORY_MODES)}")
-        cfg = spff_cfg()
-        cfg.math = MATH_NAMES[math]
         cfg.memory_mode = MEMORY_MODES[memory]
         self.memory = memory
         # the layout the engine resolves (engine.hip build_plan: lean from 2^26 voxels on auto)
-        self.layout = ("lean" if memory == "lean" or
-                       (memory == "auto" and batch * depth * height * width >= 1 << 26)
+        voxels = cfg.batch * cfg.depth * cfg.height * cfg.width
+        self.layout = ("lean" if memory == "lean" or (memory == "auto" and voxels >= 1 << 26)
                        else "full")
-        cfg.shard_world, cfg.shard_rank = int(shard_world), int(shard_rank)
-        # 0 = SPFF_SHARD_DEPTH (BASELINE config 4), 1 = SPFF_SHARD_HEIGHT (registry layout)
-        cfg.shard_axis = int(shard_axis)
-        self.math = math
-        self.shard = (int(shard_world), int(shard_rank), int(shard_axis))
-        cfg.batch, cfg.in_ch, cfg.depth, cfg.height, cfg.width = batch, in_ch, depth, height, width
-        cfg.num_classes, cfg.base, cfg.ksd = num_classes, base, ksd
+        # axis 0 = SPFF_SHARD_DEPTH (BASELINE config 4), 1 = SPFF_SHARD_HEIGHT (registry layout)
+        cfg.shard_world, cfg.shard_rank, cfg.shard_axis = self.shard = shard
+        cfg.base, cfg.ksd = base, ksd
         cfg.use_efilm, cfg.use_fgate, cfg.use_se, cfg.use_specse = (int(bool(efilm)), int(bool(fgate)),
                                                                     int(bool(se)), int(bool(specse)))
         # EnergyFiLM3D(hidden, pe_dims) / FourierGate3D(learn_phase) of the blocks
         cfg.efilm_hidden, cfg.efilm_pe_dims = int(efilm_hidden), int(efilm_pe_dims)
         cfg.fgate_learn_phase = int(bool(fgate_learn_phase))
-        self.cfg = cfg
-        self.key = (batch, in_ch, depth, height, width, num_classes, base, ksd, bool(efilm),
-                    bool(fgate), bool(se), bool(specse), math, self.shard, memory,
-                    int(efilm_hidden), int(efilm_pe_dims), bool(fgate_learn_phase))
-        L = lib()
-        h = ctypes.c_void_p()
-        check(L.spff_plan_create(ctypes.byref(cfg), ctypes.byref(h)), "spff_plan_create")
-        self._h = h
-        self.params: List[Tuple[str, Tuple[int, ...], int, int]] = []
-        for i in range(L.spff_num_params(h)):
-            name = ctypes.c_char_p()
-            nd = ctypes.c_int()
-            shape = (ctypes.c_int64 * 5)()
-            off = ctypes.c_int64()
-            n = ctypes.c_int64()
-            check(L.spff_param_info(h, i, ctypes.byref(name), ctypes.byref(nd), shape,
-                                    ctypes.byref(off), ctypes.byref(n)), "spff_param_info")
-            self.params.append((name.value.decode(), tuple(shape[k] for k in range(nd.value)),
-                                off.value, n.value))
-        self.nfloats = int(L.spff_param_floats(h))
-        self.ws_bytes = int(L.spff_workspace_bytes(h))
-        self.device = device
-        self._ws: Optional[torch.Tensor] = None
-        self.generation = 0
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None) is not None and _lib is not None:
-                _lib.spff_plan_destroy(self._h)
-        except Exception:
-            pass
 
     def set_coll(self, impl) -> None:
         """Attach a depth-sharding collective implementation: an object with
@@ -469,29 +539,9 @@ class Plan:
         self._coll_ev = []
         return out
 
-    def workspace(self, device) -> torch.Tensor:
-        if self._ws is None or self._ws.device != device:
-            self._ws = _alloc_workspace(self, device)
-        return self._ws
-
     def forward(self, x: torch.Tensor, flat: torch.Tensor, out: Optional[torch.Tensor] = None):
-        """x [B,Cin,D,H,W] contiguous fp32 -> logits channel-last [B,D,H,W,K]."""
-        c = self.cfg
-        require_device(x, "SPFF forward")
-        if tuple(x.shape) != (c.batch, c.in_ch, c.depth, c.height, c.width):
-            raise SpffError(f"input shape {tuple(x.shape)} does not match plan")
-        x = x.contiguous()
-        if x.dtype != torch.float32:
-            raise SpffError("SPFF engine computes in fp32; got " + str(x.dtype))
-        if out is None:
-            out = torch.empty((c.batch, c.depth, c.height, c.width, c.num_classes),
-                              dtype=torch.float32, device=x.device)
-        ws = self.workspace(x.device)
-        self.generation += 1
         self.coll_error = None
-        self._check(lib().spff_forward(self._h, _ptr(x), _ptr(flat), _ptr(out), _ptr(ws),
-                                       _stream(x.device)), "spff_forward")
-        return out
+        return self._forward(x, flat, out)
 
     def _check(self, rc: int, what: str) -> None:
         """check(), raising SpffCollError chained to the callback's own exception when a
@@ -587,21 +637,11 @@ class Plan:
         check(lib().spff_debug_set(self._h, int(key), int(value)), "spff_debug_set")
 
     def saved(self, name: str) -> torch.Tensor:
-        """Copy of a saved intermediate as a channel-last [V, C] tensor (debug/tests):
-        fp32, or uint8 for the max-pool argmax bytes "poolN.idx"."""
-        ws = self._ws
-        if ws is None:
-            raise SpffError("no forward has run")
-        ptr = ctypes.c_void_p()
-        nv = ctypes.c_int64()
-        ch = ctypes.c_int()
-        check(lib().spff_saved_tensor(self._h, _ptr(ws), name.encode(), ctypes.byref(ptr),
-                                      ctypes.byref(nv), ctypes.byref(ch)), "spff_saved_tensor")
-        off = ptr.value - ws.data_ptr()
-        n = nv.value * ch.value
+        """As _PlanBase.saved; uint8 for the max-pool argmax bytes "poolN.idx"."""
         if name.endswith(".idx"):
-            return ws[off:off + n].view(nv.value, ch.value).clone()
-        return ws[off:off + 4 * n].view(torch.float32).view(nv.value, ch.value).clone()
+            b, nv, ch = self._saved_view(name)
+            return b[:nv * ch].view(nv, ch).clone()
+        return super().saved(name)
 
 
 # Plans (and the workspace each pins: ~2.6 KB per voxel) belong to the module
@@ -732,59 +772,30 @@ def get_plan(owner=None, tag: str = "", **kw) -> Plan:
     return _owned_plan(owner, tag, key, make)
 
 
-class UNet3DPlan:
+class UNet3DPlan(_PlanBase):
     """Engine plan of the 3DUNet baseline variant (include/spff.h spff_unet3d_*):
     Cicek3DUNet + the depth adapter of LitCicek3DUNet_DepthAdapter_Published
     (reference models.py:718-777).  Parameters are one flat fp32 buffer in
     reference state-dict order (``params``), BatchNorm running statistics a
     second one (``buffers``)."""
 
+    PREFIX, CFG, NAME = "spff_unet3d", spff_unet3d_cfg, "3DUNet"
+
     def __init__(self, batch, in_ch, depth, height, width, num_classes, base=32, target_depth=0,
                  device=None, math=None):
-        math = default_math() if math is None else math
-        if math not in MATH_NAMES:
-            raise SpffError(f"math={math!r}: expected one of {sorted(MATH_NAMES)}")
-        cfg = spff_unet3d_cfg()
-        cfg.batch, cfg.in_ch, cfg.depth, cfg.height, cfg.width = batch, in_ch, depth, height, width
-        cfg.target_depth, cfg.num_classes, cfg.base = int(target_depth), num_classes, base
-        cfg.math = MATH_NAMES[math]
-        self.cfg, self.math, self.device = cfg, math, device
-        L = lib()
-        h = ctypes.c_void_p()
-        check(L.spff_unet3d_create(ctypes.byref(cfg), ctypes.byref(h)), "spff_unet3d_create")
-        self._h = h
-        self.params: List[Tuple[str, Tuple[int, ...], int, int]] = []
-        for i in range(L.spff_unet3d_num_params(h)):
-            name, nd = ctypes.c_char_p(), ctypes.c_int()
-            shape, off, n = (ctypes.c_int64 * 5)(), ctypes.c_int64(), ctypes.c_int64()
-            check(L.spff_unet3d_param_info(h, i, ctypes.byref(name), ctypes.byref(nd), shape,
-                                           ctypes.byref(off), ctypes.byref(n)),
-                  "spff_unet3d_param_info")
-            self.params.append((name.value.decode(), tuple(shape[k] for k in range(nd.value)),
-                                off.value, n.value))
+        super().__init__(batch, in_ch, depth, height, width, num_classes, device, math,
+                         base=base, target_depth=target_depth)
+        L, h = lib(), self._h
         self.buffers: List[Tuple[str, int, int]] = []
         for i in range(L.spff_unet3d_num_buffers(h)):
             name, off, n = ctypes.c_char_p(), ctypes.c_int64(), ctypes.c_int64()
             check(L.spff_unet3d_buffer_info(h, i, ctypes.byref(name), ctypes.byref(off),
                                             ctypes.byref(n)), "spff_unet3d_buffer_info")
             self.buffers.append((name.value.decode(), off.value, n.value))
-        self.nfloats = int(L.spff_unet3d_param_floats(h))
         self.nbuf = int(L.spff_unet3d_buffer_floats(h))
-        self.ws_bytes = int(L.spff_unet3d_workspace_bytes(h))
-        self._ws: Optional[torch.Tensor] = None
-        self.generation = 0
 
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None) is not None and _lib is not None:
-                _lib.spff_unet3d_destroy(self._h)
-        except Exception:
-            pass
-
-    def workspace(self, device) -> torch.Tensor:
-        if self._ws is None or self._ws.device != device:
-            self._ws = _alloc_workspace(self, device)
-        return self._ws
+    def _fill_cfg(self, cfg, base, target_depth):
+        cfg.base, cfg.target_depth = base, int(target_depth)
 
     def set_sync_bn(self, impl) -> None:
         """Synchronised BatchNorm over a data-parallel group (spff_unet3d_set_sync_bn):
@@ -827,167 +838,51 @@ class UNet3DPlan:
     def forward(self, x: torch.Tensor, flat: torch.Tensor, bufs: torch.Tensor, training: bool,
                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """x [B,Cin,D,H,W] fp32 -> logits channel-last [B,D,H,W,K]; training updates bufs."""
-        c = self.cfg
-        require_device(x, "3DUNet forward")
-        if tuple(x.shape) != (c.batch, c.in_ch, c.depth, c.height, c.width):
-            raise SpffError(f"input shape {tuple(x.shape)} does not match plan")
-        if x.dtype != torch.float32:
-            raise SpffError("the engine computes in fp32; got " + str(x.dtype))
-        x = x.contiguous()
-        if out is None:
-            out = torch.empty((c.batch, c.depth, c.height, c.width, c.num_classes),
-                              dtype=torch.float32, device=x.device)
-        ws = self.workspace(x.device)
-        self.generation += 1
-        check(lib().spff_unet3d_forward(self._h, _ptr(x), _ptr(flat), _ptr(bufs), int(bool(training)),
-                                        _ptr(out), _ptr(ws), _stream(x.device)),
-              "spff_unet3d_forward")
-        return out
-
-    def backward(self, dlogits_cl: torch.Tensor, flat: torch.Tensor, grad_hook=None) -> torch.Tensor:
-        """``grad_hook`` (GradBucketer protocol): this plan reports its whole
-        gradient as ready once the backward is enqueued (no per-block hook)."""
-        dlogits_cl = dlogits_cl.contiguous()
-        dflat = torch.empty(self.nfloats, dtype=torch.float32, device=dlogits_cl.device)
-        ws = self.workspace(dlogits_cl.device)
-        check(lib().spff_unet3d_backward(self._h, _ptr(dlogits_cl), _ptr(flat), _ptr(dflat),
-                                         _ptr(ws), _stream(dlogits_cl.device)),
-              "spff_unet3d_backward")
-        _whole_buffer_hook(grad_hook, dflat)
-        return dflat
-
-    def saved(self, name: str) -> torch.Tensor:
-        ws = self._ws
-        if ws is None:
-            raise SpffError("no forward has run")
-        ptr, nv, ch = ctypes.c_void_p(), ctypes.c_int64(), ctypes.c_int()
-        check(lib().spff_unet3d_saved_tensor(self._h, _ptr(ws), name.encode(), ctypes.byref(ptr),
-                                             ctypes.byref(nv), ctypes.byref(ch)),
-              "spff_unet3d_saved_tensor")
-        off = ptr.value - ws.data_ptr()
-        n = nv.value * ch.value
-        return ws[off:off + 4 * n].view(torch.float32).view(nv.value, ch.value).clone()
+        return self._forward(x, flat, out, _ptr(bufs), int(bool(training)))
 
 
-def _whole_buffer_hook(grad_hook, dflat: torch.Tensor) -> None:
-    if grad_hook is None:
-        return
-    grad_hook.begin(dflat)
-    grad_hook.ready(0, int(dflat.numel()))
-    grad_hook.finish()
+def _get_variant_plan(cls, owner, tag: str, kw: dict):
+    """The plan of class ``cls`` for ``owner`` / ``tag`` (owned like get_plan); the cache key
+    is the constructor's arguments with its declared defaults filled in."""
+    args = inspect.signature(cls.__init__).bind(None, **kw)
+    args.apply_defaults()
+    args.arguments["math"] = kw.get("math") or default_math()
+    kind = cls.PREFIX[len("spff_"):]
+    key = (kind,) + tuple(tuple(v) if isinstance(v, (list, tuple)) else v
+                          for n, v in args.arguments.items() if n not in ("self", "device"))
+    return _owned_plan(owner, kind + ":" + tag, key, lambda: cls(**kw))
 
 
 def get_unet3d_plan(owner=None, tag: str = "", **kw) -> UNet3DPlan:
-    """UNet3D plans, owned like get_plan."""
-    key = ("unet3d", kw["batch"], kw["in_ch"], kw["depth"], kw["height"], kw["width"],
-           kw["num_classes"], kw.get("base", 32), kw.get("target_depth", 0),
-           kw.get("math") or default_math())
-    return _owned_plan(owner, "unet3d:" + tag, key, lambda: UNet3DPlan(**kw))
+    return _get_variant_plan(UNet3DPlan, owner, tag, kw)
 
 
-class SwinPlan:
+class SwinPlan(_PlanBase):
     """One spff_swin plan (SwinUNETR variant) + its workspace."""
+
+    PREFIX, CFG, NAME = "spff_swin", spff_swin_cfg, "SwinUNETR"
 
     def __init__(self, batch, in_ch, depth, height, width, num_classes, feature_size=12,
                  window=7, heads=(1, 2, 4, 8), mlp_ratio=2.0, device=None, math=None):
-        math = math or default_math()
-        if math not in MATH_NAMES:
-            raise SpffError(f"math={math!r}: expected one of {sorted(MATH_NAMES)}")
-        cfg = spff_swin_cfg()
-        cfg.batch, cfg.in_ch, cfg.depth, cfg.height, cfg.width = batch, in_ch, depth, height, width
-        cfg.num_classes, cfg.feature_size, cfg.window = num_classes, feature_size, window
+        super().__init__(batch, in_ch, depth, height, width, num_classes, device, math,
+                         feature_size=feature_size, window=window, heads=heads,
+                         mlp_ratio=mlp_ratio)
+
+    def _fill_cfg(self, cfg, feature_size, window, heads, mlp_ratio):
+        cfg.feature_size, cfg.window, cfg.mlp_ratio = feature_size, window, float(mlp_ratio)
         for i, h in enumerate(heads):
             cfg.heads[i] = int(h)
-        cfg.mlp_ratio = float(mlp_ratio)
-        cfg.math = MATH_NAMES[math]
-        self.cfg, self.math, self.device = cfg, math, device
-        L = lib()
-        h = ctypes.c_void_p()
-        check(L.spff_swin_create(ctypes.byref(cfg), ctypes.byref(h)), "spff_swin_create")
-        self._h = h
-        self.params: List[Tuple[str, Tuple[int, ...], int, int]] = []
-        for i in range(L.spff_swin_num_params(h)):
-            name, nd = ctypes.c_char_p(), ctypes.c_int()
-            shape, off, n = (ctypes.c_int64 * 5)(), ctypes.c_int64(), ctypes.c_int64()
-            check(L.spff_swin_param_info(h, i, ctypes.byref(name), ctypes.byref(nd), shape,
-                                         ctypes.byref(off), ctypes.byref(n)),
-                  "spff_swin_param_info")
-            self.params.append((name.value.decode(), tuple(shape[k] for k in range(nd.value)),
-                                off.value, n.value))
-        self.nfloats = int(L.spff_swin_param_floats(h))
-        self.ws_bytes = int(L.spff_swin_workspace_bytes(h))
-        self._ws: Optional[torch.Tensor] = None
-        self.generation = 0
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None) is not None and _lib is not None:
-                _lib.spff_swin_destroy(self._h)
-        except Exception:
-            pass
-
-    def workspace(self, device) -> torch.Tensor:
-        if self._ws is None or self._ws.device != device:
-            self._ws = _alloc_workspace(self, device)
-        return self._ws
-
-    def forward(self, x: torch.Tensor, flat: torch.Tensor,
-                out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """x [B,Cin,D,H,W] fp32 -> logits channel-last [B,D,H,W,K]."""
-        c = self.cfg
-        require_device(x, "SwinUNETR forward")
-        if tuple(x.shape) != (c.batch, c.in_ch, c.depth, c.height, c.width):
-            raise SpffError(f"input shape {tuple(x.shape)} does not match plan")
-        if x.dtype != torch.float32:
-            raise SpffError("the engine computes in fp32; got " + str(x.dtype))
-        x = x.contiguous()
-        if out is None:
-            out = torch.empty((c.batch, c.depth, c.height, c.width, c.num_classes),
-                              dtype=torch.float32, device=x.device)
-        ws = self.workspace(x.device)
-        self.generation += 1
-        check(lib().spff_swin_forward(self._h, _ptr(x), _ptr(flat), _ptr(out), _ptr(ws),
-                                      _stream(x.device)), "spff_swin_forward")
-        return out
-
-    def backward(self, dlogits_cl: torch.Tensor, flat: torch.Tensor,
-                 dflat: Optional[torch.Tensor] = None, grad_hook=None) -> torch.Tensor:
-        """``grad_hook`` as UNet3DPlan.backward: the whole gradient at once."""
-        dlogits_cl = dlogits_cl.contiguous()
-        if dflat is None:
-            dflat = torch.empty(self.nfloats, dtype=torch.float32, device=dlogits_cl.device)
-        ws = self.workspace(dlogits_cl.device)
-        check(lib().spff_swin_backward(self._h, _ptr(dlogits_cl), _ptr(flat), _ptr(dflat), _ptr(ws),
-                                       _stream(dlogits_cl.device)), "spff_swin_backward")
-        _whole_buffer_hook(grad_hook, dflat)
-        return dflat
-
-    def saved(self, name: str) -> torch.Tensor:
-        ws = self._ws
-        if ws is None:
-            raise SpffError("no forward has run")
-        ptr, nv, ch = ctypes.c_void_p(), ctypes.c_int64(), ctypes.c_int()
-        check(lib().spff_swin_saved_tensor(self._h, _ptr(ws), name.encode(), ctypes.byref(ptr),
-                                           ctypes.byref(nv), ctypes.byref(ch)),
-              "spff_swin_saved_tensor")
-        off = ptr.value - ws.data_ptr()
-        n = nv.value * ch.value
-        return ws[off:off + 4 * n].view(torch.float32).view(nv.value, ch.value).clone()
 
 
 def get_swin_plan(owner=None, tag: str = "", **kw) -> SwinPlan:
-    """SwinUNETR plans, owned like get_plan."""
-    key = ("swin", kw["batch"], kw["in_ch"], kw["depth"], kw["height"], kw["width"],
-           kw["num_classes"], kw.get("feature_size", 12), kw.get("window", 7),
-           tuple(kw.get("heads", (1, 2, 4, 8))), float(kw.get("mlp_ratio", 2.0)),
-           kw.get("math") or default_math())
-    return _owned_plan(owner, "swin:" + tag, key, lambda: SwinPlan(**kw))
+    return _get_variant_plan(SwinPlan, owner, tag, kw)
 
 
-def swin_loss_forward(logits_cl: torch.Tensor, labels: torch.Tensor, K: int, ignore_index: int,
-                      include_bg: bool, ce_weight: float):
-    """LitSwinUNETR_Published._loss on the HIP kernels: returns (out4, dlogits_cl)."""
-    require_device(logits_cl, "SwinUNETR loss")
+def _variant_loss(what: str, entry: str, logits_cl: torch.Tensor, labels: torch.Tensor, K: int,
+                  *tail):
+    """A variant's loss on its HIP kernels (``entry`` and ``entry``_ws_bytes): returns
+    (out4, dlogits_cl).  ``tail``: the loss's own arguments between K and out4."""
+    require_device(logits_cl, what + " loss")
     logits_cl = logits_cl.contiguous()
     B = logits_cl.shape[0]
     labels = labels.to(device=logits_cl.device, dtype=torch.int64).contiguous()
@@ -997,113 +892,45 @@ def swin_loss_forward(logits_cl: torch.Tensor, labels: torch.Tensor, K: int, ign
     dev = logits_cl.device
     out4 = torch.empty(4, dtype=torch.float32, device=dev)
     dl = torch.empty_like(logits_cl)
-    ws = torch.empty(int(lib().spff_swin_loss_ws_bytes(B, K)), dtype=torch.uint8, device=dev)
-    check(lib().spff_swin_loss(_ptr(logits_cl), _ptr(labels), B, V // B, K, int(ignore_index),
-                               int(bool(include_bg)), float(ce_weight), _ptr(out4), _ptr(dl),
-                               _ptr(ws), _stream(dev)), "spff_swin_loss")
+    L = lib()
+    ws = torch.empty(int(getattr(L, entry + "_ws_bytes")(B, K)), dtype=torch.uint8, device=dev)
+    check(getattr(L, entry)(_ptr(logits_cl), _ptr(labels), B, V // B, K, *tail, _ptr(out4),
+                            _ptr(dl), _ptr(ws), _stream(dev)), entry)
     return out4, dl
 
 
-class UNETRPlan:
+def _ignore_args(ignore_index: Optional[int]) -> Tuple[int, int]:
+    """(use_ignore, ignore_index); None: no voxel is masked"""
+    return int(ignore_index is not None), int(ignore_index) if ignore_index is not None else 0
+
+
+def swin_loss_forward(logits_cl: torch.Tensor, labels: torch.Tensor, K: int, ignore_index: int,
+                      include_bg: bool, ce_weight: float):
+    """LitSwinUNETR_Published._loss on the HIP kernels: returns (out4, dlogits_cl)."""
+    return _variant_loss("SwinUNETR", "spff_swin_loss", logits_cl, labels, K, int(ignore_index),
+                         int(bool(include_bg)), float(ce_weight))
+
+
+class UNETRPlan(_PlanBase):
     """One spff_unetr plan (UNETR variant) + its workspace.  The plan's input is the padded
     volume [B, Cin, depth, height, width]; when that differs from ``img`` the engine resamples
     to ``img`` and the logits back."""
 
+    PREFIX, CFG, NAME = "spff_unetr", spff_unetr_cfg, "UNETR"
+
     def __init__(self, batch, in_ch, depth, height, width, num_classes, img=(96, 96, 96),
                  feature_size=16, hidden=768, mlp_dim=3072, heads=12, device=None, math=None):
-        math = math or default_math()
-        if math not in MATH_NAMES:
-            raise SpffError(f"math={math!r}: expected one of {sorted(MATH_NAMES)}")
-        cfg = spff_unetr_cfg()
-        cfg.batch, cfg.in_ch, cfg.depth, cfg.height, cfg.width = batch, in_ch, depth, height, width
+        super().__init__(batch, in_ch, depth, height, width, num_classes, device, math, img=img,
+                         feature_size=feature_size, hidden=hidden, mlp_dim=mlp_dim, heads=heads)
+
+    def _fill_cfg(self, cfg, img, feature_size, hidden, mlp_dim, heads):
         for i, v in enumerate(img):
             cfg.img[i] = int(v)
-        cfg.num_classes, cfg.feature_size = num_classes, feature_size
-        cfg.hidden, cfg.mlp_dim, cfg.heads = hidden, mlp_dim, heads
-        cfg.math = MATH_NAMES[math]
-        self.cfg, self.math, self.device = cfg, math, device
-        L = lib()
-        h = ctypes.c_void_p()
-        check(L.spff_unetr_create(ctypes.byref(cfg), ctypes.byref(h)), "spff_unetr_create")
-        self._h = h
-        self.params: List[Tuple[str, Tuple[int, ...], int, int]] = []
-        for i in range(L.spff_unetr_num_params(h)):
-            name, nd = ctypes.c_char_p(), ctypes.c_int()
-            shape, off, n = (ctypes.c_int64 * 5)(), ctypes.c_int64(), ctypes.c_int64()
-            check(L.spff_unetr_param_info(h, i, ctypes.byref(name), ctypes.byref(nd), shape,
-                                          ctypes.byref(off), ctypes.byref(n)),
-                  "spff_unetr_param_info")
-            self.params.append((name.value.decode(), tuple(shape[k] for k in range(nd.value)),
-                                off.value, n.value))
-        self.nfloats = int(L.spff_unetr_param_floats(h))
-        self.ws_bytes = int(L.spff_unetr_workspace_bytes(h))
-        self._ws: Optional[torch.Tensor] = None
-        self.generation = 0
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None) is not None and _lib is not None:
-                _lib.spff_unetr_destroy(self._h)
-        except Exception:
-            pass
-
-    def workspace(self, device) -> torch.Tensor:
-        if self._ws is None or self._ws.device != device:
-            self._ws = _alloc_workspace(self, device)
-        return self._ws
-
-    def forward(self, x: torch.Tensor, flat: torch.Tensor,
-                out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """x [B,Cin,D,H,W] fp32 -> logits channel-last [B,D,H,W,K]."""
-        c = self.cfg
-        require_device(x, "UNETR forward")
-        if tuple(x.shape) != (c.batch, c.in_ch, c.depth, c.height, c.width):
-            raise SpffError(f"input shape {tuple(x.shape)} does not match plan")
-        if x.dtype != torch.float32:
-            raise SpffError("the engine computes in fp32; got " + str(x.dtype))
-        x = x.contiguous()
-        if out is None:
-            out = torch.empty((c.batch, c.depth, c.height, c.width, c.num_classes),
-                              dtype=torch.float32, device=x.device)
-        ws = self.workspace(x.device)
-        self.generation += 1
-        check(lib().spff_unetr_forward(self._h, _ptr(x), _ptr(flat), _ptr(out), _ptr(ws),
-                                       _stream(x.device)), "spff_unetr_forward")
-        return out
-
-    def backward(self, dlogits_cl: torch.Tensor, flat: torch.Tensor,
-                 dflat: Optional[torch.Tensor] = None, grad_hook=None) -> torch.Tensor:
-        """``grad_hook`` as UNet3DPlan.backward: the whole gradient at once."""
-        dlogits_cl = dlogits_cl.contiguous()
-        if dflat is None:
-            dflat = torch.empty(self.nfloats, dtype=torch.float32, device=dlogits_cl.device)
-        ws = self.workspace(dlogits_cl.device)
-        check(lib().spff_unetr_backward(self._h, _ptr(dlogits_cl), _ptr(flat), _ptr(dflat),
-                                        _ptr(ws), _stream(dlogits_cl.device)),
-              "spff_unetr_backward")
-        _whole_buffer_hook(grad_hook, dflat)
-        return dflat
-
-    def saved(self, name: str) -> torch.Tensor:
-        ws = self._ws
-        if ws is None:
-            raise SpffError("no forward has run")
-        ptr, nv, ch = ctypes.c_void_p(), ctypes.c_int64(), ctypes.c_int()
-        check(lib().spff_unetr_saved_tensor(self._h, _ptr(ws), name.encode(), ctypes.byref(ptr),
-                                            ctypes.byref(nv), ctypes.byref(ch)),
-              "spff_unetr_saved_tensor")
-        off = ptr.value - ws.data_ptr()
-        n = nv.value * ch.value
-        return ws[off:off + 4 * n].view(torch.float32).view(nv.value, ch.value).clone()
+        cfg.feature_size, cfg.hidden, cfg.mlp_dim, cfg.heads = feature_size, hidden, mlp_dim, heads
 
 
 def get_unetr_plan(owner=None, tag: str = "", **kw) -> UNETRPlan:
-    """UNETR plans, owned like get_plan."""
-    key = ("unetr", kw["batch"], kw["in_ch"], kw["depth"], kw["height"], kw["width"],
-           kw["num_classes"], tuple(kw.get("img", (96, 96, 96))), kw.get("feature_size", 16),
-           kw.get("hidden", 768), kw.get("mlp_dim", 3072), kw.get("heads", 12),
-           kw.get("math") or default_math())
-    return _owned_plan(owner, "unetr:" + tag, key, lambda: UNETRPlan(**kw))
+    return _get_variant_plan(UNETRPlan, owner, tag, kw)
 
 
 def _vit_shape(qkv: torch.Tensor, batch: int, heads: int) -> Tuple[int, int]:
@@ -1182,100 +1009,25 @@ def resize3d_bwd(dy_cl: torch.Tensor, in_size) -> torch.Tensor:
     return dx
 
 
-class R2UPlan:
+class R2UPlan(_PlanBase):
     """Engine plan of the R2UNet3D variant (include/spff.h spff_r2u_*): the recurrent
     residual U-Net backbone + 1x1x1 head of LitR2UNet3D_Published.  Parameters are one
     flat fp32 buffer in the Lit module's state-dict order and names (``params``); D, H
     and W are multiples of 16 (the wrapper pads and crops)."""
 
+    PREFIX, CFG, NAME = "spff_r2u", spff_r2u_cfg, "R2UNet3D"
+
     def __init__(self, batch, in_ch, depth, height, width, num_classes, base=16, t=2,
                  device=None, math=None):
-        math = default_math() if math is None else math
-        if math not in MATH_NAMES:
-            raise SpffError(f"math={math!r}: expected one of {sorted(MATH_NAMES)}")
-        cfg = spff_r2u_cfg()
-        cfg.batch, cfg.in_ch, cfg.depth, cfg.height, cfg.width = batch, in_ch, depth, height, width
-        cfg.num_classes, cfg.base, cfg.t = num_classes, base, int(t)
-        cfg.math = MATH_NAMES[math]
-        self.cfg, self.math, self.device = cfg, math, device
-        L = lib()
-        h = ctypes.c_void_p()
-        check(L.spff_r2u_create(ctypes.byref(cfg), ctypes.byref(h)), "spff_r2u_create")
-        self._h = h
-        self.params: List[Tuple[str, Tuple[int, ...], int, int]] = []
-        for i in range(L.spff_r2u_num_params(h)):
-            name, nd = ctypes.c_char_p(), ctypes.c_int()
-            shape, off, n = (ctypes.c_int64 * 5)(), ctypes.c_int64(), ctypes.c_int64()
-            check(L.spff_r2u_param_info(h, i, ctypes.byref(name), ctypes.byref(nd), shape,
-                                        ctypes.byref(off), ctypes.byref(n)),
-                  "spff_r2u_param_info")
-            self.params.append((name.value.decode(), tuple(shape[k] for k in range(nd.value)),
-                                off.value, n.value))
-        self.nfloats = int(L.spff_r2u_param_floats(h))
-        self.ws_bytes = int(L.spff_r2u_workspace_bytes(h))
-        self._ws: Optional[torch.Tensor] = None
-        self.generation = 0
+        super().__init__(batch, in_ch, depth, height, width, num_classes, device, math,
+                         base=base, t=t)
 
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None) is not None and _lib is not None:
-                _lib.spff_r2u_destroy(self._h)
-        except Exception:
-            pass
-
-    def workspace(self, device) -> torch.Tensor:
-        if self._ws is None or self._ws.device != device:
-            self._ws = _alloc_workspace(self, device)
-        return self._ws
-
-    def forward(self, x: torch.Tensor, flat: torch.Tensor,
-                out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """x [B,Cin,D,H,W] fp32 -> logits channel-last [B,D,H,W,K]."""
-        c = self.cfg
-        require_device(x, "R2UNet3D forward")
-        if tuple(x.shape) != (c.batch, c.in_ch, c.depth, c.height, c.width):
-            raise SpffError(f"input shape {tuple(x.shape)} does not match plan")
-        if x.dtype != torch.float32:
-            raise SpffError("the engine computes in fp32; got " + str(x.dtype))
-        x = x.contiguous()
-        if out is None:
-            out = torch.empty((c.batch, c.depth, c.height, c.width, c.num_classes),
-                              dtype=torch.float32, device=x.device)
-        ws = self.workspace(x.device)
-        self.generation += 1
-        check(lib().spff_r2u_forward(self._h, _ptr(x), _ptr(flat), _ptr(out), _ptr(ws),
-                                     _stream(x.device)), "spff_r2u_forward")
-        return out
-
-    def backward(self, dlogits_cl: torch.Tensor, flat: torch.Tensor,
-                 grad_hook=None) -> torch.Tensor:
-        """``grad_hook`` as UNet3DPlan.backward: the whole gradient at once."""
-        dlogits_cl = dlogits_cl.contiguous()
-        dflat = torch.empty(self.nfloats, dtype=torch.float32, device=dlogits_cl.device)
-        ws = self.workspace(dlogits_cl.device)
-        check(lib().spff_r2u_backward(self._h, _ptr(dlogits_cl), _ptr(flat), _ptr(dflat), _ptr(ws),
-                                      _stream(dlogits_cl.device)), "spff_r2u_backward")
-        _whole_buffer_hook(grad_hook, dflat)
-        return dflat
-
-    def saved(self, name: str) -> torch.Tensor:
-        ws = self._ws
-        if ws is None:
-            raise SpffError("no forward has run")
-        ptr, nv, ch = ctypes.c_void_p(), ctypes.c_int64(), ctypes.c_int()
-        check(lib().spff_r2u_saved_tensor(self._h, _ptr(ws), name.encode(), ctypes.byref(ptr),
-                                          ctypes.byref(nv), ctypes.byref(ch)),
-              "spff_r2u_saved_tensor")
-        off = ptr.value - ws.data_ptr()
-        n = nv.value * ch.value
-        return ws[off:off + 4 * n].view(torch.float32).view(nv.value, ch.value).clone()
+    def _fill_cfg(self, cfg, base, t):
+        cfg.base, cfg.t = base, int(t)
 
 
 def get_r2u_plan(owner=None, tag: str = "", **kw) -> R2UPlan:
-    """R2UNet3D plans, owned like get_plan."""
-    key = ("r2u", kw["batch"], kw["in_ch"], kw["depth"], kw["height"], kw["width"],
-           kw["num_classes"], kw.get("base", 16), kw.get("t", 2), kw.get("math") or default_math())
-    return _owned_plan(owner, "r2u:" + tag, key, lambda: R2UPlan(**kw))
+    return _get_variant_plan(R2UPlan, owner, tag, kw)
 
 
 def r2u_dice_loss_forward(logits_cl: torch.Tensor, labels: torch.Tensor, K: int,
@@ -1283,121 +1035,29 @@ def r2u_dice_loss_forward(logits_cl: torch.Tensor, labels: torch.Tensor, K: int,
     """LitR2UNet3D_Published._dice_only_loss_with_logits (multi-class branch) on the HIP
     kernels: returns (out4 = [dice, loss, kept_samples, N_valid], dlogits_cl).
     ``ignore_index`` None: no voxel is masked."""
-    require_device(logits_cl, "R2UNet3D loss")
-    logits_cl = logits_cl.contiguous()
-    B = logits_cl.shape[0]
-    labels = labels.to(device=logits_cl.device, dtype=torch.int64).contiguous()
-    V = labels.numel()
-    if logits_cl.numel() != V * K or V % B:
-        raise SpffError(f"logits ({tuple(logits_cl.shape)}) / labels ({tuple(labels.shape)}) mismatch")
-    dev = logits_cl.device
-    out4 = torch.empty(4, dtype=torch.float32, device=dev)
-    dl = torch.empty_like(logits_cl)
-    ws = torch.empty(int(lib().spff_r2u_dice_loss_ws_bytes(B, K)), dtype=torch.uint8, device=dev)
-    check(lib().spff_r2u_dice_loss(_ptr(logits_cl), _ptr(labels), B, V // B, K,
-                                   int(ignore_index is not None),
-                                   int(ignore_index) if ignore_index is not None else 0,
-                                   _ptr(out4), _ptr(dl), _ptr(ws), _stream(dev)),
-          "spff_r2u_dice_loss")
-    return out4, dl
+    return _variant_loss("R2UNet3D", "spff_r2u_dice_loss", logits_cl, labels, K,
+                         *_ignore_args(ignore_index))
 
 
-class RUPPPlan:
+class RUPPPlan(_PlanBase):
     """Engine plan of the ResUNet++ variant (include/spff.h spff_rupp_*): residual units,
     ASPP bottleneck, SE and attention-gated skips + the 1x1x1 head of
     LitResUNetPP3D_Published.  Parameters are one flat fp32 buffer in the Lit module's
     named_parameters() order and names (``params``); D, H and W are multiples of 16 (the
     wrapper pads and crops)."""
 
+    PREFIX, CFG, NAME = "spff_rupp", spff_rupp_cfg, "ResUNet++"
+
     def __init__(self, batch, in_ch, depth, height, width, num_classes, base=16,
                  device=None, math=None):
-        math = default_math() if math is None else math
-        if math not in MATH_NAMES:
-            raise SpffError(f"math={math!r}: expected one of {sorted(MATH_NAMES)}")
-        cfg = spff_rupp_cfg()
-        cfg.batch, cfg.in_ch, cfg.depth, cfg.height, cfg.width = batch, in_ch, depth, height, width
-        cfg.num_classes, cfg.base = num_classes, base
-        cfg.math = MATH_NAMES[math]
-        self.cfg, self.math, self.device = cfg, math, device
-        L = lib()
-        h = ctypes.c_void_p()
-        check(L.spff_rupp_create(ctypes.byref(cfg), ctypes.byref(h)), "spff_rupp_create")
-        self._h = h
-        self.params: List[Tuple[str, Tuple[int, ...], int, int]] = []
-        for i in range(L.spff_rupp_num_params(h)):
-            name, nd = ctypes.c_char_p(), ctypes.c_int()
-            shape, off, n = (ctypes.c_int64 * 5)(), ctypes.c_int64(), ctypes.c_int64()
-            check(L.spff_rupp_param_info(h, i, ctypes.byref(name), ctypes.byref(nd), shape,
-                                         ctypes.byref(off), ctypes.byref(n)),
-                  "spff_rupp_param_info")
-            self.params.append((name.value.decode(), tuple(shape[k] for k in range(nd.value)),
-                                off.value, n.value))
-        self.nfloats = int(L.spff_rupp_param_floats(h))
-        self.ws_bytes = int(L.spff_rupp_workspace_bytes(h))
-        self._ws: Optional[torch.Tensor] = None
-        self.generation = 0
+        super().__init__(batch, in_ch, depth, height, width, num_classes, device, math, base=base)
 
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None) is not None and _lib is not None:
-                _lib.spff_rupp_destroy(self._h)
-        except Exception:
-            pass
-
-    def workspace(self, device) -> torch.Tensor:
-        if self._ws is None or self._ws.device != device:
-            self._ws = _alloc_workspace(self, device)
-        return self._ws
-
-    def forward(self, x: torch.Tensor, flat: torch.Tensor,
-                out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """x [B,Cin,D,H,W] fp32 -> logits channel-last [B,D,H,W,K]."""
-        c = self.cfg
-        require_device(x, "ResUNet++ forward")
-        if tuple(x.shape) != (c.batch, c.in_ch, c.depth, c.height, c.width):
-            raise SpffError(f"input shape {tuple(x.shape)} does not match plan")
-        if x.dtype != torch.float32:
-            raise SpffError("the engine computes in fp32; got " + str(x.dtype))
-        x = x.contiguous()
-        if out is None:
-            out = torch.empty((c.batch, c.depth, c.height, c.width, c.num_classes),
-                              dtype=torch.float32, device=x.device)
-        ws = self.workspace(x.device)
-        self.generation += 1
-        check(lib().spff_rupp_forward(self._h, _ptr(x), _ptr(flat), _ptr(out), _ptr(ws),
-                                      _stream(x.device)), "spff_rupp_forward")
-        return out
-
-    def backward(self, dlogits_cl: torch.Tensor, flat: torch.Tensor,
-                 grad_hook=None) -> torch.Tensor:
-        """``grad_hook`` as UNet3DPlan.backward: the whole gradient at once."""
-        dlogits_cl = dlogits_cl.contiguous()
-        dflat = torch.empty(self.nfloats, dtype=torch.float32, device=dlogits_cl.device)
-        ws = self.workspace(dlogits_cl.device)
-        check(lib().spff_rupp_backward(self._h, _ptr(dlogits_cl), _ptr(flat), _ptr(dflat),
-                                       _ptr(ws), _stream(dlogits_cl.device)),
-              "spff_rupp_backward")
-        _whole_buffer_hook(grad_hook, dflat)
-        return dflat
-
-    def saved(self, name: str) -> torch.Tensor:
-        ws = self._ws
-        if ws is None:
-            raise SpffError("no forward has run")
-        ptr, nv, ch = ctypes.c_void_p(), ctypes.c_int64(), ctypes.c_int()
-        check(lib().spff_rupp_saved_tensor(self._h, _ptr(ws), name.encode(), ctypes.byref(ptr),
-                                           ctypes.byref(nv), ctypes.byref(ch)),
-              "spff_rupp_saved_tensor")
-        off = ptr.value - ws.data_ptr()
-        n = nv.value * ch.value
-        return ws[off:off + 4 * n].view(torch.float32).view(nv.value, ch.value).clone()
+    def _fill_cfg(self, cfg, base):
+        cfg.base = base
 
 
 def get_rupp_plan(owner=None, tag: str = "", **kw) -> RUPPPlan:
-    """ResUNet++ plans, owned like get_plan."""
-    key = ("rupp", kw["batch"], kw["in_ch"], kw["depth"], kw["height"], kw["width"],
-           kw["num_classes"], kw.get("base", 16), kw.get("math") or default_math())
-    return _owned_plan(owner, "rupp:" + tag, key, lambda: RUPPPlan(**kw))
+    return _get_variant_plan(RUPPPlan, owner, tag, kw)
 
 
 def rupp_loss_forward(logits_cl: torch.Tensor, labels: torch.Tensor, K: int,
@@ -1406,24 +1066,9 @@ def rupp_loss_forward(logits_cl: torch.Tensor, labels: torch.Tensor, K: int,
     """dice_ce_loss_with_metrics (LitResUNetPP3D_Published._loss) on the HIP kernels:
     returns (out4 = [ce, loss, dice_mean, N_valid], dlogits_cl).  Dice sums are pooled over
     the whole batch; ``ignore_index`` None: no voxel is masked."""
-    require_device(logits_cl, "ResUNet++ loss")
-    logits_cl = logits_cl.contiguous()
-    B = logits_cl.shape[0]
-    labels = labels.to(device=logits_cl.device, dtype=torch.int64).contiguous()
-    V = labels.numel()
-    if logits_cl.numel() != V * K or V % B:
-        raise SpffError(f"logits ({tuple(logits_cl.shape)}) / labels ({tuple(labels.shape)}) mismatch")
-    dev = logits_cl.device
-    out4 = torch.empty(4, dtype=torch.float32, device=dev)
-    dl = torch.empty_like(logits_cl)
-    ws = torch.empty(int(lib().spff_rupp_loss_ws_bytes(B, K)), dtype=torch.uint8, device=dev)
-    check(lib().spff_rupp_loss(_ptr(logits_cl), _ptr(labels), B, V // B, K,
-                               int(ignore_index is not None),
-                               int(ignore_index) if ignore_index is not None else 0,
-                               int(bool(include_bg)), float(ce_weight), float(dice_weight),
-                               _ptr(out4), _ptr(dl), _ptr(ws), _stream(dev)),
-          "spff_rupp_loss")
-    return out4, dl
+    return _variant_loss("ResUNet++", "spff_rupp_loss", logits_cl, labels, K,
+                         *_ignore_args(ignore_index), int(bool(include_bg)), float(ce_weight),
+                         float(dice_weight))
 
 
 # ------------------------------------------------------------- data path ops --

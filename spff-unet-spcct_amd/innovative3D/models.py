@@ -92,7 +92,6 @@ def _center_crop_to_3d(x: torch.Tensor, orig_dhw):
     return x[:, :, sd:sd + D, sh:sh + H, sw:sw + W]
 
 
-_pad_to_mult16_3d = lambda x, multiple=16: _pad_to_mult_3d(x, m=int(multiple))  # noqa: E731
 _center_crop_3d = _center_crop_to_3d
 
 
@@ -194,18 +193,18 @@ def _mark_covered(grad_hook, param_ids) -> None:
         grad_hook.cover(param_ids)
 
 
-class _SPFFFunction(torch.autograd.Function):
+class _PlanFunction(torch.autograd.Function):
+    """One forward / backward of an engine plan (any E._PlanBase) as an autograd node.
+    ``extra``: the plan's own forward arguments after ``flat`` -- (bufs, training) for the
+    3DUNet, () otherwise."""
+
     @staticmethod
-    def forward(ctx, x, core, flat, *params):
-        plan = core._plan
-        logits_cl = plan.forward(x, flat)
-        ctx.plan = plan
-        ctx.gen = plan.generation
-        ctx.flat = flat
+    def forward(ctx, x, plan, flat, grad_hook, extra, *params):
+        logits_cl = plan.forward(x, flat, *extra)
+        ctx.plan, ctx.gen, ctx.flat, ctx.grad_hook = plan, plan.generation, flat, grad_hook
         # a backward is pending on this workspace (E._alloc_workspace releases other
         # plans' workspaces on OOM, pending ones only as a last resort)
         plan._pending_gen = plan.generation if any(ctx.needs_input_grad) else None
-        ctx.grad_hook = getattr(core, "grad_hook", None)
         ctx.param_ids = tuple(id(p) for p in params)
         ctx.slices = [(off, n, shape) for (_name, shape, off, n) in plan.params]
         return logits_cl.permute(0, 4, 1, 2, 3)
@@ -214,24 +213,71 @@ class _SPFFFunction(torch.autograd.Function):
     def backward(ctx, g):
         plan = ctx.plan
         if plan.generation != ctx.gen:
-            raise E.SpffError("SPFF engine: another forward ran on this model (or its cached workspace "
-                              "was released for another plan's) before the backward "
-                              "of this one; the engine keeps one forward's activations per model")
-        g_cl = g.permute(0, 2, 3, 4, 1)
-        if not g_cl.is_contiguous():
-            g_cl = g_cl.contiguous()
+            if isinstance(plan, E.Plan):
+                raise E.SpffError("SPFF engine: another forward ran on this model (or its cached "
+                                  "workspace was released for another plan's) before the backward "
+                                  "of this one; the engine keeps one forward's activations per model")
+            raise E.SpffError(f"{plan.NAME} engine: another forward ran on this model before the "
+                              "backward of this one; the engine keeps one forward's activations")
+        g_cl = g.permute(0, 2, 3, 4, 1).contiguous()
         dflat = plan.backward(g_cl, ctx.flat, grad_hook=ctx.grad_hook)
         plan._pending_gen = None
         _mark_covered(ctx.grad_hook, ctx.param_ids)
         grads = [dflat[o:o + n].view(s) for (o, n, s) in ctx.slices]
-        return (None, None, None, *grads)
+        return (None, None, None, None, None, *grads)
+
+
+class _FlatParamMixin:
+    """For a module whose Parameters are views into its plan's one flat fp32 buffer, under
+    the plan's parameter names: every engine-backed module here."""
+
+    _DUPLICATE_PARAMS = False  # True: tied parameters keep every name they are registered under
+
+    def _engine_params(self, plan) -> List[nn.Parameter]:
+        named = dict(self.named_parameters(remove_duplicate=not self._DUPLICATE_PARAMS))
+        out = []
+        for name, shape, _off, _n in plan.params:
+            p = named.get(name)
+            if p is None or tuple(p.shape) != tuple(shape):
+                raise E.SpffError(f"parameter {name} {shape} missing or mis-shaped in the module")
+            out.append(p)
+        return out
+
+    def _ensure_flat(self, plan, params, device) -> torch.Tensor:
+        flat = self._flat
+        ok = flat is not None and flat.device == device and flat.numel() == plan.nfloats
+        if ok:
+            base = flat.data_ptr()
+            ok = all(p.data_ptr() == base + 4 * off and p.dtype == torch.float32
+                     for p, (_n, _s, off, _k) in zip(params, plan.params))
+        if not ok:
+            flat = torch.empty(plan.nfloats, dtype=torch.float32, device=device)
+            with torch.no_grad():
+                for p, (_name, shape, off, n) in zip(params, plan.params):
+                    flat[off:off + n].copy_(p.detach().reshape(-1).to(device=device,
+                                                                     dtype=torch.float32))
+                    p.data = flat[off:off + n].view(shape)
+            self._flat = flat
+        return flat
+
+    def _run_plan(self, plan, x, extra=()):
+        """x [B,Cin,D,H,W] -> logits [B,K,D,H,W] of ``plan`` on this module's parameters,
+        through autograd when a gradient is wanted (``extra``: see _PlanFunction)."""
+        params = self._engine_params(plan)
+        flat = self._ensure_flat(plan, params, x.device)
+        if torch.is_grad_enabled() and any(p.requires_grad for p in params):
+            return _PlanFunction.apply(x.float(), plan, flat, getattr(self, "grad_hook", None),
+                                       extra, *params)
+        return plan.forward(x.float(), flat, *extra).permute(0, 4, 1, 2, 3)
 
 
 # -------------------------------------------------------------------- core ----
-class UNet3D_SpectralCore(nn.Module):
+class UNet3D_SpectralCore(_FlatParamMixin, nn.Module):
     """Depth-preserving 3-level UNet (models.py:647-701).  forward runs on the
     HIP engine; pool/upsample act in (H,W) only, so D is arbitrary while H, W
     must be multiples of 8."""
+
+    _DUPLICATE_PARAMS = True
 
     def __init__(self, in_channels=1, num_classes=2, base=32, ksd=3, use_se=False,
                  use_specse=False, use_spatial=False, use_skip_gate=False, norm="instance",
@@ -321,35 +367,6 @@ class UNet3D_SpectralCore(nn.Module):
                 plan.set_coll(coll)
         return plan
 
-    def _engine_params(self, plan) -> List[nn.Parameter]:
-        named = dict(self.named_parameters(remove_duplicate=False))
-        out = []
-        for name, shape, _off, _n in plan.params:
-            p = named.get(name)
-            if p is None or tuple(p.shape) != tuple(shape):
-                raise E.SpffError(f"parameter {name} {shape} missing or mis-shaped in the module")
-            out.append(p)
-        return out
-
-    def _ensure_flat(self, plan, params, device) -> torch.Tensor:
-        flat = self._flat
-        ok = flat is not None and flat.device == device and flat.numel() == plan.nfloats
-        if ok:
-            base = flat.data_ptr()
-            for p, (_name, _shape, off, _n) in zip(params, plan.params):
-                if p.data_ptr() != base + 4 * off or p.dtype != torch.float32:
-                    ok = False
-                    break
-        if ok:
-            return flat
-        flat = torch.empty(plan.nfloats, dtype=torch.float32, device=device)
-        with torch.no_grad():
-            for p, (_name, shape, off, n) in zip(params, plan.params):
-                flat[off:off + n].copy_(p.detach().reshape(-1).to(device=device, dtype=torch.float32))
-                p.data = flat[off:off + n].view(shape)
-        self._flat = flat
-        return flat
-
     def forward(self, x):
         x = _pick_first_if_seq(x)
         E.require_device(x, "UNet3D_SpectralCore.forward")
@@ -359,7 +376,8 @@ class UNet3D_SpectralCore(nn.Module):
         flat = self._ensure_flat(plan, params, x.device)
         if need_grad:
             self._plan = plan
-            return _SPFFFunction.apply(x.float(), self, flat, *params)
+            return _PlanFunction.apply(x.float(), plan, flat, getattr(self, "grad_hook", None), (),
+                                       *params)
         logits_cl = plan.forward(x.float(), flat)
         return logits_cl.permute(0, 4, 1, 2, 3)
 
@@ -469,7 +487,7 @@ class _LitSPCT_Base(BaseLitModel):
         x = _pick_first_if_seq(x)
         if x.ndim == 4:
             x = x.unsqueeze(1)
-        x_pad, orig = _pad_to_mult16_3d(x, multiple=self._pad_multiple)
+        x_pad, orig = _pad_to_mult_3d(x, self._pad_multiple)
         return _center_crop_3d(self.model(x_pad), orig)
 
 
@@ -528,33 +546,7 @@ class LitSPCT_ControlUNet(BaseLitModel):
 # config.py:283-311): Cicek3DUNet (models.py:718-753) + the depth-adapter
 # Lightning wrapper (models.py:756-853), on the engine's spff_unet3d plan.
 # ============================================================================
-class _UNet3DFunction(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, plan, flat, bufs, training, grad_hook, *params):
-        logits_cl = plan.forward(x, flat, bufs, training)
-        ctx.plan, ctx.gen, ctx.flat, ctx.grad_hook = plan, plan.generation, flat, grad_hook
-        # a backward is pending on this workspace (E._alloc_workspace releases other
-        # plans' workspaces on OOM, pending ones only as a last resort)
-        plan._pending_gen = plan.generation if any(ctx.needs_input_grad) else None
-        ctx.param_ids = tuple(id(p) for p in params)
-        ctx.slices = [(off, n, shape) for (_name, shape, off, n) in plan.params]
-        return logits_cl.permute(0, 4, 1, 2, 3)
-
-    @staticmethod
-    def backward(ctx, g):
-        plan = ctx.plan
-        if plan.generation != ctx.gen:
-            raise E.SpffError("3DUNet engine: another forward ran on this model before the "
-                              "backward of this one; the engine keeps one forward's activations")
-        g_cl = g.permute(0, 2, 3, 4, 1).contiguous()
-        dflat = plan.backward(g_cl, ctx.flat, grad_hook=ctx.grad_hook)
-        plan._pending_gen = None
-        _mark_covered(ctx.grad_hook, ctx.param_ids)
-        grads = [dflat[o:o + n].view(s) for (o, n, s) in ctx.slices]
-        return (None, None, None, None, None, None, *grads)
-
-
-class Cicek3DUNet(nn.Module):
+class Cicek3DUNet(_FlatParamMixin, nn.Module):
     """models.py:718-753.  Same module tree / state-dict keys as the reference
     (enc1.0.weight, enc1.1.running_mean, ..., up4.weight, out.bias); the
     Conv3d / BatchNorm3d children are parameter containers and forward runs on
@@ -609,33 +601,6 @@ class Cicek3DUNet(nn.Module):
                                  device=x.device, math=getattr(self, "math", None),
                                  owner=self)
 
-    def _engine_params(self, plan):
-        named = dict(self.named_parameters())
-        out = []
-        for name, shape, _off, _n in plan.params:
-            p = named.get(name)
-            if p is None or tuple(p.shape) != tuple(shape):
-                raise E.SpffError(f"parameter {name} {shape} missing or mis-shaped in the module")
-            out.append(p)
-        return out
-
-    def _ensure_flat(self, plan, params, device):
-        flat = self._flat
-        ok = flat is not None and flat.device == device and flat.numel() == plan.nfloats
-        if ok:
-            base = flat.data_ptr()
-            ok = all(p.data_ptr() == base + 4 * off and p.dtype == torch.float32
-                     for p, (_n, _s, off, _k) in zip(params, plan.params))
-        if not ok:
-            flat = torch.empty(plan.nfloats, dtype=torch.float32, device=device)
-            with torch.no_grad():
-                for p, (_name, shape, off, n) in zip(params, plan.params):
-                    flat[off:off + n].copy_(p.detach().reshape(-1).to(device=device,
-                                                                     dtype=torch.float32))
-                    p.data = flat[off:off + n].view(shape)
-            self._flat = flat
-        return flat
-
     def _ensure_bufs(self, plan, device):
         named = dict(self.named_buffers())
         bufs = self._bufs
@@ -664,8 +629,6 @@ class Cicek3DUNet(nn.Module):
         E.require_device(x, "Cicek3DUNet.forward")
         self._check_bn()
         plan = self._plan(x, target_depth)
-        params = self._engine_params(plan)
-        flat = self._ensure_flat(plan, params, x.device)
         bufs = self._ensure_bufs(plan, x.device)
         plan.workspace(x.device)
         # data parallelism with synchronised BatchNorm: ``self.sync_bn`` = a collective with
@@ -680,11 +643,7 @@ class Cicek3DUNet(nn.Module):
             with torch.no_grad():
                 for m in self._bn_modules():
                     m.num_batches_tracked.add_(1)
-        need_grad = torch.is_grad_enabled() and any(p.requires_grad for p in params)
-        if need_grad:
-            return _UNet3DFunction.apply(x.float(), plan, flat, bufs, training,
-                                         getattr(self, "grad_hook", None), *params)
-        return plan.forward(x.float(), flat, bufs, training).permute(0, 4, 1, 2, 3)
+        return self._run_plan(plan, x, (bufs, training))
 
     def forward(self, x):
         return self.run(x, 0)
@@ -818,33 +777,6 @@ class LitCicek3DUNet_DepthAdapter_Published(pl.LightningModule):
 # names; forward runs on the HIP engine.  Parity unpinned (no MONAI offline):
 # semantics in oracle/swin_oracle.py.
 # ============================================================================
-class _SwinFunction(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, plan, flat, grad_hook, *params):
-        logits_cl = plan.forward(x, flat)
-        ctx.plan, ctx.gen, ctx.flat, ctx.grad_hook = plan, plan.generation, flat, grad_hook
-        ctx.plan_name = "UNETR" if isinstance(plan, E.UNETRPlan) else "SwinUNETR"
-        # a backward is pending on this workspace (E._alloc_workspace releases other
-        # plans' workspaces on OOM, pending ones only as a last resort)
-        plan._pending_gen = plan.generation if any(ctx.needs_input_grad) else None
-        ctx.param_ids = tuple(id(p) for p in params)
-        ctx.slices = [(off, n, shape) for (_name, shape, off, n) in plan.params]
-        return logits_cl.permute(0, 4, 1, 2, 3)
-
-    @staticmethod
-    def backward(ctx, g):
-        plan = ctx.plan
-        if plan.generation != ctx.gen:
-            raise E.SpffError(f"{ctx.plan_name} engine: another forward ran on this model before the "
-                              "backward of this one; the engine keeps one forward's activations")
-        g_cl = g.permute(0, 2, 3, 4, 1).contiguous()
-        dflat = plan.backward(g_cl, ctx.flat, grad_hook=ctx.grad_hook)
-        plan._pending_gen = None
-        _mark_covered(ctx.grad_hook, ctx.param_ids)
-        grads = [dflat[o:o + n].view(s) for (o, n, s) in ctx.slices]
-        return (None, None, None, None, *grads)
-
-
 class _Holder(nn.Module):
     """Parameter container (MONAI module names; no forward)."""
 
@@ -901,36 +833,8 @@ class _BasicLayerP(nn.Module):
         self.downsample.norm = nn.LayerNorm(8 * dim)
 
 
-class _FlatParamModule(nn.Module):
-    """A MONAI-named parameter tree whose Parameters are views into the plan's one flat fp32
-    buffer (SwinUNETR, UNETR)."""
-
-    def _engine_params(self, plan):
-        named = dict(self.named_parameters())
-        out = []
-        for name, shape, _off, _n in plan.params:
-            p = named.get(name)
-            if p is None or tuple(p.shape) != tuple(shape):
-                raise E.SpffError(f"parameter {name} {shape} missing or mis-shaped in the module")
-            out.append(p)
-        return out
-
-    def _ensure_flat(self, plan, params, device):
-        flat = self._flat
-        ok = flat is not None and flat.device == device and flat.numel() == plan.nfloats
-        if ok:
-            base = flat.data_ptr()
-            ok = all(p.data_ptr() == base + 4 * off and p.dtype == torch.float32
-                     for p, (_n, _s, off, _k) in zip(params, plan.params))
-        if not ok:
-            flat = torch.empty(plan.nfloats, dtype=torch.float32, device=device)
-            with torch.no_grad():
-                for p, (_name, shape, off, n) in zip(params, plan.params):
-                    flat[off:off + n].copy_(p.detach().reshape(-1).to(device=device,
-                                                                     dtype=torch.float32))
-                    p.data = flat[off:off + n].view(shape)
-            self._flat = flat
-        return flat
+class _FlatParamModule(_FlatParamMixin, nn.Module):
+    """A MONAI-named parameter tree on one engine plan (SwinUNETR, UNETR)."""
 
 
 class SwinUNETR(_FlatParamModule):
@@ -995,13 +899,7 @@ class SwinUNETR(_FlatParamModule):
 
     def forward(self, x_in):
         E.require_device(x_in, "SwinUNETR.forward")
-        plan = self._plan(x_in)
-        params = self._engine_params(plan)
-        flat = self._ensure_flat(plan, params, x_in.device)
-        if torch.is_grad_enabled() and any(p.requires_grad for p in params):
-            return _SwinFunction.apply(x_in.float(), plan, flat, getattr(self, "grad_hook", None),
-                                       *params)
-        return plan.forward(x_in.float(), flat).permute(0, 4, 1, 2, 3)
+        return self._run_plan(self._plan(x_in), x_in)
 
 
 class SwinUNETR_Published(nn.Module):
@@ -1136,7 +1034,7 @@ class LitSwinUNETR_Published(_DiceCEWarmupLit):
         x = _pick_first_if_seq(x)
         if x.ndim == 4:
             x = x.unsqueeze(1)
-        x_pad, orig = _pad_to_mult16_3d(x, multiple=32)
+        x_pad, orig = _pad_to_mult_3d(x, 32)
         y_pad = self.model(x_pad)
         return _center_crop_3d(y_pad, orig)
 
@@ -1147,9 +1045,6 @@ class LitSwinUNETR_Published(_DiceCEWarmupLit):
 # engine's spff_unetr plan (csrc/unetr.hip).  PARITY UNPINNED: MONAI is not
 # available offline; its semantics are restated in tests/_unetr_oracle.py.
 # ============================================================================
-_UNETRFunction = _SwinFunction  # the same hand-over: plan.forward / backward / params
-
-
 class _ViTBlockP(nn.Module):
     """MONAI TransformerBlock's parameters in its registration order.  norm_cross_attn and
     cross_attn are registered by MONAI >= 1.4 in every block and never used without
@@ -1253,13 +1148,7 @@ class UNETR(_FlatParamModule):
         to img_size and the logits back (trilinear, align_corners=False) inside the engine:
         steps 3-5 of LitUNETR_Published.forward."""
         E.require_device(x_in, "UNETR.forward")
-        plan = self._plan(x_in)
-        params = self._engine_params(plan)
-        flat = self._ensure_flat(plan, params, x_in.device)
-        if torch.is_grad_enabled() and any(p.requires_grad for p in params):
-            return _UNETRFunction.apply(x_in.float(), plan, flat, getattr(self, "grad_hook", None),
-                                        *params)
-        return plan.forward(x_in.float(), flat).permute(0, 4, 1, 2, 3)
+        return self._run_plan(self._plan(x_in), x_in)
 
     def forward(self, x_in):
         if tuple(x_in.shape[2:]) != self.img_size:
@@ -1318,7 +1207,7 @@ class LitUNETR_Published(_DiceCEWarmupLit):
         x = _pick_first_if_seq(x)
         if x.ndim == 4:
             x = x.unsqueeze(1)
-        x_pad, orig = _pad_to_mult16_3d(x)
+        x_pad, orig = _pad_to_mult_3d(x)
         y_pad = self.net.net.run(x_pad)
         return _center_crop_3d(y_pad, orig)
 
@@ -1378,30 +1267,6 @@ class R2UNet3D_backbone(nn.Module):
                                   "backbone and head together (LitR2UNet3D_Published.forward)")
 
 
-class _R2UFunction(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, plan, flat, grad_hook, *params):
-        logits_cl = plan.forward(x, flat)
-        ctx.plan, ctx.gen, ctx.flat, ctx.grad_hook = plan, plan.generation, flat, grad_hook
-        plan._pending_gen = plan.generation if any(ctx.needs_input_grad) else None
-        ctx.param_ids = tuple(id(p) for p in params)
-        ctx.slices = [(off, n, shape) for (_name, shape, off, n) in plan.params]
-        return logits_cl.permute(0, 4, 1, 2, 3)
-
-    @staticmethod
-    def backward(ctx, g):
-        plan = ctx.plan
-        if plan.generation != ctx.gen:
-            raise E.SpffError("R2UNet3D engine: another forward ran on this model before the "
-                              "backward of this one; the engine keeps one forward's activations")
-        g_cl = g.permute(0, 2, 3, 4, 1).contiguous()
-        dflat = plan.backward(g_cl, ctx.flat, grad_hook=ctx.grad_hook)
-        plan._pending_gen = None
-        _mark_covered(ctx.grad_hook, ctx.param_ids)
-        grads = [dflat[o:o + n].view(s) for (o, n, s) in ctx.slices]
-        return (None, None, None, None, *grads)
-
-
 class _R2UDiceLoss(torch.autograd.Function):
     """(loss, dice) of the foreground-only soft Dice; dice carries no gradient."""
 
@@ -1420,7 +1285,7 @@ class _R2UDiceLoss(torch.autograd.Function):
         return dl.permute(0, 4, 1, 2, 3), None, None, None
 
 
-class LitR2UNet3D_Published(pl.LightningModule):
+class LitR2UNet3D_Published(_FlatParamMixin, pl.LightningModule):
     """Registry "R2UNet3D": replicate-pad D, H, W to multiples of ``pad_multiple`` ->
     R2UNet3D_backbone -> 1x1x1 head -> centre crop (padding and cropping are torch
     plumbing, backbone and head one engine plan); foreground-only soft-Dice loss over the
@@ -1453,9 +1318,6 @@ class LitR2UNet3D_Published(pl.LightningModule):
                               num_classes=int(self.hparams.num_classes), base=bb.base, t=bb.t,
                               device=x.device, math=getattr(self, "math", None), owner=self)
 
-    _engine_params = _FlatParamModule._engine_params
-    _ensure_flat = _FlatParamModule._ensure_flat
-
     def forward(self, x):
         x = _pick_first_if_seq(x)
         E.require_device(x, "LitR2UNet3D_Published.forward")
@@ -1464,15 +1326,8 @@ class LitR2UNet3D_Published(pl.LightningModule):
         m = int(self.hparams.pad_multiple)
         if m % 16:
             raise NotImplementedError("pad_multiple must be a multiple of 16 (four poolings)")
-        x_pad, orig = _pad_to_mult16_3d(x.float(), multiple=m)
-        plan = self._plan(x_pad)
-        params = self._engine_params(plan)
-        flat = self._ensure_flat(plan, params, x_pad.device)
-        if torch.is_grad_enabled() and any(p.requires_grad for p in params):
-            y = _R2UFunction.apply(x_pad, plan, flat, getattr(self, "grad_hook", None), *params)
-        else:
-            y = plan.forward(x_pad, flat).permute(0, 4, 1, 2, 3)
-        return _center_crop_3d(y, orig)
+        x_pad, orig = _pad_to_mult_3d(x.float(), m)
+        return _center_crop_3d(self._run_plan(self._plan(x_pad), x_pad), orig)
 
     @staticmethod
     def _dice_only_loss_with_logits(logits, y, ignore_index=None, eps=1e-6):
@@ -1605,30 +1460,6 @@ class ResUNetPP3D_backbone(nn.Module):
                                   "(LitResUNetPP3D_Published.forward)")
 
 
-class _RUPPFunction(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, plan, flat, grad_hook, *params):
-        logits_cl = plan.forward(x, flat)
-        ctx.plan, ctx.gen, ctx.flat, ctx.grad_hook = plan, plan.generation, flat, grad_hook
-        plan._pending_gen = plan.generation if any(ctx.needs_input_grad) else None
-        ctx.param_ids = tuple(id(p) for p in params)
-        ctx.slices = [(off, n, shape) for (_name, shape, off, n) in plan.params]
-        return logits_cl.permute(0, 4, 1, 2, 3)
-
-    @staticmethod
-    def backward(ctx, g):
-        plan = ctx.plan
-        if plan.generation != ctx.gen:
-            raise E.SpffError("ResUNet++ engine: another forward ran on this model before the "
-                              "backward of this one; the engine keeps one forward's activations")
-        g_cl = g.permute(0, 2, 3, 4, 1).contiguous()
-        dflat = plan.backward(g_cl, ctx.flat, grad_hook=ctx.grad_hook)
-        plan._pending_gen = None
-        _mark_covered(ctx.grad_hook, ctx.param_ids)
-        grads = [dflat[o:o + n].view(s) for (o, n, s) in ctx.slices]
-        return (None, None, None, None, *grads)
-
-
 class _RUPPLoss(torch.autograd.Function):
     """(loss, out4 = [ce, loss, dice_mean, N_valid]); only the loss carries a gradient."""
 
@@ -1648,7 +1479,7 @@ class _RUPPLoss(torch.autograd.Function):
         return dl.permute(0, 4, 1, 2, 3), None, None, None, None, None, None
 
 
-class LitResUNetPP3D_Published(pl.LightningModule):
+class LitResUNetPP3D_Published(_FlatParamMixin, pl.LightningModule):
     """Registry "ResUNet++": replicate-pad D, H, W to multiples of ``pad_multiple`` ->
     ResUNetPP3D_backbone -> 1x1x1 head -> centre crop (padding and cropping are torch
     plumbing, backbone and head one engine plan); batch-pooled soft Dice + CE on the HIP loss
@@ -1684,23 +1515,13 @@ class LitResUNetPP3D_Published(pl.LightningModule):
                                num_classes=int(self.hparams.num_classes), base=bb.base,
                                device=x.device, math=getattr(self, "math", None), owner=self)
 
-    _engine_params = _FlatParamModule._engine_params
-    _ensure_flat = _FlatParamModule._ensure_flat
-
     def forward(self, x):
         x = _pick_first_if_seq(x)
         E.require_device(x, "LitResUNetPP3D_Published.forward")
         if x.ndim == 4:
             x = x.unsqueeze(1)
-        x_pad, orig = _pad_to_mult16_3d(x.float(), multiple=int(self.hparams.pad_multiple))
-        plan = self._plan(x_pad)
-        params = self._engine_params(plan)
-        flat = self._ensure_flat(plan, params, x_pad.device)
-        if torch.is_grad_enabled() and any(p.requires_grad for p in params):
-            y = _RUPPFunction.apply(x_pad, plan, flat, getattr(self, "grad_hook", None), *params)
-        else:
-            y = plan.forward(x_pad, flat).permute(0, 4, 1, 2, 3)
-        return _center_crop_3d(y, orig)
+        x_pad, orig = _pad_to_mult_3d(x.float(), int(self.hparams.pad_multiple))
+        return _center_crop_3d(self._run_plan(self._plan(x_pad), x_pad), orig)
 
     def _loss(self, logits, y):
         """dice_ce_loss_with_metrics: (loss, macro_dice, ce); Dice sums pooled over the batch."""
