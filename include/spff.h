@@ -201,6 +201,26 @@ int spff_confusion(const float* logits, const int64_t* labels, int64_t nvox, int
                    int ignore_index, int64_t* conf, void* stream);
 int spff_count_valid(const int64_t* labels, int64_t nvox, int ignore_index, int64_t* count,
                      void* stream);
+/* The ranking metrics of the test-only block of BaseLitModel._shared_step
+ * (models.py:510-584: precision_recall_curve + auc and roc_auc_score per class,
+ * models.py:521-535, and over the concatenated classes 1..K-1, models.py:552-565) and of
+ * the per-volume rows of train.py:773-798, exact and tie-aware (rank.hip: a segmented
+ * radix sort of (score, is_positive) keys and a scan over the groups of equal scores).
+ * scores: channel-last rows [batch][vox_per_sample][K]; from_logits = 1: logits, ranked by
+ * their fp32 softmax; 0: the scores themselves, finite and >= 0 (-0.0 ranks as +0.0).
+ * A voxel is positive for class c iff label == c; every other label value, 255 included,
+ * is a negative (models.py:522: there is no ignore mask).
+ * per_sample = 0: one segment per class over the whole batch and the micro segment;
+ * out = K + 1 rows, the micro row last (NaN when K < 2).  per_sample = 1: batch * K
+ * segments of vox_per_sample voxels, out = batch * K rows in (b, c) order.
+ * A row is 4 device doubles [pr_auc, roc_auc, n_pos, n_neg]; both areas are NaN when
+ * n_pos == 0 or n_neg == 0 (models.py:530).  Two calls on the same input give the same
+ * bits.  ws >= spff_rank_auc_ws_bytes device bytes (at most 16 K batch vox_per_sample +
+ * 1 MiB; 0 for arguments that spff_rank_auc rejects). */
+size_t spff_rank_auc_ws_bytes(int batch, int64_t vox_per_sample, int num_classes, int per_sample);
+int spff_rank_auc(const float* scores, const int64_t* labels, int batch, int64_t vox_per_sample,
+                  int num_classes, int from_logits, int per_sample, double* out, void* ws,
+                  void* stream);
 /* x[i] *= *scale (scale is a device scalar) */
 int spff_scale(float* x, int64_t n, const float* scale, void* stream);
 

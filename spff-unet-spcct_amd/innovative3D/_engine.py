@@ -195,6 +195,8 @@ _SIGS = {
     "spff_loss": (_I, [_P, _P, _L, _I, _I, ctypes.c_double, _P, _P, _P, _P, _P, _P]),
     "spff_confusion": (_I, [_P, _P, _L, _I, _I, _P, _P]),
     "spff_count_valid": (_I, [_P, _L, _I, _P, _P]),
+    "spff_rank_auc_ws_bytes": (_S, [_I, _L, _I, _I]),
+    "spff_rank_auc": (_I, [_P, _P, _I, _L, _I, _I, _I, _P, _P, _P]),
     "spff_scale": (_I, [_P, _L, _P, _P]),
     "spff_conv3d_ws_bytes": (_S, [_I, _I, _I, _I, _I, _I, _I]),
     "spff_conv3d_fwd": (_I, [_P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
@@ -1177,6 +1179,31 @@ def confusion(logits_cl: torch.Tensor, labels: torch.Tensor, K: int,
     check(lib().spff_confusion(_ptr(logits_cl), _ptr(labels), labels.numel(), K, ign, _ptr(conf),
                                _stream(logits_cl.device)), "spff_confusion")
     return conf.view(K, K + 1)
+
+
+def rank_auc(scores_cl: torch.Tensor, labels: torch.Tensor, K: int, from_logits: bool,
+             per_sample: bool) -> torch.Tensor:
+    """spff_rank_auc on channel-last rows [B, ..., K]: a float64 device tensor [rows, 4] of
+    (pr_auc, roc_auc, n_pos, n_neg) -- K + 1 rows (the micro row last), or B * K rows in
+    (b, c) order when ``per_sample``.  No host sync."""
+    require_device(scores_cl, "rank_auc")
+    scores_cl = scores_cl.to(torch.float32).contiguous()
+    B = scores_cl.shape[0]
+    labels = labels.to(device=scores_cl.device, dtype=torch.int64).contiguous()
+    V = labels.numel()
+    if K < 1 or scores_cl.numel() != V * K or B < 1 or V % B:
+        raise SpffError(f"scores ({tuple(scores_cl.shape)}) / labels ({tuple(labels.shape)}) "
+                        f"mismatch for K = {K}")
+    dev = scores_cl.device
+    rows = B * K if per_sample else K + 1
+    out = torch.empty((rows, 4), dtype=torch.float64, device=dev)
+    L = lib()
+    ws = torch.empty(max(1, int(L.spff_rank_auc_ws_bytes(B, V // B, K, int(bool(per_sample))))),
+                     dtype=torch.uint8, device=dev)
+    check(L.spff_rank_auc(_ptr(scores_cl), _ptr(labels), B, V // B, K, int(bool(from_logits)),
+                          int(bool(per_sample)), _ptr(out), _ptr(ws), _stream(dev)),
+          "spff_rank_auc")
+    return out
 
 
 def count_valid(labels: torch.Tensor, ignore_index: int) -> torch.Tensor:

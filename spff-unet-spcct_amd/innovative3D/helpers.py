@@ -8,6 +8,9 @@
   (helpers.py:668-725, 728-779): the confusion counts come from the HIP kernel
   (one device->host copy); the NaN / absent-class algebra runs on the host
   exactly as the reference does it.
+* ``ranking_metrics``: the test-only PR-AUC / ROC-AUC / IoU / precision block of
+  ``BaseLitModel._shared_step`` (models.py:510-584) -- the ranking part is the exact
+  segmented sort + scan of csrc/rank.hip instead of scikit-learn on the host.
 
 Only ``ce_plus_macro_dice`` is on the SPFF path (config.LOSS_NAME is never read
 by it); the other LOSS_REGISTRY entries are out of scope and raise.
@@ -24,8 +27,8 @@ from . import _engine as E
 
 __all__ = ["ce_plus_macro_dice_loss", "macro_dice_loss", "per_class_metrics_3d",
            "per_class_metrics_2d", "metrics_from_confusion", "ce_dice_with_confusion",
-           "ce_dice_parts", "dice_loss_from_confusion_t",
-           "LOSS_REGISTRY"]
+           "ce_dice_parts", "dice_loss_from_confusion_t", "ranking_metrics",
+           "iou_precision_from_confusion", "LOSS_REGISTRY"]
 
 
 def _logits_cl(logits: torch.Tensor) -> torch.Tensor:
@@ -176,6 +179,85 @@ def per_class_metrics_3d(preds, labels, num_classes, smooth=1e-6, ignore_index=N
 
 def per_class_metrics_2d(preds, labels, num_classes, smooth=1e-6, ignore_index=None):
     return per_class_metrics_3d(preds, labels, num_classes, smooth, ignore_index)
+
+
+def _nanmean_fg(vals):
+    """models.py:546: nanmean over the classes 1..K-1 (over the one class when K == 1)."""
+    v = np.asarray(vals[1:] if len(vals) > 1 else vals, dtype=np.float64)
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore", RuntimeWarning)
+        return float(np.nanmean(v)) if v.size else float("nan")
+
+
+def iou_precision_from_confusion(conf, num_classes):
+    """jaccard_score / precision_score(zero_division=0) of models.py:537-550, 566-567 on
+    confusion counts conf[pred, label] taken WITHOUT an ignore mask ([K, K+1]: column K
+    holds the labels outside [0, K), 255 included, which are "not class c" for every c
+    while their predictions still count).  Returns (iou[K], precision[K], iou_macro,
+    precision_macro, iou_micro, precision_micro).  Per class: IoU is NaN when the class is
+    absent from labels and predictions; precision is 0 when only the prediction is absent
+    and NaN when both are.  The micro forms over the classes 1..K-1 are unguarded as in
+    the reference: an empty denominator gives 0 (sklearn's zero_division), K < 2 gives NaN."""
+    K = int(num_classes)
+    conf = np.asarray(conf, dtype=np.int64)
+    iou, prec = [], []
+    tp_s = fp_s = fn_s = 0
+    for c in range(K):
+        tp = int(conf[c, c])
+        fp = int(conf[c, :].sum()) - tp
+        fn = int(conf[:K, c].sum()) - tp
+        if c >= 1:
+            tp_s, fp_s, fn_s = tp_s + tp, fp_s + fp, fn_s + fn
+        present = (tp + fp + fn) > 0
+        iou.append(tp / (tp + fp + fn) if present else float("nan"))
+        prec.append((tp / (tp + fp) if (tp + fp) > 0 else 0.0) if present else float("nan"))
+    if K > 1:
+        iou_micro = tp_s / (tp_s + fp_s + fn_s) if (tp_s + fp_s + fn_s) > 0 else 0.0
+        prec_micro = tp_s / (tp_s + fp_s) if (tp_s + fp_s) > 0 else 0.0
+    else:
+        iou_micro = prec_micro = float("nan")
+    return iou, prec, _nanmean_fg(iou), _nanmean_fg(prec), iou_micro, prec_micro
+
+
+def ranking_metrics(logits, labels, num_classes, per_sample=False):
+    """The test-only metrics of BaseLitModel._shared_step (models.py:510-584) and of the
+    per-volume rows of train.py:773-798, on the device: the exact, tie-aware PR-AUC and
+    ROC-AUC of the fp32 softmax (csrc/rank.hip) and IoU / precision from the argmax
+    confusion kernel run without an ignore mask.  Returns a dict with ``pr_auc``,
+    ``roc_auc``, ``iou`` and ``precision`` as lists of K floats and their ``_macro`` /
+    ``_micro`` forms, or -- ``per_sample`` -- as [B][K] lists only.  One device-to-host
+    copy per call (per sample for the confusion counts)."""
+    E.require_device(logits, "ranking_metrics")
+    K = int(num_classes)
+    if labels.ndim == logits.ndim and labels.shape[1] == 1:
+        labels = labels[:, 0]
+    lcl = _logits_cl(logits.detach())
+    B = lcl.shape[0]
+    labels = labels.to(lcl.device).long().reshape(B, -1)
+    auc = E.rank_auc(lcl, labels, K, True, per_sample).cpu().numpy()
+    if per_sample:
+        auc = auc.reshape(B, K, 4)
+        ip = [iou_precision_from_confusion(E.confusion(lcl[b], labels[b], K, None).cpu().numpy(), K)
+              for b in range(B)]
+        return {"pr_auc": [[float(v) for v in auc[b, :, 0]] for b in range(B)],
+                "roc_auc": [[float(v) for v in auc[b, :, 1]] for b in range(B)],
+                "iou": [p[0] for p in ip], "precision": [p[1] for p in ip]}
+    iou, prec, iou_ma, prec_ma, iou_mi, prec_mi = iou_precision_from_confusion(
+        E.confusion(lcl, labels, K, None).cpu().numpy(), K)
+    pr = [float(v) for v in auc[:K, 0]]
+    roc = [float(v) for v in auc[:K, 1]]
+    return {"pr_auc": pr, "roc_auc": roc, "iou": iou, "precision": prec,
+            "pr_auc_macro": _nanmean_fg(pr), "roc_auc_macro": _nanmean_fg(roc),
+            "iou_macro": iou_ma, "precision_macro": prec_ma,
+            "pr_auc_micro": float(auc[K, 0]), "roc_auc_micro": float(auc[K, 1]),
+            "iou_micro": iou_mi, "precision_micro": prec_mi}
+
+
+def fast_simple_metrics() -> bool:
+    """FAST_SIMPLE_METRICS=1 (train.py:24, 106-108, 120): skip the ranking metrics of the
+    test step and of test_details.csv."""
+    import os
+    return os.environ.get("FAST_SIMPLE_METRICS", "0").strip().lower() in ("1", "true", "yes", "on")
 
 
 def _out_of_scope(name):

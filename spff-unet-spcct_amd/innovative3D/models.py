@@ -31,7 +31,8 @@ import torch.nn.functional as F
 from . import _engine as E
 from .config import BEST_LR, IGNORE_INDEX, NUM_CLASSES, NUM_FRAMES  # noqa: F401
 from .helpers import (LOSS_REGISTRY, ce_plus_macro_dice_loss, ce_dice_with_confusion,  # noqa: F401
-                      metrics_from_confusion, per_class_metrics_2d, per_class_metrics_3d)
+                      fast_simple_metrics, metrics_from_confusion, per_class_metrics_2d,
+                      per_class_metrics_3d, ranking_metrics)
 from .lightning_compat import pl
 
 # ----------------------------------------------------------------- utilities --
@@ -411,8 +412,10 @@ def build_spct_energyfilm_fourier(num_classes=NUM_CLASSES, base=32, ksd=3, use_s
 class BaseLitModel(pl.LightningModule):
     """models.py:466-594.  The loss is the fused HIP ce_plus_macro_dice kernel;
     metrics come from its confusion matrix (one host copy instead of ~100
-    .item() syncs).  The test-only sklearn PR/ROC block (models.py:510-584) is
-    host-side analytics outside the hot path and is not reproduced."""
+    .item() syncs).  The test-only PR-AUC / ROC-AUC / IoU / precision block
+    (models.py:510-584) runs on the device too: helpers.ranking_metrics, the exact
+    ranking kernel of csrc/rank.hip in place of scikit-learn, under the reference's key
+    names; FAST_SIMPLE_METRICS=1 skips it as in the reference's train.py."""
 
     def __init__(self, num_classes=NUM_CLASSES, lr=BEST_LR, is_3d=True, **kwargs):
         super().__init__()
@@ -456,6 +459,18 @@ class BaseLitModel(pl.LightningModule):
             self.log(f"{prefix}_dice_class_{i}", d, on_step=False, on_epoch=True, prog_bar=False, sync_dist=True)
             self.log(f"{prefix}_sens_class_{i}", s, on_step=False, on_epoch=True, prog_bar=False, sync_dist=True)
             self.log(f"{prefix}_spec_class_{i}", sp, on_step=False, on_epoch=True, prog_bar=False, sync_dist=True)
+        # the test-only PR / ROC / IoU / precision block (models.py:510-584), 4 K + 8 keys
+        if prefix == "test" and not fast_simple_metrics():
+            rm = ranking_metrics(logits, lbls, K)
+            kw = dict(on_step=False, on_epoch=True, prog_bar=True, sync_dist=True)
+            for i in range(K):
+                self.log(f"{prefix}_pr_auc_class_{i}", rm["pr_auc"][i], **kw)
+                self.log(f"{prefix}_iou_class_{i}", rm["iou"][i], **kw)
+                self.log(f"{prefix}_precision_class_{i}", rm["precision"][i], **kw)
+                self.log(f"{prefix}_roc_auc_class_{i}", rm["roc_auc"][i], **kw)
+            for form in ("macro", "micro"):
+                for m in ("pr_auc", "roc_auc", "iou", "precision"):
+                    self.log(f"{prefix}_{m}_{form}", rm[f"{m}_{form}"], **kw)
         return loss
 
     def training_step(self, batch, batch_idx, dataloader_idx=0):

@@ -6,7 +6,9 @@ reference's test.py that touch the model (test.py:98-113 checkpoint lookup,
   for each variant in VARIANTS (INNOVATIVE3D_VARIANT honoured) and seed in SEEDS:
   load best-*.ckpt (newest) or last.ckpt from CHECKPOINT_DIR/<model>/seed<k>/,
   run the engine on the test volumes, write test_details.csv (per volume and
-  class: dice / sensitivity / specificity from the fused confusion kernel), and
+  class: dice / sensitivity / specificity from the fused confusion kernel, and
+  precision / IoU / PR-AUC / ROC-AUC from helpers.ranking_metrics unless
+  FAST_SIMPLE_METRICS=1), and
   aggregate mean +- std over seeds into analysis/per_class_summary.csv -- the
   table the reference turns into heatmaps.
 
@@ -71,18 +73,32 @@ def materialize_lazy(model, depth, device):
             m._ensure_mask(depth, device)
 
 
+DETAIL_FIELDS = ["volume", "class", "dice", "sens", "spec"]
+RANK_FIELDS = ["precision", "iou", "pr_auc", "roc_auc"]  # train.py:240-252, 313-323
+
+
+def detail_fields():
+    """Columns of test_details.csv; FAST_SIMPLE_METRICS=1 drops the ranking metrics."""
+    return DETAIL_FIELDS + ([] if Hh.fast_simple_metrics() else RANK_FIELDS)
+
+
 def evaluate(model, dataset, K, device):
     rows = []
     model.eval()
+    rank = not Hh.fast_simple_metrics()
     with torch.no_grad():
         for i in range(len(dataset)):
             x, y = dataset[i]
             x, y = x[None].to(device), y[None].to(device)
             logits = model(x)
             dice, sens, spec, *_ = Hh.per_class_metrics_3d(logits, y, K, ignore_index=255)
+            # each volume is a batch of one (train.py:773-798)
+            rm = Hh.ranking_metrics(logits, y, K, per_sample=True) if rank else None
             for c in range(K):
-                rows.append({"volume": i, "class": c, "dice": dice[c], "sens": sens[c],
-                             "spec": spec[c]})
+                row = {"volume": i, "class": c, "dice": dice[c], "sens": sens[c], "spec": spec[c]}
+                if rank:
+                    row.update({k: rm[k][0][c] for k in RANK_FIELDS})
+                rows.append(row)
     return rows
 
 
@@ -112,7 +128,7 @@ def main(argv=None):
             rows = evaluate(model, ds, K, device)
             det = ck.parent / "test_details.csv"
             with open(det, "w", newline="") as f:
-                w = csv.DictWriter(f, fieldnames=["volume", "class", "dice", "sens", "spec"])
+                w = csv.DictWriter(f, fieldnames=detail_fields())
                 w.writeheader()
                 w.writerows(rows)
             for c in range(K):
