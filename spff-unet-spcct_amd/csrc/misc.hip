@@ -467,6 +467,38 @@ hipError_t scale_by_dev(float* x, int64_t n, const float* scale, hipStream_t s) 
   return hipGetLastError();
 }
 
+// dst[i] += scale * src[i].  The plans' one accumulate pass: a shared parameter's per-step
+// gradients in a fixed order (scale 2 for R2UNet3D's doubled IN affine), the sum of two
+// gradient branches (scale 1: d + 1 s and fma(1, s, d) round alike).  HBM-bound
+// elementwise pass, float4 body + scalar tail.
+__global__ __launch_bounds__(256) void k_accumulate(float* __restrict__ dst,
+                                                    const float* __restrict__ src, int64_t n,
+                                                    float scale, int vec) {
+  const int64_t n4 = vec ? n >> 2 : 0;  // vec: both operands 16-byte aligned
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  const int64_t i0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  float4* d4 = reinterpret_cast<float4*>(dst);
+  const float4* s4 = reinterpret_cast<const float4*>(src);
+  for (int64_t i = i0; i < n4; i += stride) {
+    float4 d = d4[i];
+    const float4 v = s4[i];
+    d.x += scale * v.x; d.y += scale * v.y; d.z += scale * v.z; d.w += scale * v.w;
+    d4[i] = d;
+  }
+  for (int64_t i = 4 * n4 + i0; i < n; i += stride) dst[i] += scale * src[i];
+}
+
+hipError_t accumulate(float* dst, const float* src, int64_t n, float scale, hipStream_t s) {
+  // (workspace slots are 256-byte aligned and the plans' channel counts are multiples of 4:
+  //  the float4 body is the usual path)
+  const int vec = !((reinterpret_cast<uintptr_t>(dst) | reinterpret_cast<uintptr_t>(src)) & 15);
+  const int64_t work = vec ? (n + 3) / 4 : n;
+  const unsigned grid = (unsigned)std::min<int64_t>((work + 255) / 256, 4096);
+  hipLaunchKernelGGL(k_accumulate, dim3(std::max(grid, 1u)), dim3(256), 0, s, dst, src, n, scale,
+                     vec);
+  return hipGetLastError();
+}
+
 // hipMemsetAsync replacement for the step's stream-ordered zeroing (counters, amax slots,
 // accumulators): a kernel node, so that a HIP-graph capture of the step replays it like the
 // step's other kernels (scripts/graph_probe3.py: with hipMemsetAsync inside the captured

@@ -23,7 +23,7 @@
 //
 // Accumulation order.  The shared conv weight and IN_ru affine receive t contributions.
 // Step t writes the gradient, steps t-1 .. 1 go to a scratch tensor and are added in that
-// order by k_r2u_acc on the plan's stream: one fixed order, bitwise repeatable.
+// order by accumulate() on the plan's stream: one fixed order, bitwise repeatable.
 //
 // Everything else runs on the engine's kernels: conv3d_run / conv3d_wgrad (any
 // SPFF_MATH_*), slab_reduce + in_mean / in_rstd per (b, c) (InstanceNorm, eps 1e-5, biased
@@ -34,7 +34,7 @@
 // rows past in_ch are zero; no dedicated kernel.
 // Saved for backward per block: x1, y_k (raw conv outputs), a_k, s, o, the statistics and
 // the pool argmax bytes.
-#include "plan_base.h"
+#include "plan_ops.h"
 #include "swin_internal.h"
 
 #include <algorithm>
@@ -45,48 +45,18 @@ using namespace spff;
 
 namespace {
 
-constexpr int NLVL = 5, NBLK = 9, NUP = 4, NSUB = 8, TMAX = 8;
-
-struct RStat {
-  size_t mean, rstd, al, de;
-};
+constexpr int NLVL = 5, NBLK = 9, NUP = 4, TMAX = 8;
 
 struct RBlk {
   std::string name;
   int lvl, Cin, C;
-  int64_t w_inp = -1, w_ru = -1, g_ru = -1, b_ru = -1, w_out = -1, g_bn = -1, b_bn = -1;
-  size_t x1, y[TMAX], a[TMAX], s, o;
-  RStat st[TMAX], bn;
+  int64_t w_inp = -1, g_ru = -1, b_ru = -1, w_out = -1, g_bn = -1, b_bn = -1;
+  Conv3 cv[1];               // the recurrent unit's conv, shared by the t steps
+  size_t x1, y[TMAX], a[TMAX], s, out;
+  Stat4 st[TMAX], bn;
   size_t gb2 = 0;            // [2][C]: 2 gamma_ru, 2 beta_ru (t > 1)
   size_t pk_inp, pk_out;     // head_pack images of the two 1x1x1 convs
-  size_t pk[2] = {0, 0};     // batched conv images: forward, input gradient
 };
-
-struct RUp {
-  int Cin, Cout, lvl_low;
-  int64_t w, b;
-  size_t pk, out;
-};
-
-// dst[i] += scale * src[i]: the fixed-order accumulation of a shared parameter's
-// per-step gradients (scale 2 for the doubled IN affine of a step k < t) and the sum of
-// the two x1 gradients.  HBM-bound elementwise pass, float4 body + scalar tail.
-__global__ __launch_bounds__(256) void k_r2u_acc(float* __restrict__ dst,
-                                                 const float* __restrict__ src, int64_t n,
-                                                 float scale, int vec) {
-  const int64_t n4 = vec ? n >> 2 : 0;  // vec: both operands 16-byte aligned
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  const int64_t i0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  float4* d4 = reinterpret_cast<float4*>(dst);
-  const float4* s4 = reinterpret_cast<const float4*>(src);
-  for (int64_t i = i0; i < n4; i += stride) {
-    float4 d = d4[i];
-    const float4 v = s4[i];
-    d.x += scale * v.x; d.y += scale * v.y; d.z += scale * v.z; d.w += scale * v.w;
-    d4[i] = d;
-  }
-  for (int64_t i = 4 * n4 + i0; i < n; i += stride) dst[i] += scale * src[i];
-}
 
 // gb2 = [2 gamma | 2 beta]: the affine of the recurrence's steps k < t
 __global__ void k_r2u_double(const float* __restrict__ gamma, const float* __restrict__ beta,
@@ -98,17 +68,6 @@ __global__ void k_r2u_double(const float* __restrict__ gamma, const float* __res
   }
 }
 
-hipError_t r2u_acc(float* dst, const float* src, int64_t n, float scale, hipStream_t s) {
-  // (workspace slots are 256-byte aligned and, with base % 8 == 0, the offsets of the
-  //  accumulated parameters are multiples of 4 floats: the float4 body is the usual path)
-  const int vec = !((reinterpret_cast<uintptr_t>(dst) | reinterpret_cast<uintptr_t>(src)) & 15);
-  const int64_t work = vec ? (n + 3) / 4 : n;
-  const unsigned grid = (unsigned)std::min<int64_t>((work + 255) / 256, 4096);
-  hipLaunchKernelGGL(k_r2u_acc, dim3(std::max(grid, 1u)), dim3(256), 0, s, dst, src, n, scale,
-                     vec);
-  return hipGetLastError();
-}
-
 }  // namespace
 
 struct spff_r2u : PlanBase {
@@ -116,7 +75,7 @@ struct spff_r2u : PlanBase {
   Vol vol[NLVL];
   int f, K, ldx, t;
   RBlk blk[NBLK];  // e1..e4, b, d4..d1
-  RUp up[NUP];     // up4, up3, up2, up1
+  UpConv up[NUP];  // up4, up3, up2, up1
   int64_t head_w = -1, head_b = -1;
   size_t head_pk = 0, x_cl = 0, pool[4] = {}, pidx[4] = {};
   size_t red_ws = 0, red_out = 0, kk1 = 0, kk2 = 0, wg_ws = 0, wt = 0;
@@ -132,7 +91,7 @@ void reg_block(spff_r2u* p, RBlk& b) {
   const int C = b.C;
   const std::string n = "backbone." + b.name;
   b.w_inp = p->reg(n + ".inp.weight", {C, b.Cin, 1, 1, 1});
-  b.w_ru = p->reg(n + ".ru.conv.weight", {C, C, 3, 3, 3});
+  b.cv[0] = reg_conv(p, n + ".ru.conv.weight", C, C);
   b.g_ru = p->reg(n + ".ru.inn.weight", {C});
   b.b_ru = p->reg(n + ".ru.inn.bias", {C});
   b.w_out = p->reg(n + ".out.weight", {C, C, 1, 1, 1});
@@ -177,10 +136,10 @@ int build(spff_r2u* p) {
   for (int i = 0; i < 5; ++i) reg_block(p, p->blk[i]);
   const char* upn[NUP] = {"up4", "up3", "up2", "up1"};
   for (int u = 0; u < NUP; ++u) {
-    RUp& U = p->up[u];
+    UpConv& U = p->up[u];
     U.Cin = 16 * f >> u;
     U.Cout = 8 * f >> u;
-    U.lvl_low = 4 - u;
+    U.Llow = 4 - u;
     U.w = p->reg(std::string("backbone.") + upn[u] + ".weight", {U.Cin, U.Cout, 2, 2, 2});
     U.b = p->reg(std::string("backbone.") + upn[u] + ".bias", {U.Cout});
     reg_block(p, p->blk[5 + u]);
@@ -199,18 +158,15 @@ int build(spff_r2u* p) {
     const int64_t M = nvox(v);
     const size_t act = M * b.C * sizeof(float);
     const size_t bc = (size_t)B * b.C * sizeof(float);
-    auto stat = [&](RStat& s) {
-      s.mean = p->alloc(bc); s.rstd = p->alloc(bc); s.al = p->alloc(bc); s.de = p->alloc(bc);
-    };
     b.x1 = p->alloc(act);
     for (int k = 0; k < T; ++k) {
       b.y[k] = p->alloc(act);
       b.a[k] = p->alloc(act);
-      stat(b.st[k]);
+      b.st[k] = stat_alloc(p, bc);
     }
     b.s = p->alloc(act);
-    b.o = p->alloc(act);
-    stat(b.bn);
+    b.out = p->alloc(act);
+    b.bn = stat_alloc(p, bc);
     if (T > 1) b.gb2 = p->alloc((size_t)2 * b.C * sizeof(float));
     // the GEMM reads level 0's input through its 8-channel rows: same image size
     b.pk_inp = p->alloc(head_pack_floats(i == 0 ? p->ldx : b.Cin, b.C) * sizeof(float));
@@ -230,11 +186,9 @@ int build(spff_r2u* p) {
     p->pidx[l] = p->alloc(nvox(vl) * C);
   }
   for (int u = 0; u < NUP; ++u) {
-    RUp& U = p->up[u];
-    const Vol& vh = p->vol[U.lvl_low - 1];
-    U.out = p->alloc(nvox(vh) * U.Cout * sizeof(float));
-    U.pk = p->alloc(upconv_pack_floats(U.Cin, U.Cout, NSUB) * sizeof(float));
-    wg = std::max(wg, upconv_wgrad_ws_bytes(p->vol[U.lvl_low], U.Cin, U.Cout, NSUB));
+    UpConv& U = p->up[u];
+    up_alloc(p, U);
+    wg = std::max(wg, upconv_wgrad_ws_bytes(p->vol[U.Llow], U.Cin, U.Cout, UP_NS));
   }
   p->head_pk = p->alloc(head_pack_floats(f, p->K) * sizeof(float));
   wg = std::max(wg, head_wgrad_ws_bytes(nvox(v0), f, p->K));
@@ -246,17 +200,7 @@ int build(spff_r2u* p) {
   p->tmp_w = p->alloc((size_t)16 * f * 16 * f * 27 * sizeof(float));
   p->tmp_gb = p->alloc((size_t)2 * 16 * f * sizeof(float));
   p->db_scr = p->alloc((size_t)16 * f * sizeof(float));
-  p->pkb = conv3d_packs_batched(c.math);
-  if (p->pkb) {
-    for (int i = 0; i < NBLK; ++i) {
-      RBlk& b = p->blk[i];
-      b.pk[0] = p->alloc(conv3d_pack_bytes(3, b.C, b.C));
-      b.pk[1] = p->alloc(conv3d_pack_bytes(3, b.C, b.C));
-    }
-    p->wsl = p->alloc(NBLK * sizeof(unsigned));
-  } else {
-    p->wt = p->alloc(wt);
-  }
+  alloc_convs(p, p->blk, NBLK, wt);
   size_t gmax = 0;  // max over levels of V_l * C_l
   for (int l = 0; l < NLVL; ++l)
     gmax = std::max(gmax, (size_t)nvox(p->vol[l]) * (size_t)(f << l) * sizeof(float));
@@ -274,7 +218,6 @@ int build(spff_r2u* p) {
 // forward and backward): the 1x1x1 GEMM images, the doubled IN affine and, for the split
 // arithmetics, the conv images (forward and input gradient) in one launch pair
 int prep_weights(spff_r2u* p) {
-  const int math = p->cfg.math;
   for (int i = 0; i < NBLK; ++i) {
     RBlk& b = p->blk[i];
     const int kin = i == 0 ? p->ldx : b.Cin;
@@ -290,69 +233,7 @@ int prep_weights(spff_r2u* p) {
       PLAN_HIPCK(hipGetLastError());
     }
   }
-  if (!p->pkb) return SPFF_OK;
-  const bool f16 = math == SPFF_MATH_F16X3;
-  unsigned* sl = reinterpret_cast<unsigned*>(p->ws + p->wsl);
-  PrepJobs pj;
-  PackJobs kj;
-  if (f16) PLAN_HIPCK(spff::zero_async(sl, NBLK * sizeof(unsigned), p->st));
-  for (int i = 0; i < NBLK; ++i) {
-    RBlk& b = p->blk[i];
-    unsigned* wm = f16 ? sl + i : nullptr;
-    bool ok = true;
-    if (f16) ok = ok && prep_absmax(&pj, p->P(b.w_ru), (int64_t)b.C * b.C * 27, wm);
-    ok = ok && conv3d_pack_job(&kj, p->P(b.w_ru), p->F(b.pk[0]), 3, b.C, b.C, false, wm);
-    ok = ok && conv3d_pack_job(&kj, p->P(b.w_ru), p->F(b.pk[1]), 3, b.C, b.C, true, wm);
-    if (!ok) return plan_fail(SPFF_EINVAL, "weight preparation table overflow");
-  }
-  PLAN_HIPCK(prep_run(pj, p->st));
-  PLAN_HIPCK(conv3d_pack_many(kj, math, p->st));
-  return SPFF_OK;
-}
-
-// the block's conv image (forward or input gradient): the batched one, else packed now
-int conv_image(spff_r2u* p, const RBlk& b, bool dgrad, const Vol& v, const float** img,
-               const unsigned** wmax) {
-  if (p->pkb) {
-    *img = p->F(b.pk[dgrad ? 1 : 0]);
-    *wmax = p->cfg.math == SPFF_MATH_F16X3
-                ? reinterpret_cast<const unsigned*>(p->ws + p->wsl) + (int)(&b - p->blk)
-                : nullptr;
-    return SPFF_OK;
-  }
-  PLAN_HIPCK(conv3d_pack(p->P(b.w_ru), p->F(p->wt), v, 3, b.C, b.C, dgrad, p->cfg.math, p->st));
-  *img = p->F(p->wt);
-  *wmax = nullptr;
-  return SPFF_OK;
-}
-
-// InstanceNorm3d statistics of y per (b, c) and the apply coefficients al = gamma rstd,
-// de = beta - mean al
-int in_fwd(spff_r2u* p, const Vol& v, int C, const float* y, const RStat& s, const float* gamma,
-           const float* beta) {
-  RedArgs a{};
-  a.y = y;
-  PLAN_HIPCK(slab_reduce(RED_SUM, a, v, C, p->F(p->red_out), p->F(p->red_ws), p->st));
-  PLAN_HIPCK(in_mean(p->F(p->red_out), p->F(s.mean), v, C, p->st));
-  a.mean = p->F(s.mean);
-  PLAN_HIPCK(slab_reduce(RED_SQDEV, a, v, C, p->F(p->red_out), p->F(p->red_ws), p->st));
-  PLAN_HIPCK(in_rstd(p->F(p->red_out), gamma, beta, p->F(s.mean), p->F(s.rstd), p->F(s.al),
-                 p->F(s.de), v, C, p->st));
-  return SPFF_OK;
-}
-
-// InstanceNorm + ReLU backward: dy = rstd gamma (dr - k1 - xhat k2), dr = g [r > 0]
-int in_bwd(spff_r2u* p, const Vol& v, int C, const float* y, const float* g, float* dy,
-           const RStat& s, const float* gamma, float* dgamma, float* dbeta) {
-  RedArgs a{};
-  a.y = y; a.g = g; a.mean = p->F(s.mean); a.rstd = p->F(s.rstd);
-  a.al = p->F(s.al); a.de = p->F(s.de); a.neg = 0.f;
-  PLAN_HIPCK(slab_reduce(RED_BWD_IN, a, v, C, p->F(p->red_out), p->F(p->red_ws), p->st));
-  PLAN_HIPCK(in_bwd_stats(p->F(p->red_out), gamma, dgamma, dbeta, p->F(p->kk1), p->F(p->kk2), v, C,
-                      p->st));
-  PLAN_HIPCK(in_bwd_apply(y, g, dy, p->F(s.mean), p->F(s.rstd), p->F(s.al), p->F(s.de), gamma,
-                      nullptr, nullptr, p->F(p->kk1), p->F(p->kk2), v, C, p->st, 0.f));
-  return SPFF_OK;
+  return prep_convs(p, p->blk, NBLK);
 }
 
 // affine of recurrence step k (0-based): doubled for every step but the last
@@ -365,16 +246,12 @@ const float* ru_beta(const spff_r2u* p, const RBlk& b, int k) {
 
 int fwd_block(spff_r2u* p, RBlk& b, const Src2& in, int kin) {
   const Vol& v = p->vol[b.lvl];
-  const int C = b.C, math = p->cfg.math;
+  const int C = b.C;
   const int64_t M = nvox(v);
   PLAN_HIPCK(linear_fwd2(in, kin, p->F(b.pk_inp), nullptr, p->F(b.x1), C, C, M, p->st));
   const float* cur = p->F(b.x1);
   for (int k = 0; k < p->t; ++k) {
-    const float* img;
-    const unsigned* wmax;
-    PLAN_CK(conv_image(p, b, false, v, &img, &wmax));
-    PLAN_HIPCK(conv3d_run(src1(cur, C), img, dst1(p->F(b.y[k]), C), v, 3, C, C, false, math, p->st,
-                      p->F(p->wg_ws), nullptr, 0, wmax));
+    PLAN_CK(conv_run(p, b.cv[0], false, src1(cur, C), dst1(p->F(b.y[k]), C), v));
     PLAN_CK(in_fwd(p, v, C, p->F(b.y[k]), b.st[k], ru_gamma(p, b, k), ru_beta(p, b, k)));
     PLAN_HIPCK(act_apply(p->F(b.y[k]), p->F(b.a[k]), p->F(b.st[k].al), p->F(b.st[k].de), nullptr,
                      nullptr, v, C, p->st, 0.f));
@@ -382,7 +259,7 @@ int fwd_block(spff_r2u* p, RBlk& b, const Src2& in, int kin) {
   }
   PLAN_HIPCK(linear_fwd(cur, C, C, p->F(b.pk_out), nullptr, p->F(b.s), C, C, M, p->F(b.x1), C, p->st));
   PLAN_CK(in_fwd(p, v, C, p->F(b.s), b.bn, p->P(b.g_bn), p->P(b.b_bn)));
-  PLAN_HIPCK(act_apply(p->F(b.s), p->F(b.o), p->F(b.bn.al), p->F(b.bn.de), nullptr, nullptr, v, C,
+  PLAN_HIPCK(act_apply(p->F(b.s), p->F(b.out), p->F(b.bn.al), p->F(b.bn.de), nullptr, nullptr, v, C,
                    p->st, 0.f));
   return SPFF_OK;
 }
@@ -397,7 +274,8 @@ int bwd_block(spff_r2u* p, RBlk& b, const float* dout, const Dst2* dx, const Src
   float* gn = p->F(p->G_2);
   float* wgs = p->F(p->wg_ws);
   // o = relu(IN_bn(s)): ds, which is also the residual branch's share of dx1
-  PLAN_CK(in_bwd(p, v, C, p->F(b.s), dout, ds, b.bn, p->P(b.g_bn), p->DP(b.g_bn), p->DP(b.b_bn)));
+  PLAN_CK(in_bwd(p, v, C, p->F(b.s), dout, ds, b.bn, p->P(b.g_bn), p->DP(b.g_bn), p->DP(b.b_bn),
+                 0.f));
   // s = x1 + out(a_t)
   PLAN_HIPCK(linear_wgrad(p->F(b.a[T - 1]), C, C, ds, C, C, p->DP(b.w_out), p->F(p->db_scr), M, wgs,
                       p->st));
@@ -408,24 +286,20 @@ int bwd_block(spff_r2u* p, RBlk& b, const float* dout, const Dst2* dx, const Src
     const bool last = k == T - 1;
     float* dgam = last ? p->DP(b.g_ru) : p->F(p->tmp_gb);
     float* dbet = last ? p->DP(b.b_ru) : p->F(p->tmp_gb) + C;
-    PLAN_CK(in_bwd(p, v, C, p->F(b.y[k]), g, g, b.st[k], ru_gamma(p, b, k), dgam, dbet));
+    PLAN_CK(in_bwd(p, v, C, p->F(b.y[k]), g, g, b.st[k], ru_gamma(p, b, k), dgam, dbet, 0.f));
     if (!last) {  // affine (2 gamma, 2 beta): d/dgamma = 2 d/d(2 gamma)
-      PLAN_HIPCK(r2u_acc(p->DP(b.g_ru), dgam, C, 2.f, p->st));
-      PLAN_HIPCK(r2u_acc(p->DP(b.b_ru), dbet, C, 2.f, p->st));
+      PLAN_HIPCK(accumulate(p->DP(b.g_ru), dgam, C, 2.f, p->st));
+      PLAN_HIPCK(accumulate(p->DP(b.b_ru), dbet, C, 2.f, p->st));
     }
     const float* xin = k == 0 ? p->F(b.x1) : p->F(b.a[k - 1]);
-    float* dw = last ? p->DP(b.w_ru) : p->F(p->tmp_w);
+    float* dw = last ? p->DP(b.cv[0].w) : p->F(p->tmp_w);
     PLAN_HIPCK(conv3d_wgrad(src1(xin, C), g, C, dw, v, 3, C, C, math, wgs, p->st));
-    if (!last) PLAN_HIPCK(r2u_acc(p->DP(b.w_ru), dw, nw, 1.f, p->st));
-    const float* img;
-    const unsigned* wmax;
-    PLAN_CK(conv_image(p, b, true, v, &img, &wmax));
-    PLAN_HIPCK(conv3d_run(src1(g, C), img, dst1(gn, C), v, 3, C, C, true, math, p->st, wgs, nullptr, 0,
-                      wmax));
+    if (!last) PLAN_HIPCK(accumulate(p->DP(b.cv[0].w), dw, nw, 1.f, p->st));
+    PLAN_CK(conv_run(p, b.cv[0], true, src1(g, C), dst1(gn, C), v));
     std::swap(g, gn);
   }
   // x1 feeds the recurrent unit and the residual: dx1 = ds + (the unit's input gradient)
-  PLAN_HIPCK(r2u_acc(ds, g, M * C, 1.f, p->st));
+  PLAN_HIPCK(accumulate(ds, g, M * C, 1.f, p->st));
   PLAN_HIPCK(linear_wgrad2(in, b.Cin, ds, C, C, p->DP(b.w_inp), p->F(p->db_scr), M, wgs, p->st));
   if (dx)
     PLAN_HIPCK(linear_dgrad2(ds, C, C, p->F(b.pk_inp) + head_pack_dgrad_offset(b.Cin, C), *dx, b.Cin,
@@ -434,81 +308,18 @@ int bwd_block(spff_r2u* p, RBlk& b, const float* dout, const Dst2* dx, const Src
 }
 
 int forward(spff_r2u* p, const float* x, float* logits) {
-  const spff_r2u_cfg& c = p->cfg;
-  const int f = p->f;
-  const Vol& v0 = p->vol[0];
-  PLAN_HIPCK(ncdhw_to_ndhwc(x, p->F(p->x_cl), v0, c.in_ch, p->ldx, p->st));
+  PLAN_HIPCK(ncdhw_to_ndhwc(x, p->F(p->x_cl), p->vol[0], p->cfg.in_ch, p->ldx, p->st));
   PLAN_CK(prep_weights(p));
-  RBlk* B = p->blk;
-  Src2 in = src1(p->F(p->x_cl), p->ldx);
-  int kin = p->ldx;
-  for (int l = 0; l < 4; ++l) {
-    PLAN_CK(fwd_block(p, B[l], in, kin));
-    PLAN_HIPCK(maxpool3_fwd(p->F(B[l].o), p->F(p->pool[l]),
-                        reinterpret_cast<uint8_t*>(p->ws + p->pidx[l]), p->vol[l], f << l, p->st));
-    in = src1(p->F(p->pool[l]), f << l);
-    kin = f << l;
-  }
-  PLAN_CK(fwd_block(p, B[4], in, kin));
-  const float* prev = p->F(B[4].o);
-  for (int u = 0; u < NUP; ++u) {
-    RUp& U = p->up[u];
-    float* pk = p->F(U.pk);
-    PLAN_HIPCK(upconv_pack(p->P(U.w), pk, pk + upconv_pack_dgrad_offset(U.Cin, U.Cout, NSUB), U.Cin,
-                       U.Cout, p->st, NSUB));
-    PLAN_HIPCK(upconv_fwd(prev, pk, p->P(U.b), p->F(U.out), p->vol[U.lvl_low], U.Cin, U.Cout, p->st,
-                      NSUB, p->cfg.math));
-    RBlk& d = B[5 + u];
-    const RBlk& skip = B[3 - u];
-    // torch.cat([up(x), skip], dim=1) read in place through the two-source view
-    PLAN_CK(fwd_block(p, d, Src2{p->F(U.out), p->F(skip.o), U.Cout, U.Cout, U.Cout}, 2 * U.Cout));
-    prev = p->F(d.o);
-  }
-  float* hp = p->F(p->head_pk);
-  PLAN_HIPCK(head_pack(p->P(p->head_w), hp, hp + head_pack_dgrad_offset(f, p->K), f, p->K, p->st));
-  PLAN_HIPCK(head_fwd(prev, hp, p->P(p->head_b), logits, nvox(v0), f, p->K, p->st, p->cfg.math));
-  return SPFF_OK;
+  return unet5_forward(p, p->head_w, p->head_b, logits, [&](RBlk& b, const Src2& in, int kin) {
+    return fwd_block(p, b, in, kin);
+  });
 }
 
 int backward(spff_r2u* p, const float* dl) {
-  const int f = p->f;
-  const int64_t V0 = nvox(p->vol[0]);
-  RBlk* B = p->blk;
-  float* hp = p->F(p->head_pk);
-  PLAN_HIPCK(head_wgrad(p->F(B[8].o), dl, p->DP(p->head_w), p->DP(p->head_b), V0, f, p->K,
-                    p->F(p->wg_ws), p->st));
-  PLAN_HIPCK(head_dgrad(dl, hp + head_pack_dgrad_offset(f, p->K), p->F(p->G_out), V0, f, p->K, p->st,
-                    p->cfg.math));
-  for (int k = 0; k < NUP; ++k) {  // d1 <- up1 <- d2 ... <- up4
-    const int bi = 8 - k, ui = 3 - k;
-    RBlk& d = B[bi];
-    RUp& U = p->up[ui];
-    const int C = d.C, lvl = d.lvl;
-    Dst2 dx{p->F(p->G_dx), p->F(p->dskip[lvl]), C, C, C};
-    PLAN_CK(bwd_block(p, d, p->F(p->G_out), &dx, Src2{p->F(U.out), p->F(B[lvl].o), C, C, C}));
-    const Vol& low = p->vol[U.lvl_low];
-    PLAN_HIPCK(upconv_wgrad(p->F(B[bi - 1].o), p->F(p->G_dx), C, p->DP(U.w), p->DP(U.b), low, U.Cin,
-                        U.Cout, p->F(p->wg_ws), p->st, NSUB, p->cfg.math));
-    float* pk = p->F(U.pk);
-    PLAN_HIPCK(upconv_dgrad(p->F(p->G_dx), C, pk + upconv_pack_dgrad_offset(U.Cin, U.Cout, NSUB),
-                        p->F(p->G_out), low, U.Cin, U.Cout, p->st, NSUB, p->cfg.math));
-  }
-  {
-    Dst2 dx = dst1(p->F(p->G_dx), 8 * f);
-    PLAN_CK(bwd_block(p, B[4], p->F(p->G_out), &dx, src1(p->F(p->pool[3]), 8 * f)));
-  }
-  for (int l = 3; l >= 0; --l) {
-    const int C = f << l;
-    PLAN_HIPCK(maxpool3_bwd_add(p->F(p->G_dx), reinterpret_cast<const uint8_t*>(p->ws + p->pidx[l]),
-                            p->F(p->dskip[l]), C, p->F(p->dskip[l]), p->vol[l], C, p->st));
-    if (l > 0) {
-      Dst2 dx = dst1(p->F(p->G_dx), C / 2);
-      PLAN_CK(bwd_block(p, B[l], p->F(p->dskip[l]), &dx, src1(p->F(p->pool[l - 1]), C / 2)));
-    } else {
-      PLAN_CK(bwd_block(p, B[0], p->F(p->dskip[0]), nullptr, src1(p->F(p->x_cl), p->ldx)));
-    }
-  }
-  return SPFF_OK;
+  return unet5_backward(p, p->head_w, p->head_b, dl,
+                        [&](RBlk& b, const float* dout, const Dst2* dx, const Src2& in) {
+                          return bwd_block(p, b, dout, dx, in);
+                        });
 }
 
 }  // namespace
@@ -556,7 +367,7 @@ int spff_r2u_saved_tensor(const spff_r2u* p, void* ws, const char* name, const f
     const RBlk& b = p->blk[i];
     const Vol& v = p->vol[b.lvl];
     if (n == b.name + ".x1") return ret(b.x1, v, b.C);
-    if (n == b.name + ".out") return ret(b.o, v, b.C);
+    if (n == b.name + ".out") return ret(b.out, v, b.C);
     for (int k = 0; k < p->t; ++k)
       if (n == b.name + ".ru" + std::to_string(k + 1)) return ret(b.a[k], v, b.C);
   }

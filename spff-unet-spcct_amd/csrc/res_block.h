@@ -1,15 +1,16 @@
-// The pieces that the MONAI-style plans (swin.hip, unetr.hip) share: packed Linear / 1x1
-// conv, UnetResBlock and 2x2x2 transposed-conv descriptors, and the UnetResBlock forward /
-// backward schedule on the engine's convs and InstanceNorm kernels.  Everything here is
-// internal to the including translation unit (namespace spff, anonymous).  A plan type P
-// derives from PlanBase (plan_base.h: F / P / DP, reg, alloc, ws, st, PLAN_HIPCK / PLAN_CK)
-// and provides, under these names:
-//   cfg.math; Vol vol[]; RB rb[P::kNRB]; int maxC
-//   workspace offsets ones, zeros [maxC], dummy [2 maxC], red_ws, red_out, kk1, kk2 [B maxC],
-//   wg_ws, cst, G_dz, G_dy2, G_da1, and pkb ? rb[i].pk[] + wsl [kNRB][2] : wt, sized as
-//   build() of swin.hip / unetr.hip sizes them
+// MONAI's UnetResBlock as the MONAI-style plans (swin.hip, unetr.hip) run it: the packed
+// Linear / 1x1 conv descriptor, the block descriptor and its forward / backward schedule on
+// the engine's convs and affine-free InstanceNorm.  The plan-generic steps (statistics slot,
+// InstanceNorm forward / backward, conv descriptor and weight preparation, transposed conv)
+// come from plan_ops.h.  Everything here is internal to the including translation unit
+// (namespace spff, anonymous).  A plan type P derives from PlanBase and provides, beside
+// what plan_ops.h lists:
+//   RB rb[]; int maxC
+//   workspace offsets ones, zeros [maxC], dummy [2 maxC] (the affine-free norm's gamma, beta
+//   and the sink of its dgamma / dbeta), cst, G_dz, G_dy2, G_da1, sized as build() of
+//   swin.hip / unetr.hip sizes them
 #pragma once
-#include "plan_base.h"
+#include "plan_ops.h"
 #include "swin_internal.h"
 
 #include <algorithm>
@@ -29,17 +30,10 @@ struct RB {
   std::string name;
   int L, Cin, C;
   bool has3;
-  int64_t w1 = -1, w2 = -1;
+  Conv3 cv[2];
   Lin c3;
   size_t y1, a1, y2, y3, out;
-  size_t st[3][4];  // (mean, rstd, al, de) of the IN after conv1, conv2, conv3
-  size_t pk[4] = {0, 0, 0, 0};  // batched conv images: w1 fwd, w2 fwd, w2 dgrad, w1 dgrad
-};
-
-struct Up {
-  int Cin, Cout, Llow;
-  int64_t w = -1;
-  size_t pk, out;
+  Stat4 st[3];  // of the IN after conv1, conv2, conv3
 };
 
 template <class P>
@@ -60,131 +54,58 @@ void reg_rb(P* p, RB& r, const std::string& name, int L, int Cin, int C) {
   r.Cin = Cin;
   r.C = C;
   r.has3 = Cin != C;
-  r.w1 = p->reg(name + ".conv1.conv.weight", {C, Cin, 3, 3, 3});
-  r.w2 = p->reg(name + ".conv2.conv.weight", {C, C, 3, 3, 3});
+  r.cv[0] = reg_conv(p, name + ".conv1.conv.weight", Cin, C);
+  r.cv[1] = reg_conv(p, name + ".conv2.conv.weight", C, C);
   if (r.has3) reg_lin(p, r.c3, name + ".conv3.conv", Cin, C, false, {C, Cin, 1, 1, 1});
 }
 
-// affine-free InstanceNorm3d statistics of y [V][C] -> (mean, rstd, al, de)
+// the block's activations and statistics slots
 template <class P>
-int in_stats(P* p, const Vol& v, int C, size_t y, const size_t* st4) {
-  RedArgs a{};
-  a.y = p->F(y);
-  PLAN_HIPCK(slab_reduce(RED_SUM, a, v, C, p->F(p->red_out), p->F(p->red_ws), p->st));
-  PLAN_HIPCK(in_mean(p->F(p->red_out), p->F(st4[0]), v, C, p->st));
-  a.mean = p->F(st4[0]);
-  PLAN_HIPCK(slab_reduce(RED_SQDEV, a, v, C, p->F(p->red_out), p->F(p->red_ws), p->st));
-  PLAN_HIPCK(in_rstd(p->F(p->red_out), p->F(p->ones), p->F(p->zeros), p->F(st4[0]), p->F(st4[1]),
-                 p->F(st4[2]), p->F(st4[3]), v, C, p->st));
-  return SPFF_OK;
+void rb_alloc(P* p, RB& r) {
+  const size_t act = fbytes(nvox(p->vol[r.L]) * r.C);
+  r.y1 = p->alloc(act);
+  r.a1 = p->alloc(act);
+  r.y2 = p->alloc(act);
+  r.y3 = r.has3 ? p->alloc(act) : 0;
+  r.out = p->alloc(act);
+  for (Stat4& s : r.st) s = stat_alloc(p, fbytes((int64_t)p->cfg.batch * r.C));
 }
 
-// batched plans: every conv's max |w| (f16x3) in one launch, then every conv image
-// (forward and input gradient; 39 for SwinUNETR, 31 for UNETR) in one more, at the forward start -- the weights do not
-// change between a step's forward and backward (the up-conv / linear images are packed up
-// front the same way).  Otherwise conv3d_pack before each conv (max + pack launches).
+// 3x3x3 conv c + (fused where the kernel allows) affine-free IN statistics
 template <class P>
-int prep_weights(P* p) {
-  if (!p->pkb) return SPFF_OK;
-  const int math = p->cfg.math;
-  const bool f16 = math == SPFF_MATH_F16X3;
-  unsigned* sl = reinterpret_cast<unsigned*>(p->ws + p->wsl);
-  PrepJobs pj;
-  PackJobs kj;
-  if (f16) PLAN_HIPCK(spff::zero_async(sl, P::kNRB * 2 * sizeof(unsigned), p->st));
-  for (int i = 0; i < P::kNRB; ++i) {
-    RB& r = p->rb[i];
-    unsigned* w1 = f16 ? sl + 2 * i : nullptr;
-    unsigned* w2 = f16 ? sl + 2 * i + 1 : nullptr;
-    bool ok = true;
-    if (f16) {
-      ok = ok && prep_absmax(&pj, p->P(r.w1), (int64_t)r.C * r.Cin * 27, w1);
-      ok = ok && prep_absmax(&pj, p->P(r.w2), (int64_t)r.C * r.C * 27, w2);
-    }
-    ok = ok && conv3d_pack_job(&kj, p->P(r.w1), p->F(r.pk[0]), 3, r.Cin, r.C, false, w1);
-    ok = ok && conv3d_pack_job(&kj, p->P(r.w2), p->F(r.pk[1]), 3, r.C, r.C, false, w2);
-    ok = ok && conv3d_pack_job(&kj, p->P(r.w2), p->F(r.pk[2]), 3, r.C, r.C, true, w2);
-    if (r.pk[3]) ok = ok && conv3d_pack_job(&kj, p->P(r.w1), p->F(r.pk[3]), 3, r.Cin, r.C, true, w1);
-    if (!ok) return plan_fail(SPFF_EINVAL, "weight preparation table overflow");
-  }
-  PLAN_HIPCK(prep_run(pj, p->st));
-  PLAN_HIPCK(conv3d_pack_many(kj, math, p->st));
-  return SPFF_OK;
-}
-// conv k of residual block r (0: w1 fwd, 1: w2 fwd, 2: w2 dgrad, 3: w1 dgrad): its image
-// (the batched one, else packed now into the scratch image) and its max |w| slot
-template <class P>
-int conv_image(P* p, const RB& r, int k, const Vol& v, const float** img,
-               const unsigned** wmax) {
-  const bool c1 = k == 0 || k == 3;
-  const int ri = (int)(&r - p->rb);
-  if (p->pkb) {
-    if (!r.pk[k]) return plan_fail(SPFF_EINVAL, "no batched image for this conv");
-    *img = p->F(r.pk[k]);
-    *wmax = p->cfg.math == SPFF_MATH_F16X3
-                ? reinterpret_cast<const unsigned*>(p->ws + p->wsl) + 2 * ri + (c1 ? 0 : 1)
-                : nullptr;
-    return SPFF_OK;
-  }
-  PLAN_HIPCK(conv3d_pack(p->P(c1 ? r.w1 : r.w2), p->F(p->wt), v, 3, c1 ? r.Cin : r.C, r.C, k >= 2,
-                     p->cfg.math, p->st));
-  *img = p->F(p->wt);
-  *wmax = nullptr;
-  return SPFF_OK;
-}
-
-// 3x3x3 conv k (0 / 1) of r + (fused where the kernel allows) IN statistics
-template <class P>
-int conv_in(P* p, const Src2& in, const RB& r, int k, const Vol& v, int Cin, int C,
-            size_t y, const size_t* st4) {
+int conv_in(P* p, const Src2& in, const Conv3& c, const Vol& v, size_t y, const Stat4& s) {
   const int math = p->cfg.math;
   const float* img;
   const unsigned* wmax;
-  PLAN_CK(conv_image(p, r, k, v, &img, &wmax));
-  const bool fuse = conv3d_fuses_stats(v, 3, Cin, C, math);
-  PLAN_HIPCK(conv3d_run(in, img, dst1(p->F(y), C), v, 3, Cin, C, false, math, p->st,
+  PLAN_CK(conv_image(p, c, false, v, &img, &wmax));
+  const bool fuse = conv3d_fuses_stats(v, 3, c.Cin, c.C, math);
+  PLAN_HIPCK(conv3d_run(in, img, dst1(p->F(y), c.C), v, 3, c.Cin, c.C, false, math, p->st,
                     p->F(p->wg_ws), fuse ? p->F(p->cst) : nullptr, 0, wmax));
   if (fuse) {
-    PLAN_HIPCK(conv3d_in_stats_fin(p->F(p->cst), v, 3, Cin, C, math, p->F(p->ones), p->F(p->zeros),
-                               p->F(st4[0]), p->F(st4[1]), p->F(st4[2]), p->F(st4[3]), p->st));
+    PLAN_HIPCK(conv3d_in_stats_fin(p->F(p->cst), v, 3, c.Cin, c.C, math, p->F(p->ones),
+                               p->F(p->zeros), p->F(s.mean), p->F(s.rstd), p->F(s.al), p->F(s.de),
+                               p->st));
     return SPFF_OK;
   }
-  return in_stats(p, v, C, y, st4);
+  return in_fwd(p, v, c.C, p->F(y), s, p->F(p->ones), p->F(p->zeros));
 }
 
 template <class P>
 int rb_fwd(P* p, RB& r, const Src2& in, const float* ident) {
   const Vol& v = p->vol[r.L];
   const int C = r.C;
-  PLAN_CK(conv_in(p, in, r, 0, v, r.Cin, C, r.y1, r.st[0]));
-  PLAN_HIPCK(act_apply(p->F(r.y1), p->F(r.a1), p->F(r.st[0][2]), p->F(r.st[0][3]), nullptr, nullptr, v,
+  PLAN_CK(conv_in(p, in, r.cv[0], v, r.y1, r.st[0]));
+  PLAN_HIPCK(act_apply(p->F(r.y1), p->F(r.a1), p->F(r.st[0].al), p->F(r.st[0].de), nullptr, nullptr, v,
                    C, p->st));
-  PLAN_CK(conv_in(p, src1(p->F(r.a1), C), r, 1, v, C, C, r.y2, r.st[1]));
+  PLAN_CK(conv_in(p, src1(p->F(r.a1), C), r.cv[1], v, r.y2, r.st[1]));
   if (r.has3) {
     float* pk = p->F(r.c3.pk);
     PLAN_HIPCK(head_pack(p->P(r.c3.w), pk, pk + head_pack_dgrad_offset(r.Cin, C), r.Cin, C, p->st));
     PLAN_HIPCK(linear_fwd2(in, r.Cin, pk, nullptr, p->F(r.y3), C, C, nvox(v), p->st));
-    PLAN_CK(in_stats(p, v, C, r.y3, r.st[2]));
+    PLAN_CK(in_fwd(p, v, C, p->F(r.y3), r.st[2], p->F(p->ones), p->F(p->zeros)));
   }
-  PLAN_HIPCK(res_act(p->F(r.y2), p->F(r.st[1][2]), p->F(r.st[1][3]), r.has3 ? p->F(r.y3) : nullptr,
-                 p->F(r.st[2][2]), p->F(r.st[2][3]), ident, nullptr, p->F(r.out), v, C, p->st));
-  return SPFF_OK;
-}
-
-// IN (+ activation slope neg) backward: dy = IN'(g * slope(r)) for r = y*al + de
-template <class P>
-int in_bwd(P* p, const Vol& v, int C, size_t y, const float* g, float* dy,
-           const size_t* st4, float neg) {
-  RedArgs a{};
-  a.y = p->F(y); a.g = g; a.mean = p->F(st4[0]); a.rstd = p->F(st4[1]);
-  a.al = p->F(st4[2]); a.de = p->F(st4[3]); a.neg = neg;
-  PLAN_HIPCK(slab_reduce(RED_BWD_IN, a, v, C, p->F(p->red_out), p->F(p->red_ws), p->st));
-  float* dm = p->F(p->dummy);
-  PLAN_HIPCK(in_bwd_stats(p->F(p->red_out), p->F(p->ones), dm, dm + p->maxC, p->F(p->kk1),
-                      p->F(p->kk2), v, C, p->st));
-  PLAN_HIPCK(in_bwd_apply(p->F(y), g, dy, p->F(st4[0]), p->F(st4[1]), p->F(st4[2]), p->F(st4[3]),
-                      p->F(p->ones), nullptr, nullptr, p->F(p->kk1), p->F(p->kk2), v, C, p->st,
-                      neg));
+  PLAN_HIPCK(res_act(p->F(r.y2), p->F(r.st[1].al), p->F(r.st[1].de), r.has3 ? p->F(r.y3) : nullptr,
+                 p->F(r.st[2].al), p->F(r.st[2].de), ident, nullptr, p->F(r.out), v, C, p->st));
   return SPFF_OK;
 }
 
@@ -198,25 +119,22 @@ int rb_bwd(P* p, RB& r, const float* dout, const Src2& in, const float* ident,
   float* dz = p->F(p->G_dz);
   float* dy2 = p->F(p->G_dy2);
   float* da1 = p->F(p->G_da1);
-  PLAN_HIPCK(res_act(p->F(r.y2), p->F(r.st[1][2]), p->F(r.st[1][3]), r.has3 ? p->F(r.y3) : nullptr,
-                 p->F(r.st[2][2]), p->F(r.st[2][3]), ident, dout, dz, v, C, p->st));
-  PLAN_CK(in_bwd(p, v, C, r.y2, dz, dy2, r.st[1], 1.f));
-  PLAN_HIPCK(conv3d_wgrad(src1(p->F(r.a1), C), dy2, C, p->DP(r.w2), v, 3, C, C, math, p->F(p->wg_ws),
-                      p->st));
-  const float* img;
-  const unsigned* wmax;
-  PLAN_CK(conv_image(p, r, 2, v, &img, &wmax));
-  PLAN_HIPCK(conv3d_run(src1(dy2, C), img, dst1(da1, C), v, 3, C, C, true, math, p->st,
-                    p->F(p->wg_ws), nullptr, 0, wmax));
-  PLAN_CK(in_bwd(p, v, C, r.y1, da1, da1, r.st[0], 0.01f));
-  PLAN_HIPCK(conv3d_wgrad(in, da1, C, p->DP(r.w1), v, 3, r.Cin, C, math, p->F(p->wg_ws), p->st));
-  if (dsrc) {
-    PLAN_CK(conv_image(p, r, 3, v, &img, &wmax));
-    PLAN_HIPCK(conv3d_run(src1(da1, C), img, *dsrc, v, 3, r.Cin, C, true, math, p->st,
-                      p->F(p->wg_ws), nullptr, 0, wmax));
-  }
+  // affine-free IN (+ activation slope neg) backward: gamma = 1, dgamma / dbeta discarded
+  auto in_bwd1 = [&](size_t y, const float* g, float* dy, const Stat4& s, float neg) {
+    float* dm = p->F(p->dummy);
+    return in_bwd(p, v, C, p->F(y), g, dy, s, p->F(p->ones), dm, dm + p->maxC, neg);
+  };
+  PLAN_HIPCK(res_act(p->F(r.y2), p->F(r.st[1].al), p->F(r.st[1].de), r.has3 ? p->F(r.y3) : nullptr,
+                 p->F(r.st[2].al), p->F(r.st[2].de), ident, dout, dz, v, C, p->st));
+  PLAN_CK(in_bwd1(r.y2, dz, dy2, r.st[1], 1.f));
+  PLAN_HIPCK(conv3d_wgrad(src1(p->F(r.a1), C), dy2, C, p->DP(r.cv[1].w), v, 3, C, C, math,
+                      p->F(p->wg_ws), p->st));
+  PLAN_CK(conv_run(p, r.cv[1], true, src1(dy2, C), dst1(da1, C), v));
+  PLAN_CK(in_bwd1(r.y1, da1, da1, r.st[0], 0.01f));
+  PLAN_HIPCK(conv3d_wgrad(in, da1, C, p->DP(r.cv[0].w), v, 3, r.Cin, C, math, p->F(p->wg_ws), p->st));
+  if (dsrc) PLAN_CK(conv_run(p, r.cv[0], true, src1(da1, C), *dsrc, v));
   if (r.has3) {
-    PLAN_CK(in_bwd(p, v, C, r.y3, dz, dy2, r.st[2], 1.f));
+    PLAN_CK(in_bwd1(r.y3, dz, dy2, r.st[2], 1.f));
     PLAN_HIPCK(linear_wgrad2(in, r.Cin, dy2, C, C, p->DP(r.c3.w), p->F(p->dummy), V, p->F(p->wg_ws),
                          p->st));
     if (dsrc) {
@@ -224,7 +142,7 @@ int rb_bwd(P* p, RB& r, const float* dout, const Src2& in, const float* ident,
       PLAN_HIPCK(linear_dgrad2(dy2, C, C, wd, *dsrc, r.Cin, V, 1, p->st));
     }
   } else if (dsrc) {
-    PLAN_HIPCK(add_inplace(dsrc->p0, dz, V * C, p->st));
+    PLAN_HIPCK(accumulate(dsrc->p0, dz, V * C, 1.f, p->st));
   }
   return SPFF_OK;
 }

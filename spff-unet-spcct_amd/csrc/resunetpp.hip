@@ -36,7 +36,7 @@
 //
 // Order of every accumulation is fixed (single stream, ordered partial sums): two runs give
 // the same bits.
-#include "plan_base.h"
+#include "plan_ops.h"
 #include "swin_internal.h"
 
 #include <algorithm>
@@ -47,7 +47,7 @@ using namespace spff;
 
 namespace {
 
-constexpr int NLVL = 5, NUNIT = 10, NUP = 4, NSUB = 8, NBR = 4, NSE = 4, NAG = 3;
+constexpr int NLVL = 5, NUNIT = 10, NUP = 4, NBR = 4, NSE = 4, NAG = 3;
 constexpr int AG_NB = 256;  // blocks of the psi weight-gradient partial sums
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -287,17 +287,6 @@ __global__ __launch_bounds__(256) void k_rupp_relu(float* __restrict__ x, int64_
     float4 a = reinterpret_cast<float4*>(x)[i];
     a.x = fmaxf(a.x, 0.f); a.y = fmaxf(a.y, 0.f); a.z = fmaxf(a.z, 0.f); a.w = fmaxf(a.w, 0.f);
     reinterpret_cast<float4*>(x)[i] = a;
-  }
-}
-// dst += src
-__global__ __launch_bounds__(256) void k_rupp_acc(float* __restrict__ dst,
-                                                  const float* __restrict__ src, int64_t n4) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4;
-       i += (int64_t)gridDim.x * blockDim.x) {
-    float4 d = reinterpret_cast<float4*>(dst)[i];
-    const float4 v = reinterpret_cast<const float4*>(src)[i];
-    d.x += v.x; d.y += v.y; d.z += v.z; d.w += v.w;
-    reinterpret_cast<float4*>(dst)[i] = d;
   }
 }
 
@@ -565,21 +554,14 @@ __global__ __launch_bounds__(256) void k_ag_dhid(const float* __restrict__ att,
   }
 }
 
-struct PStat {
-  size_t mean, rstd, al, de;
-};
 struct PUnit {
   std::string name;
   int lvl, Cin, C;
   bool skip;
-  int64_t w1 = -1, g1 = -1, b1 = -1, w2 = -1, g2 = -1, b2 = -1, wsk = -1;
+  Conv3 cv[2];
+  int64_t g1 = -1, b1 = -1, g2 = -1, b2 = -1, wsk = -1;
   size_t y1, a1, y2, out, pk_sk = 0;
-  PStat s1, s2;
-};
-struct PUp {
-  int Cin, Cout, lvl_low;
-  int64_t w, b;
-  size_t pk, out;
+  Stat4 s1, s2;
 };
 struct PSe {
   int C, Hd, lvl;
@@ -599,13 +581,15 @@ struct spff_rupp : PlanBase {
   Vol vol[NLVL];
   int f, K, ldx;
   PUnit un[NUNIT];  // e1..e4, b_aspp_in, b_aspp_out, d4..d1
-  PUp up[NUP];      // up4..up1
+  UpConv up[NUP];   // up4..up1
   PSe se[NSE];      // se1..se4
   PAg ag[NAG];      // ag4, ag3, ag2
   int64_t w_br[NBR] = {}, w_proj = -1, head_w = -1, head_b = -1;
   size_t br_pk[NBR] = {}, cat = 0, dcat = 0, proj_pk = 0, aspp_out = 0;
   size_t head_pk = 0, x_cl = 0, pool[4] = {}, pidx[4] = {};
   size_t red_ws = 0, red_out = 0, kk1 = 0, kk2 = 0, wg_ws = 0, wt = 0, db_scr = 0;
+  static constexpr bool pkb = false;  // every conv image is packed before its conv, into wt
+  static constexpr size_t wsl = 0;
   size_t ones = 0, zeros = 0, ag_part = 0;
   size_t G_out = 0, G_s = 0, G_1 = 0, G_2 = 0, G_dx = 0, G_ds = 0, dskip[4] = {};
 };
@@ -617,10 +601,10 @@ const int DIL[NBR] = {1, 2, 4, 8};
 void reg_unit(spff_rupp* p, PUnit& u) {
   const int C = u.C;
   const std::string n = "backbone." + u.name;
-  u.w1 = p->reg(n + ".c1.weight", {C, u.Cin, 3, 3, 3});
+  u.cv[0] = reg_conv(p, n + ".c1.weight", u.Cin, C);
   u.g1 = p->reg(n + ".n1.weight", {C});
   u.b1 = p->reg(n + ".n1.bias", {C});
-  u.w2 = p->reg(n + ".c2.weight", {C, C, 3, 3, 3});
+  u.cv[1] = reg_conv(p, n + ".c2.weight", C, C);
   u.g2 = p->reg(n + ".n2.weight", {C});
   u.b2 = p->reg(n + ".n2.bias", {C});
   if (u.skip) u.wsk = p->reg(n + ".skip.weight", {C, u.Cin, 1, 1, 1});
@@ -683,10 +667,10 @@ int build(spff_rupp* p) {
     s.b2 = p->reg(n + "2.bias", {s.C});
   }
   for (int u = 0; u < NUP; ++u) {
-    PUp& U = p->up[u];
+    UpConv& U = p->up[u];
     U.Cin = 16 * f >> u;
     U.Cout = 8 * f >> u;
-    U.lvl_low = 4 - u;
+    U.Llow = 4 - u;
     const std::string lv = std::to_string(4 - u);
     U.w = p->reg("backbone.up" + lv + ".weight", {U.Cin, U.Cout, 2, 2, 2});
     U.b = p->reg("backbone.up" + lv + ".bias", {U.Cout});
@@ -718,15 +702,12 @@ int build(spff_rupp* p) {
     const int64_t M = nvox(v);
     const size_t act = M * u.C * sizeof(float);
     const size_t bc = (size_t)B * u.C * sizeof(float);
-    auto stat = [&](PStat& s) {
-      s.mean = p->alloc(bc); s.rstd = p->alloc(bc); s.al = p->alloc(bc); s.de = p->alloc(bc);
-    };
     u.y1 = p->alloc(act);
     u.a1 = p->alloc(act);
     u.y2 = p->alloc(act);
     u.out = p->alloc(act);
-    stat(u.s1);
-    stat(u.s2);
+    u.s1 = stat_alloc(p, bc);
+    u.s2 = stat_alloc(p, bc);
     const int kin = i == 0 ? p->ldx : u.Cin;
     if (u.skip) {
       u.pk_sk = p->alloc(head_pack_floats(kin, u.C) * sizeof(float));
@@ -780,11 +761,9 @@ int build(spff_rupp* p) {
     p->pidx[l] = p->alloc(nvox(vl) * C);
   }
   for (int u = 0; u < NUP; ++u) {
-    PUp& U = p->up[u];
-    const Vol& vh = p->vol[U.lvl_low - 1];
-    U.out = p->alloc(nvox(vh) * U.Cout * sizeof(float));
-    U.pk = p->alloc(upconv_pack_floats(U.Cin, U.Cout, NSUB) * sizeof(float));
-    wg = std::max(wg, upconv_wgrad_ws_bytes(p->vol[U.lvl_low], U.Cin, U.Cout, NSUB));
+    UpConv& U = p->up[u];
+    up_alloc(p, U);
+    wg = std::max(wg, upconv_wgrad_ws_bytes(p->vol[U.Llow], U.Cin, U.Cout, UP_NS));
   }
   p->head_pk = p->alloc(head_pack_floats(f, p->K) * sizeof(float));
   wg = std::max(wg, head_wgrad_ws_bytes(nvox(v0), f, p->K));
@@ -817,46 +796,6 @@ int build(spff_rupp* p) {
     PLAN_HIPCK(hipGetLastError());                                                         \
   } while (0)
 
-// InstanceNorm3d statistics of y per (b, c) and the apply coefficients al = gamma rstd,
-// de = beta - mean al
-int in_fwd(spff_rupp* p, const Vol& v, int C, const float* y, const PStat& s, const float* gamma,
-           const float* beta) {
-  RedArgs a{};
-  a.y = y;
-  PLAN_HIPCK(slab_reduce(RED_SUM, a, v, C, p->F(p->red_out), p->F(p->red_ws), p->st));
-  PLAN_HIPCK(in_mean(p->F(p->red_out), p->F(s.mean), v, C, p->st));
-  a.mean = p->F(s.mean);
-  PLAN_HIPCK(slab_reduce(RED_SQDEV, a, v, C, p->F(p->red_out), p->F(p->red_ws), p->st));
-  PLAN_HIPCK(in_rstd(p->F(p->red_out), gamma, beta, p->F(s.mean), p->F(s.rstd), p->F(s.al),
-                 p->F(s.de), v, C, p->st));
-  return SPFF_OK;
-}
-
-// InstanceNorm backward: dy = rstd gamma (dr - k1 - xhat k2) with dr = g slope(IN(y)).
-// neg = 0: the ReLU that follows the norm; neg = 1: g is already the gradient at the
-// norm's output (the residual tail's dz), no mask.
-int in_bwd(spff_rupp* p, const Vol& v, int C, const float* y, const float* g, float* dy,
-           const PStat& s, const float* gamma, float* dgamma, float* dbeta, float neg) {
-  RedArgs a{};
-  a.y = y; a.g = g; a.mean = p->F(s.mean); a.rstd = p->F(s.rstd);
-  a.al = p->F(s.al); a.de = p->F(s.de); a.neg = neg;
-  PLAN_HIPCK(slab_reduce(RED_BWD_IN, a, v, C, p->F(p->red_out), p->F(p->red_ws), p->st));
-  PLAN_HIPCK(in_bwd_stats(p->F(p->red_out), gamma, dgamma, dbeta, p->F(p->kk1), p->F(p->kk2), v, C,
-                      p->st));
-  PLAN_HIPCK(in_bwd_apply(y, g, dy, p->F(s.mean), p->F(s.rstd), p->F(s.al), p->F(s.de), gamma,
-                      nullptr, nullptr, p->F(p->kk1), p->F(p->kk2), v, C, p->st, neg));
-  return SPFF_OK;
-}
-
-// a 3x3x3 conv of the plan's arithmetic: pack the image, run it
-int conv(spff_rupp* p, const Src2& x, int64_t w, const Dst2& y, const Vol& v, int Cin_w,
-         int Cout_w, bool dgrad) {
-  const int math = p->cfg.math;
-  PLAN_HIPCK(conv3d_pack(p->P(w), p->F(p->wt), v, 3, Cin_w, Cout_w, dgrad, math, p->st));
-  PLAN_HIPCK(conv3d_run(x, p->F(p->wt), y, v, 3, Cin_w, Cout_w, dgrad, math, p->st, p->F(p->wg_ws)));
-  return SPFF_OK;
-}
-
 int fwd_unit(spff_rupp* p, PUnit& u, const Src2& in, int kin) {
   const Vol& v = p->vol[u.lvl];
   const int C = u.C;
@@ -868,11 +807,11 @@ int fwd_unit(spff_rupp* p, PUnit& u, const Src2& in, int kin) {
     PLAN_HIPCK(linear_fwd2(in, kin, pk, nullptr, p->F(p->G_s), C, C, M, p->st));
     sk = p->F(p->G_s);
   }
-  PLAN_CK(conv(p, in, u.w1, dst1(p->F(u.y1), C), v, u.Cin, C, false));
+  PLAN_CK(conv_run(p, u.cv[0], false, in, dst1(p->F(u.y1), C), v));
   PLAN_CK(in_fwd(p, v, C, p->F(u.y1), u.s1, p->P(u.g1), p->P(u.b1)));
   PLAN_HIPCK(act_apply(p->F(u.y1), p->F(u.a1), p->F(u.s1.al), p->F(u.s1.de), nullptr, nullptr, v, C,
                    p->st, 0.f));
-  PLAN_CK(conv(p, src1(p->F(u.a1), C), u.w2, dst1(p->F(u.y2), C), v, C, C, false));
+  PLAN_CK(conv_run(p, u.cv[1], false, src1(p->F(u.a1), C), dst1(p->F(u.y2), C), v));
   PLAN_CK(in_fwd(p, v, C, p->F(u.y2), u.s2, p->P(u.g2), p->P(u.b2)));
   EW(k_rupp_tail, M * C / 4, p->F(u.y2), p->F(u.s2.al), p->F(u.s2.de), sk, p->F(u.out),
      M * C / 4, C / 4, M / v.B);
@@ -890,18 +829,18 @@ int bwd_unit(spff_rupp* p, PUnit& u, const float* dout, const Dst2* dx, const Sr
   float* wgs = p->F(p->wg_ws);
   EW(k_rupp_mask, M * C / 4, dout, p->F(u.out), dz, M * C / 4);
   PLAN_CK(in_bwd(p, v, C, p->F(u.y2), dz, g1, u.s2, p->P(u.g2), p->DP(u.g2), p->DP(u.b2), 1.f));
-  PLAN_HIPCK(conv3d_wgrad(src1(p->F(u.a1), C), g1, C, p->DP(u.w2), v, 3, C, C, math, wgs, p->st));
-  PLAN_CK(conv(p, src1(g1, C), u.w2, dst1(g2, C), v, C, C, true));
+  PLAN_HIPCK(conv3d_wgrad(src1(p->F(u.a1), C), g1, C, p->DP(u.cv[1].w), v, 3, C, C, math, wgs, p->st));
+  PLAN_CK(conv_run(p, u.cv[1], true, src1(g1, C), dst1(g2, C), v));
   PLAN_CK(in_bwd(p, v, C, p->F(u.y1), g2, g2, u.s1, p->P(u.g1), p->DP(u.g1), p->DP(u.b1), 0.f));
-  PLAN_HIPCK(conv3d_wgrad(in, g2, C, p->DP(u.w1), v, 3, u.Cin, C, math, wgs, p->st));
-  if (dx) PLAN_CK(conv(p, src1(g2, C), u.w1, *dx, v, u.Cin, C, true));
+  PLAN_HIPCK(conv3d_wgrad(in, g2, C, p->DP(u.cv[0].w), v, 3, u.Cin, C, math, wgs, p->st));
+  if (dx) PLAN_CK(conv_run(p, u.cv[0], true, src1(g2, C), *dx, v));
   if (u.skip) {
     PLAN_HIPCK(linear_wgrad2(in, u.Cin, dz, C, C, p->DP(u.wsk), p->F(p->db_scr), M, wgs, p->st));
     if (dx)
       PLAN_HIPCK(linear_dgrad2(dz, C, C, p->F(u.pk_sk) + head_pack_dgrad_offset(kin, C), *dx, u.Cin,
                            M, 1, p->st));
   } else if (dx) {
-    EW(k_rupp_acc, M * C / 4, dx->p0, dz, M * C / 4);
+    PLAN_HIPCK(accumulate(dx->p0, dz, M * C, 1.f, p->st));
   }
   return SPFF_OK;
 }
@@ -1013,13 +952,9 @@ int forward(spff_rupp* p, const float* x, float* logits) {
   PLAN_CK(fwd_unit(p, U[5], src1(p->F(p->aspp_out), C4), C4));
   const float* prev = p->F(U[5].out);
   for (int u = 0; u < NUP; ++u) {
-    PUp& Up = p->up[u];
+    UpConv& Up = p->up[u];
     const int lvl = 3 - u, C = Up.Cout;
-    float* pk = p->F(Up.pk);
-    PLAN_HIPCK(upconv_pack(p->P(Up.w), pk, pk + upconv_pack_dgrad_offset(Up.Cin, Up.Cout, NSUB),
-                       Up.Cin, Up.Cout, p->st, NSUB));
-    PLAN_HIPCK(upconv_fwd(prev, pk, p->P(Up.b), p->F(Up.out), p->vol[Up.lvl_low], Up.Cin, Up.Cout,
-                      p->st, NSUB, p->cfg.math));
+    PLAN_CK(up_fwd(p, Up, prev, p->P(Up.b), p->cfg.math));
     const float* second = p->F(p->se[lvl].out);
     if (u < NAG) {
       PLAN_CK(ag_fwd(p, p->ag[u], p->F(Up.out), p->F(p->se[lvl].out)));
@@ -1029,28 +964,20 @@ int forward(spff_rupp* p, const float* x, float* logits) {
     PLAN_CK(fwd_unit(p, d, Src2{p->F(Up.out), second, C, C, C}, 2 * C));
     prev = p->F(d.out);
   }
-  float* hp = p->F(p->head_pk);
-  PLAN_HIPCK(head_pack(p->P(p->head_w), hp, hp + head_pack_dgrad_offset(f, p->K), f, p->K, p->st));
-  PLAN_HIPCK(head_fwd(prev, hp, p->P(p->head_b), logits, nvox(v0), f, p->K, p->st, p->cfg.math));
-  return SPFF_OK;
+  return head_fwd_packed(p, p->head_w, p->head_b, prev, logits);
 }
 
 int backward(spff_rupp* p, const float* dl) {
   const int f = p->f, C4 = 16 * f;
-  const int64_t V0 = nvox(p->vol[0]);
   const Vol& v4 = p->vol[4];
   const int64_t M4 = nvox(v4);
   PUnit* U = p->un;
   float* wgs = p->F(p->wg_ws);
-  float* hp = p->F(p->head_pk);
-  PLAN_HIPCK(head_wgrad(p->F(U[9].out), dl, p->DP(p->head_w), p->DP(p->head_b), V0, f, p->K, wgs,
-                    p->st));
-  PLAN_HIPCK(head_dgrad(dl, hp + head_pack_dgrad_offset(f, p->K), p->F(p->G_out), V0, f, p->K, p->st,
-                    p->cfg.math));
+  PLAN_CK(head_bwd(p, p->head_w, p->head_b, p->F(U[9].out), dl, p->F(p->G_out)));
   for (int lvl = 0; lvl < 4; ++lvl) {  // d1 <- up1 <- d2 ... <- up4
     const int u = 3 - lvl;
     PUnit& d = U[6 + u];
-    PUp& Up = p->up[u];
+    UpConv& Up = p->up[u];
     const int C = d.C;
     const bool gated = u < NAG;
     const float* second = gated ? p->F(p->ag[u].s) : p->F(p->se[lvl].out);
@@ -1062,13 +989,8 @@ int backward(spff_rupp* p, const float* dl) {
       PLAN_CK(ag_bwd(p, p->ag[u], p->F(Up.out), p->F(p->se[lvl].out), p->F(p->G_ds), p->F(p->G_dx),
                  p->F(p->dskip[lvl])));
     PLAN_CK(se_bwd(p, p->se[lvl], p->F(U[lvl].out), p->F(p->dskip[lvl])));
-    const Vol& low = p->vol[Up.lvl_low];
     const float* below = u == 0 ? p->F(U[5].out) : p->F(U[6 + u - 1].out);
-    PLAN_HIPCK(upconv_wgrad(below, p->F(p->G_dx), C, p->DP(Up.w), p->DP(Up.b), low, Up.Cin, Up.Cout,
-                        wgs, p->st, NSUB, p->cfg.math));
-    float* pk = p->F(Up.pk);
-    PLAN_HIPCK(upconv_dgrad(p->F(p->G_dx), C, pk + upconv_pack_dgrad_offset(Up.Cin, Up.Cout, NSUB),
-                        p->F(p->G_out), low, Up.Cin, Up.Cout, p->st, NSUB, p->cfg.math));
+    PLAN_CK(up_bwd(p, Up, below, p->F(p->G_dx), p->DP(Up.b), p->F(p->G_out), p->cfg.math));
   }
   {  // bottleneck
     Dst2 dx = dst1(p->F(p->G_dx), C4);

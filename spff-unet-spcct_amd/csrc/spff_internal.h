@@ -517,6 +517,8 @@ hipError_t maxpool_fwd(const float* x, float* y, uint8_t* idx, Vol in, int C, hi
 hipError_t maxpool_bwd_add(const float* dp, const uint8_t* idx, const float* dskip, int ldskip,
                            float* dx, Vol in, int C, hipStream_t s);
 hipError_t scale_by_dev(float* x, int64_t n, const float* scale, hipStream_t s);
+// dst[i] += scale * src[i], i < n (any alignment)
+hipError_t accumulate(float* dst, const float* src, int64_t n, float scale, hipStream_t s);
 // stream-ordered fill of 32-bit words by a kernel (graph-capturable in place of
 // hipMemsetAsync); bytes and p multiples of 4
 hipError_t fill32_async(void* p, size_t bytes, unsigned value, hipStream_t s);

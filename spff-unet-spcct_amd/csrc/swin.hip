@@ -45,18 +45,17 @@ struct spff_swin : PlanBase {
   spff_swin_cfg cfg;
   Vol vol[NL];
   int f, K, ldx;
-  static constexpr int kNRB = NRB;
   int64_t pe_w = -1, pe_b = -1;
   size_t pe_pk = 0;
   Stage stg[NST];
   RB rb[NRB];  // enc0, enc1, enc2, enc3, enc10, dec5, dec4, dec3, dec2, dec1
-  Up up[NUP];  // decoder5 .. decoder1 transposed convs
+  UpConv up[NUP];  // decoder5 .. decoder1 transposed convs
   Lin head;
   size_t x_cl = 0, t[5] = {}, hs[5] = {}, hmu[5] = {}, hrs[5] = {};
   size_t ones = 0, zeros = 0, dummy = 0, red_ws = 0, red_out = 0, kk1 = 0, kk2 = 0, wg_ws = 0,
          wt = 0, cst = 0;
-  bool pkb = false;  // conv images packed in one batch at the forward start (rb[i].pk)
-  size_t wsl = 0;    // SPFF_MATH_F16X3 max |w| per conv, [NRB][2] (batched plans)
+  bool pkb = false;  // conv images packed in one batch at the forward start
+  size_t wsl = 0;    // SPFF_MATH_F16X3 max |w| per conv (batched plans)
   // backward scratch
   size_t G_out = 0, G_dz = 0, G_dy2 = 0, G_da1 = 0, G_up = 0;
   size_t d_enc[4] = {}, d_hs[5] = {}, dT[5] = {};
@@ -122,6 +121,7 @@ int build(spff_swin* p) {
   }
   RB* R = p->rb;
   reg_rb(p, R[0], "encoder1.layer", 0, c.in_ch, f);
+  R[0].cv[0].dx = false;  // the network's input
   reg_rb(p, R[1], "encoder2.layer", 1, f, f);
   reg_rb(p, R[2], "encoder3.layer", 2, 2 * f, 2 * f);
   reg_rb(p, R[3], "encoder4.layer", 3, 4 * f, 4 * f);
@@ -130,7 +130,7 @@ int build(spff_swin* p) {
   const int uci[NUP] = {16 * f, 8 * f, 4 * f, 2 * f, f};
   const int uco[NUP] = {8 * f, 4 * f, 2 * f, f, f};
   for (int u = 0; u < NUP; ++u) {
-    Up& U = p->up[u];
+    UpConv& U = p->up[u];
     U.Cin = uci[u];
     U.Cout = uco[u];
     U.Llow = 5 - u;
@@ -197,13 +197,7 @@ int build(spff_swin* p) {
     const Vol& v = p->vol[r.L];
     const int64_t V = nvox(v);
     const int C = r.C;
-    r.y1 = p->alloc(fbytes(V * C));
-    r.a1 = p->alloc(fbytes(V * C));
-    r.y2 = p->alloc(fbytes(V * C));
-    r.y3 = r.has3 ? p->alloc(fbytes(V * C)) : 0;
-    r.out = p->alloc(fbytes(V * C));
-    for (int k = 0; k < 3; ++k)
-      for (int j = 0; j < 4; ++j) r.st[k][j] = p->alloc(fbytes((int64_t)B * C));
+    rb_alloc(p, r);
     red_ws = std::max(red_ws, slab_reduce_ws_bytes(v, C, 2));
     red_out = std::max(red_out, fbytes((int64_t)B * C * v.D * 2));
     wg = std::max(wg, conv3d_wgrad_ws_bytes(v, 3, r.Cin, C));
@@ -220,9 +214,8 @@ int build(spff_swin* p) {
     maxC = std::max(maxC, std::max(C, r.Cin));
   }
   for (int u = 0; u < NUP; ++u) {
-    Up& U = p->up[u];
-    U.out = p->alloc(fbytes(nvox(p->vol[U.Llow - 1]) * U.Cout));
-    U.pk = p->alloc(upconv_pack_floats(U.Cin, U.Cout, 8) * sizeof(float));
+    UpConv& U = p->up[u];
+    up_alloc(p, U);
     wg = std::max(wg, upconv_wgrad_ws_bytes(p->vol[U.Llow], U.Cin, U.Cout, 8));
   }
   wg = std::max(wg, linear_wgrad_ws_bytes(nvox(v0), f, p->K));
@@ -236,19 +229,7 @@ int build(spff_swin* p) {
   p->kk1 = p->alloc(fbytes((int64_t)B * maxC));
   p->kk2 = p->alloc(fbytes((int64_t)B * maxC));
   p->wg_ws = p->alloc(wg);
-  p->pkb = conv3d_packs_batched(c.math);
-  if (p->pkb) {
-    for (int i = 0; i < NRB; ++i) {
-      RB& r = R[i];
-      r.pk[0] = p->alloc(conv3d_pack_bytes(3, r.Cin, r.C));
-      r.pk[1] = p->alloc(conv3d_pack_bytes(3, r.C, r.C));
-      r.pk[2] = p->alloc(conv3d_pack_bytes(3, r.C, r.C));
-      if (i > 0) r.pk[3] = p->alloc(conv3d_pack_bytes(3, r.Cin, r.C));  // enc0's input: no dx
-    }
-    p->wsl = p->alloc(NRB * 2 * sizeof(unsigned));
-  } else {
-    p->wt = p->alloc(wt);
-  }
+  alloc_convs(p, R, NRB, wt);
   p->cst = p->alloc(cst);
   p->G_out = p->alloc(gmax);
   p->G_dz = p->alloc(gmax);
@@ -335,7 +316,7 @@ int stage_bwd(spff_swin* p, Stage& S, const float* tin, const float* dtout, floa
   PLAN_HIPCK(hipMemcpyAsync(A, dpad, fbytes(3 * C), hipMemcpyDeviceToDevice, st));  // A free again
   PLAN_HIPCK(linear_wgrad(p->F(S.n1), C, C, dq, 3 * C, 3 * C, p->DP(S.qkv.w), p->DP(S.qkv.b), T, wg,
                       st));
-  PLAN_HIPCK(add_inplace(p->DP(S.qkv.b), A, 3 * C, st));
+  PLAN_HIPCK(accumulate(p->DP(S.qkv.b), A, 3 * C, 1.f, st));
   // d t = d x1 + LN1'(d n1)
   PLAN_HIPCK(ln_bwd(tin, C, C, p->P(S.n1w), p->F(S.mu1), p->F(S.rs1), Bf, C, dtin, C, Cf, C,
                 p->DP(S.n1w), wg, T, st));
@@ -362,7 +343,7 @@ int forward(spff_swin* p, const float* x, float* logits) {
     PLAN_HIPCK(ln_fwd(p->F(p->t[l]), C, C, nullptr, nullptr, p->F(p->hs[l]), C, p->F(p->hmu[l]),
                   p->F(p->hrs[l]), nvox(p->vol[l + 1]), st));
   }
-  PLAN_CK(prep_weights(p));
+  PLAN_CK(prep_convs(p, p->rb, NRB));
   RB* R = p->rb;
   PLAN_CK(rb_fwd(p, R[0], src1(p->F(p->x_cl), p->ldx), nullptr));
   for (int i = 1; i < 4; ++i) {
@@ -374,11 +355,8 @@ int forward(spff_swin* p, const float* x, float* logits) {
   const float* skip[NUP] = {p->F(p->hs[3]), p->F(R[3].out), p->F(R[2].out), p->F(R[1].out),
                             p->F(R[0].out)};
   for (int u = 0; u < NUP; ++u) {
-    Up& U = p->up[u];
-    float* upk = p->F(U.pk);
-    PLAN_HIPCK(upconv_pack(p->P(U.w), upk, upk + upconv_pack_dgrad_offset(U.Cin, U.Cout, 8), U.Cin,
-                       U.Cout, st, 8));
-    PLAN_HIPCK(upconv_fwd(prev, upk, p->F(p->zeros), p->F(U.out), p->vol[U.Llow], U.Cin, U.Cout, st, 8));
+    UpConv& U = p->up[u];
+    PLAN_CK(up_fwd(p, U, prev, p->F(p->zeros)));
     RB& r = R[5 + u];
     PLAN_CK(rb_fwd(p, r, Src2{p->F(U.out), skip[u], U.Cout, U.Cout, U.Cout}, nullptr));
     prev = p->F(r.out);
@@ -408,17 +386,13 @@ int backward(spff_swin* p, const float* dl) {
   const float* skip[NUP] = {p->F(p->hs[3]), p->F(R[3].out), p->F(R[2].out), p->F(R[1].out),
                             p->F(R[0].out)};
   for (int u = NUP - 1; u >= 0; --u) {
-    Up& U = p->up[u];
+    UpConv& U = p->up[u];
     RB& r = R[5 + u];
     float* dup = p->F(p->G_up);
     Dst2 dx{dup, dskip[u], U.Cout, U.Cout, U.Cout};
     PLAN_CK(rb_bwd(p, r, Gout, Src2{p->F(U.out), skip[u], U.Cout, U.Cout, U.Cout}, nullptr, &dx));
     const float* xlow = p->F(u == 0 ? R[4].out : R[5 + u - 1].out);
-    PLAN_HIPCK(upconv_wgrad(xlow, dup, U.Cout, p->DP(U.w), p->F(p->dummy), p->vol[U.Llow], U.Cin, U.Cout,
-                        wg, st, 8));
-    float* upk = p->F(U.pk);
-    PLAN_HIPCK(upconv_dgrad(dup, U.Cout, upk + upconv_pack_dgrad_offset(U.Cin, U.Cout, 8), Gout,
-                        p->vol[U.Llow], U.Cin, U.Cout, st, 8));
+    PLAN_CK(up_bwd(p, U, xlow, dup, p->F(p->dummy), Gout));
   }
   // Gout = d enc10.out
   {
@@ -516,8 +490,8 @@ int spff_swin_saved_tensor(const spff_swin* p, void* ws, const char* name, const
     for (int k = 0; k < 3; ++k) {
       if (k == 2 && !r.has3) break;
       const std::string j = std::to_string(k + 1);
-      if (n == r.name + ".al" + j) return ret(r.st[k][2], p->cfg.batch, r.C);
-      if (n == r.name + ".de" + j) return ret(r.st[k][3], p->cfg.batch, r.C);
+      if (n == r.name + ".al" + j) return ret(r.st[k].al, p->cfg.batch, r.C);
+      if (n == r.name + ".de" + j) return ret(r.st[k].de, p->cfg.batch, r.C);
     }
   }
   const char* upn[NUP] = {"up5", "up4", "up3", "up2", "up1"};

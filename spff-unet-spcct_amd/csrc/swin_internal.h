@@ -34,7 +34,6 @@ hipError_t unmerge(const float* dcat, int Cf, int B, int D, int H, int W, float*
 hipError_t res_act(const float* y2, const float* al2, const float* de2, const float* y3,
                    const float* al3, const float* de3, const float* r, const float* dout,
                    float* out, Vol v, int C, hipStream_t s);
-hipError_t add_inplace(float* y, const float* x, int64_t n, hipStream_t s);
 // out[i] (+)= sum_k part[k*stride + i] (k < n, in order), i < count
 hipError_t col_reduce(const float* part, int n, int64_t stride, int count, float* out, int acc,
                       hipStream_t s);

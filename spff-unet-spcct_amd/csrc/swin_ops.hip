@@ -488,18 +488,6 @@ hipError_t res_act(const float* y2, const float* al2, const float* de2, const fl
   return hipGetLastError();
 }
 
-// y += x (elementwise, n floats)
-__global__ void k_add(float* __restrict__ y, const float* __restrict__ x, int64_t n) {
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
-       i += (int64_t)gridDim.x * blockDim.x)
-    y[i] += x[i];
-}
-hipError_t add_inplace(float* y, const float* x, int64_t n, hipStream_t s) {
-  hipLaunchKernelGGL(k_add, dim3((unsigned)std::min<int64_t>(cdiv64(n, 256), 16384)), dim3(256), 0,
-                     s, y, x, n);
-  return hipGetLastError();
-}
-
 // ------------------------------------------------- soft Dice + CE loss --
 // LitSwinUNETR_Published._loss (models.py:910-928):
 //   L = (1-w) * (1 - mean_{b, c>=sc} 2 I/(P+G+eps)) + w * CE(ignore),

@@ -40,7 +40,6 @@ struct Blk {
 }  // namespace
 
 struct spff_unetr : PlanBase {
-  static constexpr int kNRB = NRB;
   spff_unetr_cfg cfg;
   Vol vol[NLV];
   int f, K, ldx, hid, mlp, nh, n;  // n: tokens per sample
@@ -52,7 +51,7 @@ struct spff_unetr : PlanBase {
   // rb: enc1, enc2.blocks.0.1, enc2.blocks.1.1, enc3.blocks.0.1, dec5, dec4, dec3, dec2
   RB rb[NRB];
   // up: enc2.init, enc2.b0, enc2.b1, enc3.init, enc3.b0, enc4.init, dec5 .. dec2
-  Up up[NUP];
+  UpConv up[NUP];
   Lin head;
   size_t x_cl = 0, rows = 0, tok = 0, hN = 0, nmu = 0, nrs = 0, lg = 0;
   size_t ones = 0, zeros = 0, dummy = 0, red_ws = 0, red_out = 0, kk1 = 0, kk2 = 0, wg_ws = 0,
@@ -67,7 +66,7 @@ struct spff_unetr : PlanBase {
 
 namespace {
 
-void reg_up(spff_unetr* p, Up& U, const std::string& name, int Cin, int Cout, int Llow) {
+void reg_up(spff_unetr* p, UpConv& U, const std::string& name, int Cin, int Cout, int Llow) {
   U.Cin = Cin;
   U.Cout = Cout;
   U.Llow = Llow;
@@ -126,8 +125,9 @@ int build(spff_unetr* p) {
   p->nfw = p->reg("vit.norm.weight", {Hd});
   p->nfb = p->reg("vit.norm.bias", {Hd});
   RB* R = p->rb;
-  Up* U = p->up;
+  UpConv* U = p->up;
   reg_rb(p, R[0], "encoder1.layer", 0, c.in_ch, f);
+  R[0].cv[0].dx = false;  // the network's input
   reg_up(p, U[0], "encoder2.transp_conv_init", Hd, 2 * f, 4);
   reg_up(p, U[1], "encoder2.blocks.0.0", 2 * f, 2 * f, 3);
   reg_rb(p, R[1], "encoder2.blocks.0.1", 2, 2 * f, 2 * f);
@@ -195,13 +195,7 @@ int build(spff_unetr* p) {
     const Vol& v = p->vol[r.L];
     const int64_t V = nvox(v);
     const int C = r.C;
-    r.y1 = p->alloc(fbytes(V * C));
-    r.a1 = p->alloc(fbytes(V * C));
-    r.y2 = p->alloc(fbytes(V * C));
-    r.y3 = r.has3 ? p->alloc(fbytes(V * C)) : 0;
-    r.out = p->alloc(fbytes(V * C));
-    for (int k = 0; k < 3; ++k)
-      for (int j = 0; j < 4; ++j) r.st[k][j] = p->alloc(fbytes((int64_t)B * C));
+    rb_alloc(p, r);
     red_ws = std::max(red_ws, slab_reduce_ws_bytes(v, C, 2));
     red_out = std::max(red_out, fbytes((int64_t)B * C * v.D * 2));
     wg = std::max(wg, conv3d_wgrad_ws_bytes(v, 3, r.Cin, C));
@@ -218,10 +212,9 @@ int build(spff_unetr* p) {
     maxC = std::max(maxC, std::max(C, r.Cin));
   }
   for (int u = 0; u < NUP; ++u) {
-    Up& X = U[u];
+    UpConv& X = U[u];
     const int64_t Vh = nvox(p->vol[X.Llow - 1]);
-    X.out = p->alloc(fbytes(Vh * X.Cout));
-    X.pk = p->alloc(upconv_pack_floats(X.Cin, X.Cout, 8) * sizeof(float));
+    up_alloc(p, X);
     wg = std::max(wg, upconv_wgrad_ws_bytes(p->vol[X.Llow], X.Cin, X.Cout, 8));
     gmax = std::max(gmax, fbytes(Vh * X.Cout));
     gmax = std::max(gmax, fbytes(nvox(p->vol[X.Llow]) * X.Cin));
@@ -236,19 +229,7 @@ int build(spff_unetr* p) {
   p->kk1 = p->alloc(fbytes((int64_t)B * maxC));
   p->kk2 = p->alloc(fbytes((int64_t)B * maxC));
   p->wg_ws = p->alloc(wg);
-  p->pkb = conv3d_packs_batched(c.math);
-  if (p->pkb) {
-    for (int i = 0; i < NRB; ++i) {
-      RB& r = R[i];
-      r.pk[0] = p->alloc(conv3d_pack_bytes(3, r.Cin, r.C));
-      r.pk[1] = p->alloc(conv3d_pack_bytes(3, r.C, r.C));
-      r.pk[2] = p->alloc(conv3d_pack_bytes(3, r.C, r.C));
-      if (i > 0) r.pk[3] = p->alloc(conv3d_pack_bytes(3, r.Cin, r.C));  // enc1's input: no dx
-    }
-    p->wsl = p->alloc(NRB * 2 * sizeof(unsigned));
-  } else {
-    p->wt = p->alloc(wt);
-  }
+  alloc_convs(p, R, NRB, wt);
   p->cst = p->alloc(cst);
   p->G_out = p->alloc(gmax);
   p->G_dz = p->alloc(gmax);
@@ -269,22 +250,10 @@ const float* wd_of(spff_unetr* p, const Lin& l) {
   return p->F(l.pk) + head_pack_dgrad_offset(l.K, l.N);
 }
 
-int up_fwd(spff_unetr* p, Up& U, const float* x) {
-  float* upk = p->F(U.pk);
-  PLAN_HIPCK(upconv_pack(p->P(U.w), upk, upk + upconv_pack_dgrad_offset(U.Cin, U.Cout, 8), U.Cin,
-                     U.Cout, p->st, 8));
-  PLAN_HIPCK(upconv_fwd(x, upk, p->F(p->zeros), p->F(U.out), p->vol[U.Llow], U.Cin, U.Cout, p->st, 8));
-  return SPFF_OK;
-}
-// dout [high][Cout] -> the weight gradient and (dx non-null) dx [low][Cin], written
-int up_bwd(spff_unetr* p, Up& U, const float* x, const float* dout, float* dx) {
-  PLAN_HIPCK(upconv_wgrad(x, dout, U.Cout, p->DP(U.w), p->F(p->dummy), p->vol[U.Llow], U.Cin, U.Cout,
-                      p->F(p->wg_ws), p->st, 8));
-  if (dx) {
-    const float* wd = p->F(U.pk) + upconv_pack_dgrad_offset(U.Cin, U.Cout, 8);
-    PLAN_HIPCK(upconv_dgrad(dout, U.Cout, wd, dx, p->vol[U.Llow], U.Cin, U.Cout, p->st, 8));
-  }
-  return SPFF_OK;
+// the MONAI transposed convs have no bias: zeros forward, dummy takes the bias gradient
+int up_fwd(spff_unetr* p, UpConv& U, const float* x) { return up_fwd(p, U, x, p->F(p->zeros)); }
+int up_bwd(spff_unetr* p, UpConv& U, const float* x, const float* dout, float* dx) {
+  return up_bwd(p, U, x, dout, p->F(p->dummy), dx);
 }
 
 int block_fwd(spff_unetr* p, Blk& b, const float* tin) {
@@ -372,9 +341,9 @@ int forward(spff_unetr* p, const float* x, float* logits) {
   PLAN_HIPCK(ln_fwd(p->F(p->blk[NBLK - 1].x2), Hd, Hd, p->P(p->nfw), p->P(p->nfb), p->F(p->hN), Hd,
                 p->F(p->nmu), p->F(p->nrs), T, st));
   pv.end(st);
-  PLAN_CK(prep_weights(p));
+  PLAN_CK(prep_convs(p, p->rb, NRB));
   RB* R = p->rb;
-  Up* U = p->up;
+  UpConv* U = p->up;
   PLAN_CK(rb_fwd(p, R[0], src1(p->F(p->x_cl), p->ldx), nullptr));
   // encoder2: hs[3] -> T -> (T, RB) -> (T, RB)
   PLAN_CK(up_fwd(p, U[0], p->F(p->blk[3].x2)));
@@ -391,7 +360,7 @@ int forward(spff_unetr* p, const float* x, float* logits) {
   const float* prev = p->F(p->hN);
   const float* skip[4] = {p->F(U[5].out), p->F(R[3].out), p->F(R[2].out), p->F(R[0].out)};
   for (int u = 0; u < 4; ++u) {
-    Up& X = U[6 + u];
+    UpConv& X = U[6 + u];
     PLAN_CK(up_fwd(p, X, prev));
     RB& r = R[4 + u];
     PLAN_CK(rb_fwd(p, r, Src2{p->F(X.out), skip[u], X.Cout, X.Cout, X.Cout}, nullptr));
@@ -416,7 +385,7 @@ int backward(spff_unetr* p, const float* dl) {
   const int64_t T = (int64_t)B * n;
   hipStream_t st = p->st;
   RB* R = p->rb;
-  Up* U = p->up;
+  UpConv* U = p->up;
   float* wg = p->F(p->wg_ws);
   float* Gout = p->F(p->G_out);
   float* dup = p->F(p->G_up);
@@ -434,7 +403,7 @@ int backward(spff_unetr* p, const float* dl) {
   float* dskip[4] = {p->F(p->d_enc[3]), p->F(p->d_enc[2]), p->F(p->d_enc[1]), p->F(p->d_enc[0])};
   const float* skip[4] = {p->F(U[5].out), p->F(R[3].out), p->F(R[2].out), p->F(R[0].out)};
   for (int u = 3; u >= 0; --u) {
-    Up& X = U[6 + u];
+    UpConv& X = U[6 + u];
     RB& r = R[4 + u];
     Dst2 dx{dup, dskip[u], X.Cout, X.Cout, X.Cout};
     PLAN_CK(rb_bwd(p, r, Gout, Src2{p->F(X.out), skip[u], X.Cout, X.Cout, X.Cout}, nullptr, &dx));
@@ -467,9 +436,9 @@ int backward(spff_unetr* p, const float* dl) {
                 p->F(p->d_hN), Hd, A, Hd, nullptr, 0, p->DP(p->nfw), wg, T, st));
   float* dtin = p->F(p->d_hN);  // free from here on
   for (int i = NBLK - 1; i >= 0; --i) {
-    if (i == 9) PLAN_HIPCK(add_inplace(A, p->F(p->d_tap[2]), T * Hd, st));
-    if (i == 6) PLAN_HIPCK(add_inplace(A, p->F(p->d_tap[1]), T * Hd, st));
-    if (i == 3) PLAN_HIPCK(add_inplace(A, p->F(p->d_tap[0]), T * Hd, st));
+    if (i == 9) PLAN_HIPCK(accumulate(A, p->F(p->d_tap[2]), T * Hd, 1.f, st));
+    if (i == 6) PLAN_HIPCK(accumulate(A, p->F(p->d_tap[1]), T * Hd, 1.f, st));
+    if (i == 3) PLAN_HIPCK(accumulate(A, p->F(p->d_tap[0]), T * Hd, 1.f, st));
     PLAN_CK(block_bwd(p, p->blk[i], block_in(p, i), A, dtin));
     std::swap(A, dtin);
   }
@@ -530,7 +499,7 @@ int spff_unetr_saved_tensor(const spff_unetr* p, void* ws, const char* name, con
   if (s == "h9") return ret(p->blk[9].x2, T, p->hid);
   if (s == "hN") return ret(p->hN, T, p->hid);
   const RB* R = p->rb;
-  const Up* U = p->up;
+  const UpConv* U = p->up;
   auto rbout = [&](const RB& r) { return ret(r.out, nvox(p->vol[r.L]), r.C); };
   if (s == "enc1") return rbout(R[0]);
   if (s == "enc2") return rbout(R[2]);
