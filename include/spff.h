@@ -159,7 +159,9 @@ int spff_saved_tensor(const spff_plan* plan, void* workspace, const char* name,
 
 /* debug knobs (tests): key 0 = stop the backward after N decoder blocks (-1 off);
  * key 1 = also store the block outputs the up-conv / head GEMMs apply on the fly
- * (bott/dec*.out; otherwise spff_saved_tensor reports them as not stored) */
+ * (bott/dec*.out; otherwise spff_saved_tensor reports them as not stored);
+ * key 4 = 0: the head's backward as passes of its own (weight gradient, input gradient)
+ * before the last block's tail reduction, instead of folded into that block's passes */
 int spff_debug_set(spff_plan* plan, int key, int value);
 
 /* optional HIP-event timing of the engine's kernels on the plan's stream (bench.py):

@@ -149,6 +149,8 @@ struct spff_plan : PlanBase {
   bool keep_out = false;  // debug: store the fused block outputs too (saved views)
   bool pool_fold = SPFF_POOL_FOLD;  // PoolAdd in the encoder backward (debug key 2: off)
   bool bst_fuse = true;  // conv1's IN-backward sums in the dgrad epilogue (debug key 3: off)
+  bool head_fold = true;  // the head's backward inside dec1's tail pass (debug key 4: off)
+  size_t wg_bytes = 0;    // size of wg_ws (the fold's partials must fit it: the layout is fixed)
   // depth-sharded plans: side stream + events of the halo exchange that overlaps the
   // interior depth tiles of the next convolution (conv_halo)
   hipStream_t st2 = nullptr;
@@ -435,6 +437,7 @@ int build_plan(spff_plan* p) {
   p->kk1 = p->alloc((size_t)B * 8 * f * sizeof(float));
   p->kk2 = p->alloc((size_t)B * 8 * f * sizeof(float));
   p->wg_ws = p->alloc(wg);
+  p->wg_bytes = wg;
   // (the lean layout keeps the one scratch image: it trades time for the smallest footprint)
   p->pkb = !p->lean && conv3d_packs_batched(p->cfg.math);
   if (p->pkb) {
@@ -1015,8 +1018,11 @@ int hsh_gate_grads(spff_plan* p, const Blk& b, GateGrads& gg) {
   return SPFF_OK;
 }
 
+// hs (dec1 with the head folded in, backward()): the output gradient is never stored -- dout
+// is unused, head_tail_bwd has left the tail sums in red_out / red_out4, and the IN-backward
+// apply forms its rows from the dlogits (HeadSrc)
 int bwd_block(spff_plan* p, Blk& b, const float* dout, const Dst2* dx, const Src2& in_saved,
-              int dec_bi = -1, PoolAdd pa = {}) {
+              int dec_bi = -1, PoolAdd pa = {}, const HeadSrc* hs = nullptr) {
   const Vol& v = p->vol[b.lvl];
   const int C = b.C, KD = p->KD;
   Src2 in = in_saved;
@@ -1032,11 +1038,13 @@ int bwd_block(spff_plan* p, Blk& b, const float* dout, const Dst2* dx, const Src
     a.rstd = p->F(b.rstd2);
     a.pa = pa;
     // (SPFF_RED_FUSE: the IN-backward sums of y2 in the same pass, RED_BWD_TAIL6)
-    PROFB(p, 4, 0.0, 8.0 * (double)nvox(v) * C,
-          SPFF_RED_FUSE ? slab_reduce(RED_BWD_TAIL6, a, v, C, p->F(p->red_out), p->F(p->red_ws),
-                                      p->st, p->F(p->red_out4))
-                        : slab_reduce(RED_BWD_TAIL, a, v, C, p->F(p->red_out), p->F(p->red_ws),
-                                      p->st));
+    if (!hs) {
+      PROFB(p, 4, 0.0, 8.0 * (double)nvox(v) * C,
+            SPFF_RED_FUSE ? slab_reduce(RED_BWD_TAIL6, a, v, C, p->F(p->red_out), p->F(p->red_ws),
+                                        p->st, p->F(p->red_out4))
+                          : slab_reduce(RED_BWD_TAIL, a, v, C, p->F(p->red_out), p->F(p->red_ws),
+                                        p->st));
+    }
     GateParams gp = gate_params(p, b);
     GateSaved sv = gate_saved(p, b);
     GateGrads gg;
@@ -1089,7 +1097,7 @@ int bwd_block(spff_plan* p, Blk& b, const float* dout, const Dst2* dx, const Src
     PROFB(p, 6, 0.0, 12.0 * (double)nvox(v) * C,
           in_bwd_apply(p->F(b.y2), dout, dy2, p->F(b.mean2), p->F(b.rstd2), p->F(b.al2),
                        p->F(b.de2), p->P(b.g2), A, Bc, p->F(p->kk1), p->F(p->kk2), v, C, p->st,
-                       0.01f, f16_slot(p, b, F16_DY2), pa));
+                       0.01f, f16_slot(p, b, F16_DY2), pa, hs ? *hs : HeadSrc{}));
   }
   const double V = (double)nvox(v), T = 9.0 * KD;
   Src2 a1 = act_src(p, b);  // (fused: y1 and its halo as the forward left them)
@@ -1213,13 +1221,35 @@ int backward(spff_plan* p, const float* dl) {
   const int64_t V0 = nvox(p->vol[0]);
   float* hp = p->F(p->head_pk);
   const ActRows hact = act_rows(p, B[6]);
-  PROF(p, 3, 2.0 * V0 * f * p->K,
-       head_wgrad(p->F(B[6].out), dl, p->DP(p->out_w), p->DP(p->out_b), V0, f, p->K,
-                  p->F(p->wg_ws), p->st, B[6].fout ? &hact : nullptr));
-  CK(grad_ready(p, p->out_w, p->out_b + p->K));
-  PROF(p, 3, 2.0 * V0 * f * p->K,
-       head_dgrad(dl, hp + head_pack_dgrad_offset(f, p->K), p->F(p->G_out), V0, f, p->K,
-                  p->st, p->cfg.math));
+  // The head folded into dec1's tail pass (unsharded plans whose head streams): one pass
+  // over (y2, dl) gives the head's weight gradient and dec1's tail sums, dec1's IN-backward
+  // apply forms dout from dl, and G_out is first written by up1's input gradient.
+  const HeadSrc hsrc = head_src(dl, hp, f, p->K);
+  const bool fold = p->head_fold && SPFF_RED_FUSE && !p->co.on() && !p->hsh && B[6].tail() &&
+                    head_streams(f, p->K) && head_tail_bwd_ok(p->vol[0], f, hsrc) &&
+                    head_tail_bwd_fits(p->vol[0], f, p->wg_bytes);
+  if (fold) {
+    const Blk& d1 = B[6];
+    RedArgs a{};
+    a.y = p->F(d1.y2);
+    a.al = p->F(d1.al2);
+    a.de = p->F(d1.de2);
+    a.mean = p->F(d1.mean2);
+    a.rstd = p->F(d1.rstd2);
+    PROFB(p, 4, 2.0 * V0 * f * p->K, (double)V0 * (4.0 * f + 4.0 * p->K),
+          head_tail_bwd(a, p->F(d1.P), p->F(d1.Q), hsrc, p->vol[0], f, p->F(p->red_out),
+                        p->F(p->red_out4), p->F(p->wg_ws), p->wg_bytes, p->DP(p->out_w),
+                        p->DP(p->out_b), p->st));
+    CK(grad_ready(p, p->out_w, p->out_b + p->K));
+  } else {
+    PROF(p, 3, 2.0 * V0 * f * p->K,
+         head_wgrad(p->F(B[6].out), dl, p->DP(p->out_w), p->DP(p->out_b), V0, f, p->K,
+                    p->F(p->wg_ws), p->st, B[6].fout ? &hact : nullptr));
+    CK(grad_ready(p, p->out_w, p->out_b + p->K));
+    PROF(p, 3, 2.0 * V0 * f * p->K,
+         head_dgrad(dl, hp + head_pack_dgrad_offset(f, p->K), p->F(p->G_out), V0, f, p->K,
+                    p->st, p->cfg.math));
+  }
   // decoder: dec1 (B[6]) <- up1 (up[2]) <- dec2 ... ; skip grads go to dskip[l]
   for (int k = 0; k < 3; ++k) {
     const int bi = 6 - k;          // dec1, dec2, dec3
@@ -1229,7 +1259,8 @@ int backward(spff_plan* p, const float* dl) {
     const int C = d.C;             // = U.Cout = skip channels
     const int lvl = d.lvl;
     Dst2 dx{p->F(p->G_dx), p->F(p->dskip[lvl]), C, C, C};
-    CK(bwd_block(p, d, p->F(p->G_out), &dx, src2(p->F(U.out), p->F(B[lvl].out), C), bi));
+    CK(bwd_block(p, d, p->F(p->G_out), &dx, src2(p->F(U.out), p->F(B[lvl].out), C), bi, {},
+                 fold && k == 0 ? &hsrc : nullptr));
     CK(block_grads_ready(p, d));
     if (p->dbg_stop == k + 1) return SPFF_OK;
     const Blk& ub = (ui == 0) ? B[3] : B[bi - 1];  // the up-conv's input block
@@ -1435,6 +1466,7 @@ int spff_debug_set(spff_plan* p, int key, int value) {
   if (key == 1) p->keep_out = value != 0;  // store the GEMM-applied block outputs too
   if (key == 2) p->pool_fold = value != 0;  // 0: k_maxpool_bwd_add pass instead of PoolAdd
   if (key == 3) p->bst_fuse = value != 0;   // 0: conv1's IN-backward sums by a slab_reduce pass
+  if (key == 4) p->head_fold = value != 0;  // 0: head_wgrad + head_dgrad + dec1's tail reduction
   return SPFF_OK;
 }
 

@@ -1758,6 +1758,19 @@ hipError_t head_wgrad(const float* x, const float* dy, float* dw, float* db, int
   return launch_xty(x, Cin, Cin, dy, K, K, nullptr, V, K, 1, dw, db, ws, s);
 }
 
+bool head_streams(int Cin, int K) { return head_stream_ok(Cin, K); }
+HeadSrc head_src(const float* dl, const float* pk, int Cin, int K) {
+  return HeadSrc{dl, pk + head_pack_dgrad_offset(Cin, K), head_dn(Cin), K};
+}
+// (k_xty's partial layout with k1pad = Cin, npad = 32: one slab per workgroup)
+hipError_t head_wgrad_reduce(const float* part, const float* csum, float* dw, float* db, int nwg,
+                             int Cin, int K, hipStream_t s) {
+  if (Cin % 32 || K > 32) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_atb_reduce, dim3(Cin + 1), dim3(ATB_RG * 32), 0, s, part, csum, dw, db, nwg,
+                     Cin, 32, Cin, K, K, 1, Cin);
+  return hipGetLastError();
+}
+
 // ------------------------------------------------------- linear layers --
 // nn.Linear / 1x1x1 Conv3d on channel-last rows: y = x W^T + b with W [N][K]
 // (PyTorch layout), packed by head_pack(w, wf, wd, K, N) (wf = W^T, wd = W).

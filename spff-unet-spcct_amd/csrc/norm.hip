@@ -320,6 +320,278 @@ hipError_t slab_reduce(RedOp op, const RedArgs& a, Vol vol, int C, float* out, f
   return hipGetLastError();
 }
 
+// ------------------------------------- head backward + dec1 tail sums, one pass --
+// The last decoder block's output feeds only the head, so its output gradient is dout[v] =
+// dl[v] . W (13 -> 32: a linear map of a tensor 2.5x smaller).  Instead of writing it once
+// (head_dgrad) and reading it twice, its readers form it: this pass and
+// k_in_bwd_apply_head.  One workgroup streams a run of rows of one (b, d) slab, 256 at a time:
+//   stage   the dl rows into LDS (coalesced float4)
+//   dgrad   thread = row: dout[c] by k_head_dgrad_s's fmaf chain, W uniform through the
+//           scalar cache (no per-thread copy of it), into the LDS tile
+//   sums    thread = (voxel lane, channel quad) as in k_slab_reduce, its y2 quads loaded
+//           coalesced into registers: red_accum<RED_BWD_TAIL6> on (y2, dout), and out =
+//           lrelu(y2 al + de) P + Q (the head's input rows, ActRows' formula) over dout
+//   wgrad   out^T dl on the fp32 MFMA (v_mfma_f32_16x16x4_f32: 16 channels x 16 classes over
+//           4 rows, lanes 16 q .. 16 q + 15 row 4 g + q; K = 13 wastes 3 of its 16 columns
+//           where the 32 x 32 form wastes 19 of 32), wave w the row quads w, w + 4, ...;
+//           each lane also sums its dl column (db)
+// then the fixed-order reductions: the six sums as k_slab_reduce leaves them (k_slab_combine
+// follows), the MFMA tiles of the 4 waves added in wave order into the workgroup's partial
+// slab (head_wgrad_reduce follows).  No atomics; every partial is written, nothing is zeroed.
+#ifndef SPFF_HT_IT
+#define SPFF_HT_IT 8  // 256-row tiles per workgroup at most (fewer while < SPFF_HT_WG workgroups)
+#endif
+#ifndef SPFF_HT_WG
+#define SPFF_HT_WG 2048
+#endif
+typedef float ht_f32x4 __attribute__((ext_vector_type(4)));
+
+template <int C, int KM>
+__global__ __launch_bounds__(256, (C == 32 && KM == 16) ? 3 : 1) void k_head_tail_bwd(
+    RedArgs a, const float* __restrict__ P, const float* __restrict__ Q, HeadSrc hs, Vol vol,
+    float* __restrict__ ws, float* __restrict__ part, float* __restrict__ csum, int nsplit,
+    int chunk) {
+  constexpr int CP = C + 1, TPV = C / 4, VPP = 256 / TPV, NJ = TPV, NL = KM / 4;
+  constexpr int TM = C / 16, TN = KM / 16, NE = TM * TN * 4, NQ = 6;
+  static_assert(4 * NE * 64 <= 256 * CP, "the waves' MFMA tiles fit the LDS tile");
+  static_assert(4 * NQ * TPV * 4 + 256 * TN <= 256 * KM, "the final sums fit the dl tile");
+  __shared__ __align__(16) float tile[256 * CP];  // dout rows, then out rows over them
+  __shared__ __align__(16) float gt[256 * KM];    // dl rows [256][K]
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, kq = lane >> 4, l16 = lane & 15;
+  const int bd = blockIdx.y, split = blockIdx.x, b = bd / vol.D, d = bd % vol.D;
+  const int HW = vol.H * vol.W, K = hs.K, dn = hs.dn;
+  const int cq = tid % TPV, vo = tid / TPV, c = 4 * cq;
+  float pal[4], pde[4], pmu[4], prs[4], pp[4], pq[4];
+  const float one[4] = {1.f, 1.f, 1.f, 1.f}, zero[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int bc = b * C + c + j;
+    pal[j] = a.al[bc]; pde[j] = a.de[bc]; pmu[j] = a.mean[bc]; prs[j] = a.rstd[bc];
+    pp[j] = P ? P[(int64_t)bc * vol.D + d] : 1.f;
+    pq[j] = P ? Q[(int64_t)bc * vol.D + d] : 0.f;
+  }
+  float acc[NQ][4];
+#pragma unroll
+  for (int q = 0; q < NQ; ++q)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[q][j] = 0.f;
+  ht_f32x4 macc[TM][TN];
+  float cs[TN];  // this lane's dl columns 16 tn + l16 over its wave's rows 4 g + kq
+#pragma unroll
+  for (int tn = 0; tn < TN; ++tn) {
+    cs[tn] = 0.f;
+#pragma unroll
+    for (int t = 0; t < TM; ++t)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) macc[t][tn][r] = 0.f;
+  }
+  const int hb = split * chunk, he = min(HW, hb + chunk);
+  const int64_t base = (int64_t)bd * HW;
+  for (int r0 = hb; r0 < he; r0 += 256) {
+    const int nr = min(256, he - r0);
+    const int n = nr * K, n4 = n >> 2;
+    const float* gb = hs.dl + (base + r0) * K;  // 16-B aligned: HW % 4 == 0, r0 % 256 == 0
+    {
+      float4 gv[NL];
+#pragma unroll
+      for (int j = 0; j < NL; ++j) {
+        const int i = tid + j * 256;
+        gv[j] = i < n4 ? ld_s(gb + 4 * i) : make_float4(0.f, 0.f, 0.f, 0.f);
+      }
+#pragma unroll
+      for (int j = 0; j < NL; ++j) {
+        const int i = tid + j * 256;
+        if (i < n4) *reinterpret_cast<float4*>(gt + 4 * i) = gv[j];
+      }
+    }
+    for (int i = n4 * 4 + tid; i < n; i += 256) gt[i] = gb[i];
+    for (int i = n + tid; i < 256 * K; i += 256) gt[i] = 0.f;  // rows past a ragged tile's end
+    __syncthreads();
+    {  // dgrad: row tid's dout, k_head_dgrad_s's chain (a row past the end: dl = 0 -> 0)
+      float g[KM];
+#pragma unroll
+      for (int k = 0; k < KM; ++k) g[k] = k < K ? gt[tid * K + k] : 0.f;
+      float dx[C];
+#pragma unroll
+      for (int cc = 0; cc < C; ++cc) dx[cc] = 0.f;
+#pragma unroll
+      for (int k = 0; k < KM; ++k)
+        if (k < K) {
+#pragma unroll
+          for (int cc = 0; cc < C; ++cc) dx[cc] = fmaf(g[k], hs.wd[k * dn + cc], dx[cc]);
+        }
+#pragma unroll
+      for (int cc = 0; cc < C; ++cc) tile[tid * CP + cc] = dx[cc];
+    }
+    // (the y2 rows load only now: they and the dgrad registers are never live together)
+    float4 yv[NJ];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+      const int rr = vo + j * VPP;
+      yv[j] = ld_s(a.y + (base + r0 + (rr < nr ? rr : 0)) * C + c);
+    }
+    __syncthreads();
+    // sums on (y2, dout); the thread then puts out = lrelu(y2 al + de) P + Q where it read
+    // dout (its own four words of the tile)
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+      const int rr = vo + j * VPP;
+      if (rr >= nr) break;
+      const float ys[4] = {yv[j].x, yv[j].y, yv[j].z, yv[j].w};
+      float* t = tile + rr * CP + c;
+      const float gs[4] = {t[0], t[1], t[2], t[3]};
+      red_accum<RED_BWD_TAIL6, NQ>(a, ys, gs, pal, pde, one, zero, pmu, prs, acc);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const float r = ys[e] * pal[e] + pde[e];
+        t[e] = (r > 0.f ? r : a.neg * r) * pp[e] + pq[e];
+      }
+    }
+    __syncthreads();
+    // wgrad: a row past the end carries dl = 0 and a finite tile row (its dout = 0)
+    for (int g4 = wave; 4 * g4 < nr; g4 += 4) {
+      const int row = 4 * g4 + kq;
+      float bv[TN];
+#pragma unroll
+      for (int tn = 0; tn < TN; ++tn) {
+        bv[tn] = 16 * tn + l16 < K ? gt[row * K + 16 * tn + l16] : 0.f;
+        cs[tn] += bv[tn];
+      }
+#pragma unroll
+      for (int t = 0; t < TM; ++t) {
+        const float av = tile[row * CP + 16 * t + l16];
+#pragma unroll
+        for (int tn = 0; tn < TN; ++tn)
+          macc[t][tn] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv[tn], macc[t][tn], 0, 0, 0);
+      }
+    }
+    __syncthreads();  // the next tile's staging overwrites both LDS tiles
+  }
+  // the six sums: k_slab_reduce's xor-shuffle tree over the wave's voxel lanes, then the waves
+  float* red = gt;
+  float* cred = gt + 4 * NQ * TPV * 4;
+#pragma unroll
+  for (int q = 0; q < NQ; ++q)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      float v = acc[q][j];
+      for (int o = TPV; o < 64; o <<= 1) v += __shfl_xor(v, o);
+      acc[q][j] = v;
+    }
+  if (lane < TPV) {
+#pragma unroll
+    for (int q = 0; q < NQ; ++q)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) red[((wave * NQ + q) * TPV + lane) * 4 + j] = acc[q][j];
+  }
+#pragma unroll
+  for (int tn = 0; tn < TN; ++tn) cred[((wave * 4 + kq) * TN + tn) * 16 + l16] = cs[tn];
+#pragma unroll
+  for (int t = 0; t < TM; ++t)
+#pragma unroll
+    for (int tn = 0; tn < TN; ++tn)
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+        tile[(wave * NE + (t * TN + tn) * 4 + r) * 64 + lane] = macc[t][tn][r];
+  __syncthreads();
+  const int64_t wg = (int64_t)bd * nsplit + split;
+  for (int i = tid; i < NQ * TPV * 4; i += 256) {
+    const int j = i & 3, cqq = (i >> 2) % TPV, q = (i >> 2) / TPV;
+    float t = 0.f;
+    for (int w = 0; w < 4; ++w) t += red[((w * NQ + q) * TPV + cqq) * 4 + j];
+    ws[((wg * C) + 4 * cqq + j) * NQ + q] = t;
+  }
+  // (columns K .. 31 of a partial slab are never read: with KM = 16 the upper 16 stay unwritten)
+  for (int e = wave; e < NE; e += 4) {
+    const int t = e / (TN * 4), tn = (e >> 2) % TN, r = e & 3;
+    const float v = ((tile[(0 * NE + e) * 64 + lane] + tile[(1 * NE + e) * 64 + lane]) +
+                     tile[(2 * NE + e) * 64 + lane]) +
+                    tile[(3 * NE + e) * 64 + lane];
+    // register r of lane (kq, l16) holds result row (channel) 4 kq + r, column (class) l16
+    part[(wg * C + 16 * t + 4 * kq + r) * 32 + 16 * tn + l16] = v;
+  }
+  if (tid < 16 * TN) {
+    const int tn = tid >> 4, l = tid & 15;
+    float v = 0.f;
+#pragma unroll
+    for (int w = 0; w < 16; ++w) v += cred[(w * TN + tn) * 16 + l];  // (wave, kq) in order
+    csum[wg * 32 + tid] = v;
+  }
+}
+
+namespace {
+struct HtPlan {
+  int chunk, nsplit;
+  int64_t nwg;
+};
+// 256-row tiles per workgroup: as many as leave >= wgs workgroups, itmax at most
+HtPlan ht_plan(Vol vol, int wgs = SPFF_HT_WG, int itmax = SPFF_HT_IT) {
+  const int64_t HW = (int64_t)vol.H * vol.W, V = HW * vol.B * vol.D;
+  int64_t it = (V + 256 * (int64_t)wgs - 1) / (256 * (int64_t)wgs);
+  it = std::max<int64_t>(1, std::min<int64_t>(it, itmax));
+  HtPlan p;
+  p.chunk = (int)(256 * it);
+  p.nsplit = (int)((HW + p.chunk - 1) / p.chunk);
+  p.nwg = (int64_t)p.nsplit * vol.B * vol.D;
+  return p;
+}
+}  // namespace
+
+bool head_tail_bwd_ok(Vol vol, int C, const HeadSrc& hs) {
+  // a slab's first dl row 16-B aligned (the float4 staging): H W K % 4 == 0, here H W % 4 == 0
+  return (C == 32 || C == 64) && hs.K >= 1 && hs.K <= 32 && hs.dn >= C && hs.dl && hs.wd &&
+         (vol.H * vol.W) % 4 == 0 && vol.B * vol.D <= 65535 &&
+         !(reinterpret_cast<uintptr_t>(hs.dl) & 15);
+}
+// part: the workgroups' partials [nwg][C][32] (dW), [nwg][32] (db), [nwg][C][6] (the sums)
+static size_t ht_bytes(const HtPlan& p, int C) {
+  return (size_t)p.nwg * ((C + 1) * 32 + C * 6) * sizeof(float);
+}
+// the plan whose partials fit `bytes` of scratch: more tiles per workgroup (fewer, longer
+// workgroups) until they do; nwg = 0: none does
+static HtPlan ht_plan_fit(Vol vol, int C, size_t bytes) {
+  HtPlan p = ht_plan(vol);
+  const int HW = vol.H * vol.W;
+  while (ht_bytes(p, C) > bytes) {
+    if (p.nsplit == 1) return HtPlan{0, 0, 0};
+    p.chunk *= 2;
+    p.nsplit = (HW + p.chunk - 1) / p.chunk;
+    p.nwg = (int64_t)p.nsplit * vol.B * vol.D;
+  }
+  return p;
+}
+bool head_tail_bwd_fits(Vol vol, int C, size_t bytes) { return ht_plan_fit(vol, C, bytes).nwg > 0; }
+
+hipError_t head_tail_bwd(const RedArgs& a, const float* P, const float* Q, const HeadSrc& hs,
+                         Vol vol, int C, float* out, float* out2, float* part, size_t part_bytes,
+                         float* dw, float* db, hipStream_t s) {
+  if (!head_tail_bwd_ok(vol, C, hs) || !out || !out2 || a.pa.dp) return hipErrorInvalidValue;
+  const HtPlan p = ht_plan_fit(vol, C, part_bytes);
+  if (p.nwg < 1 || p.nwg >= (int64_t(1) << 31) / ((C + 1) * 32)) return hipErrorInvalidValue;
+  float* csum = part + p.nwg * C * 32;
+  float* ws = csum + p.nwg * 32;
+  const dim3 grid(p.nsplit, vol.B * vol.D);
+#define SPFF_HT(C_, KM_)                                                                         \
+  hipLaunchKernelGGL((k_head_tail_bwd<C_, KM_>), grid, dim3(256), 0, s, a, P, Q, hs, vol, ws, part, \
+                     csum, p.nsplit, p.chunk)
+  if (C == 32) {
+    if (hs.K <= 16) SPFF_HT(32, 16);
+    else SPFF_HT(32, 32);
+  } else {
+    if (hs.K <= 16) SPFF_HT(64, 16);
+    else SPFF_HT(64, 32);
+  }
+#undef SPFF_HT
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  const int total = vol.B * vol.D * C * 6;
+  hipLaunchKernelGGL(k_slab_combine, dim3(std::min(cdiv(total, 256), 4096)), dim3(256), 0, s, ws,
+                     out, vol, C, 6, p.nsplit, out2);
+  e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  return head_wgrad_reduce(part, csum, dw, db, (int)p.nwg, C, hs.K, s);
+}
+
 // ------------------------------------------------------------ finalizers --
 __global__ void k_in_mean(const float* __restrict__ sums, float* __restrict__ mean, Vol vol, int C) {
   const int bc = blockIdx.x * blockDim.x + threadIdx.x;
@@ -848,6 +1120,101 @@ __global__ __launch_bounds__(256) void k_in_bwd_apply(
   if (amax) block_amax(m, amax);
 }
 
+// k_in_bwd_apply with g = the HeadSrc rows, staged through LDS as k_head_dgrad_s forms them
+// (a kernel of its own: the other launches per step keep k_in_bwd_apply's code).  One
+// workgroup streams a run of rows of one (b, d) slab, 256 at a time: the y rows stay in
+// registers (thread = (voxel lane, channel quad), coalesced float4), the dl rows go to LDS,
+// thread = row forms dout[c] (W uniform through the scalar cache) into the LDS tile, and
+// each thread reads its quads of it back for dy = rstd gamma (dr - k1 - xhat k2).
+template <int C, int KM>
+__global__ __launch_bounds__(256) void k_in_bwd_apply_head(
+    const float* __restrict__ y, float* __restrict__ dy, const float* __restrict__ mean,
+    const float* __restrict__ rstd, const float* __restrict__ al, const float* __restrict__ de,
+    const float* __restrict__ gamma, const float* __restrict__ A, const float* __restrict__ Bc,
+    const float* __restrict__ k1, const float* __restrict__ k2, Vol vol, float neg,
+    unsigned* __restrict__ amax, HeadSrc hs, int chunk) {
+  constexpr int CP = C + 1, TPV = C / 4, VPP = 256 / TPV, NJ = TPV, NL = KM / 4;
+  __shared__ __align__(16) float tile[256 * CP];  // the dl rows [256][K], then dout [256][CP]
+  const int tid = threadIdx.x;
+  const int bd = blockIdx.y, b = bd / vol.D, d = bd % vol.D;
+  const int HW = vol.H * vol.W, K = hs.K, dn = hs.dn;
+  const int vo = tid / TPV, c = 4 * (tid % TPV);
+  float pal[4], pde[4], pmu[4], prs[4], psc[4], pk1[4], pk2[4], pA[4], pB[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int bc = b * C + c + j;
+    pal[j] = al[bc]; pde[j] = de[bc]; pmu[j] = mean[bc]; prs[j] = rstd[bc];
+    psc[j] = rstd[bc] * gamma[c + j]; pk1[j] = k1[bc]; pk2[j] = k2[bc];
+    pA[j] = A ? A[(int64_t)bc * vol.D + d] : 1.f;
+    pB[j] = A ? Bc[(int64_t)bc * vol.D + d] : 0.f;
+  }
+  float m = 0.f;
+  const int hb = blockIdx.x * chunk, he = min(HW, hb + chunk);
+  const int64_t base = (int64_t)bd * HW;
+  for (int r0 = hb; r0 < he; r0 += 256) {
+    const int nr = min(256, he - r0);
+    const int n = nr * K, n4 = n >> 2;
+    const float* gb = hs.dl + (base + r0) * K;  // 16-B aligned: HW % 4 == 0, r0 % 256 == 0
+    float4 gv[NL];
+#pragma unroll
+    for (int j = 0; j < NL; ++j) {
+      const int i = tid + j * 256;
+      gv[j] = i < n4 ? ld_s(gb + 4 * i) : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+#pragma unroll
+    for (int j = 0; j < NL; ++j) {
+      const int i = tid + j * 256;
+      if (i < n4) *reinterpret_cast<float4*>(tile + 4 * i) = gv[j];
+    }
+    for (int i = n4 * 4 + tid; i < n; i += 256) tile[i] = gb[i];
+    __syncthreads();
+    float g[KM];
+#pragma unroll
+    for (int k = 0; k < KM; ++k) g[k] = (k < K && tid < nr) ? tile[tid * K + k] : 0.f;
+    __syncthreads();
+    {
+      float dx[C];
+#pragma unroll
+      for (int cc = 0; cc < C; ++cc) dx[cc] = 0.f;
+#pragma unroll
+      for (int k = 0; k < KM; ++k)
+        if (k < K) {
+#pragma unroll
+          for (int cc = 0; cc < C; ++cc) dx[cc] = fmaf(g[k], hs.wd[k * dn + cc], dx[cc]);
+        }
+#pragma unroll
+      for (int cc = 0; cc < C; ++cc) tile[tid * CP + cc] = dx[cc];
+    }
+    // (the y rows load only now: they and the dgrad registers are never live together)
+    float4 yv[NJ];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+      const int rr = vo + j * VPP;
+      yv[j] = ld_s(y + (base + r0 + (rr < nr ? rr : 0)) * C + c);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+      const int rr = vo + j * VPP;
+      if (rr >= nr) break;
+      const float ys[4] = {yv[j].x, yv[j].y, yv[j].z, yv[j].w};
+      const float* t = tile + rr * CP + c;
+      float o[4];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const float r = ys[e] * pal[e] + pde[e];
+        const float dr = (t[e] * pA[e] + pB[e]) * slope(r, neg);
+        const float xh = (ys[e] - pmu[e]) * prs[e];
+        o[e] = psc[e] * (dr - pk1[e] - xh * pk2[e]);
+        m = fmaxf(m, fabsf(o[e]));
+      }
+      st_s(dy + (base + r0 + rr) * C + c, make_float4(o[0], o[1], o[2], o[3]));
+    }
+    __syncthreads();  // the next tile's dl rows overwrite the LDS tile
+  }
+  if (amax) block_amax(m, amax);
+}
+
 __global__ __launch_bounds__(256) void k_act_bound(const float* __restrict__ gamma,
                                                    const float* __restrict__ beta, int C,
                                                    float sq, unsigned* __restrict__ slot) {
@@ -880,7 +1247,28 @@ hipError_t act_bound(const float* gamma, const float* beta, int C, double N, uns
 hipError_t in_bwd_apply(const float* y, const float* g, float* dy, const float* mean,
                         const float* rstd, const float* al, const float* de, const float* gamma,
                         const float* A, const float* Bc, const float* k1, const float* k2, Vol vol,
-                        int C, hipStream_t s, float neg, unsigned* amax, PoolAdd pa) {
+                        int C, hipStream_t s, float neg, unsigned* amax, PoolAdd pa, HeadSrc hs) {
+  if (hs.dl) {
+    if ((C != 32 && C != 64) || hs.K < 1 || hs.K > 32 || hs.dn < C || pa.dp ||
+        (reinterpret_cast<uintptr_t>(hs.wd) & 15))
+      return hipErrorInvalidValue;
+    if ((vol.H * vol.W) % 4 || (reinterpret_cast<uintptr_t>(hs.dl) & 15) || vol.B * vol.D > 65535)
+      return hipErrorInvalidValue;
+    const HtPlan p = ht_plan(vol, SPFF_EW_MINWG, 16);
+    const dim3 grid(p.nsplit, vol.B * vol.D);
+#define SPFF_IBH(C_, KM_)                                                                       \
+  hipLaunchKernelGGL((k_in_bwd_apply_head<C_, KM_>), grid, dim3(256), 0, s, y, dy, mean, rstd, al, \
+                     de, gamma, A, Bc, k1, k2, vol, neg, amax, hs, p.chunk)
+    if (C == 32) {
+      if (hs.K <= 16) SPFF_IBH(32, 16);
+      else SPFF_IBH(32, 32);
+    } else {
+      if (hs.K <= 16) SPFF_IBH(64, 16);
+      else SPFF_IBH(64, 32);
+    }
+#undef SPFF_IBH
+    return hipGetLastError();
+  }
   hipLaunchKernelGGL(k_in_bwd_apply, ew_grid(vol, C), dim3(ew_bs(C)), 0, s, y, g, dy, mean, rstd, al,
                      de, gamma, A, Bc, k1, k2, vol, C, neg, amax, pa);
   return hipGetLastError();

@@ -225,6 +225,16 @@ hipError_t conv3d_wgrad_reduce(const float* part, float* dw, int nsplit, int T, 
                                int npad, int Cin, int Cout, hipStream_t s);
 
 // ---------------------------------------------------------------- gemms --
+// The last decoder block's output gradient formed where it is read: row v of it is the
+// head's input gradient dout[v][c] = sum_k dl[v][k] wd[k][c] (dl = dlogits [V][K], wd =
+// head_pack's dgrad image [K][dn]), the fmaf chain of k_head_dgrad_s (k ascending from 0),
+// so bitwise the tensor head_dgrad writes -- folded into its two readers (head_tail_bwd and
+// the IN-backward apply) instead of a [V][C] pass of its own
+struct HeadSrc {
+  const float* dl = nullptr;
+  const float* wd = nullptr;
+  int dn = 0, K = 0;
+};
 // A block output applied as a GEMM reads it (the decoders' and the bottleneck's outputs
 // feed only the up-convs and the head): row v = lrelu(y[v] al[b] + de[b], neg) P[b,d] + Q[b,d]
 // (k_act_apply's formula, bitwise), y [V][C] channel-last, al / de [B][C], PT / QT the
@@ -271,6 +281,14 @@ hipError_t head_dgrad(const float* dy, const float* wd, float* dx, int64_t V, in
 size_t head_wgrad_ws_bytes(int64_t V, int Cin, int K);
 hipError_t head_wgrad(const float* x, const float* dy, float* dw, float* db, int64_t V,
                       int Cin, int K, float* ws, hipStream_t s, const ActRows* act = nullptr);
+// the streaming head kernels take (Cin, K): Cin = 32 or 64, K <= 32, SPFF_HEAD_STREAM != 0
+bool head_streams(int Cin, int K);
+// the dlogits rows and the packed head weight (head_pack's image pk) as a HeadSrc
+HeadSrc head_src(const float* dl, const float* pk, int Cin, int K);
+// fixed-order sum of head_tail_bwd's nwg per-workgroup partials part [nwg][Cin][32] and
+// csum [nwg][32] into dw [K][Cin], db [K]
+hipError_t head_wgrad_reduce(const float* part, const float* csum, float* dw, float* db, int nwg,
+                             int Cin, int K, hipStream_t s);
 
 // nn.Linear / 1x1x1 Conv3d on channel-last rows (SwinUNETR path): W [N][K] packed by
 // head_pack(w, wf, wd, K, N) (wf = W^T for the forward, wd = W for dgrad).
@@ -334,6 +352,17 @@ struct RedArgs {
 size_t slab_reduce_ws_bytes(Vol vol, int C, int nq);
 hipError_t slab_reduce(RedOp op, const RedArgs& a, Vol vol, int C, float* out, float* ws,
                        hipStream_t s, float* out2 = nullptr);
+// The head's weight gradient, its input gradient and the last block's RED_BWD_TAIL6 in one
+// pass over (y2, dlogits): a.g is ignored (g = the HeadSrc rows, never stored); out / out2
+// as slab_reduce(RED_BWD_TAIL6) leaves them; dw [K][C], db [K] = the head's gradients over
+// the rows lrelu(y al + de) P + Q (P, Q [B][C][D], ActRows' formula).  part: part_bytes of
+// scratch for the workgroups' partials; the launch shapes itself to fit them
+// (head_tail_bwd_fits: it can).  Needs head_tail_bwd_ok too (else hipErrorInvalidValue).
+bool head_tail_bwd_ok(Vol vol, int C, const HeadSrc& hs);
+bool head_tail_bwd_fits(Vol vol, int C, size_t part_bytes);
+hipError_t head_tail_bwd(const RedArgs& a, const float* P, const float* Q, const HeadSrc& hs,
+                         Vol vol, int C, float* out, float* out2, float* part, size_t part_bytes,
+                         float* dw, float* db, hipStream_t s);
 // out[i] = {A t4[i][0] + Bc t4[i][1], A t4[i][2] + Bc t4[i][3]} for the n = B C D slabs
 hipError_t in_sums_from_tail(const float* t4, const float* A, const float* Bc, float* out,
                              int64_t n, hipStream_t s);
@@ -371,7 +400,9 @@ hipError_t in_bwd_apply(const float* y, const float* g, float* dy, const float* 
                         const float* rstd, const float* al, const float* de, const float* gamma,
                         const float* A, const float* Bc, const float* k1, const float* k2,
                         Vol vol, int C, hipStream_t s, float neg = 0.01f,
-                        unsigned* amax = nullptr, PoolAdd pa = {});
+                        unsigned* amax = nullptr, PoolAdd pa = {}, HeadSrc hs = {});
+// (hs.dl set: g is ignored and formed from the voxel's dlogits row, see HeadSrc; C = 32 or 64,
+// K <= 32, no PoolAdd)
 // (amax: also atomicMax the largest |dy| (float bits) into *amax -- an SPFF_MATH_F16X3 operand
 // scale for the convs that read dy; the caller zeroed it)
 // a bound on max |lrelu(IN(y))| from the parameters alone, into *slot (float bits): per
