@@ -511,9 +511,7 @@ hipError_t conv3d_wgrad(const Src2& x, const float* dy, int lddy, float* dw, Vol
                         int Cin, int Cout, int math, float* ws, hipStream_t s,
                         const unsigned* xmax, const unsigned* ymax) {
   CProf pr(2, 2.0 * (double)nvox(vol) * Cin * Cout * 9 * KD, s);
-  const hipError_t e = conv3d_wgrad_(x, dy, lddy, dw, vol, KD, Cin, Cout, math, ws, s, xmax, ymax);
-  pr.end(s);
-  return e;
+  return conv3d_wgrad_(x, dy, lddy, dw, vol, KD, Cin, Cout, math, ws, s, xmax, ymax);
 }
 static hipError_t conv3d_wgrad_(const Src2& x, const float* dy, int lddy, float* dw, Vol vol,
                                 int KD, int Cin, int Cout, int math, float* ws, hipStream_t s,

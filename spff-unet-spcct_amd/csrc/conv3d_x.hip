@@ -1906,8 +1906,8 @@ CProf::CProf(int cls, double flops, hipStream_t s) : st(s) {
   if (hipEventRecord(r.a, s) != hipSuccess) return;
   rec = (int)g_cprof_n++;
 }
-void CProf::end(hipStream_t s) {
-  if (rec >= 0) (void)hipEventRecord(g_cprof[rec].b, s);
+void CProf::end() {
+  if (rec >= 0) (void)hipEventRecord(g_cprof[rec].b, st);
   rec = -1;
 }
 void conv_prof_enable(bool on) {
@@ -1941,10 +1941,8 @@ hipError_t conv3d_run(const Src2& x, const void* wpack, const Dst2& y, Vol vol, 
                       int Cin_w, int Cout_w, bool dgrad, int math, hipStream_t s, float* ws,
                       float* stats, int dpart, const unsigned* wmax, const BStat* bst) {
   CProf pr(dgrad ? 1 : 0, 2.0 * (double)nvox(vol) * Cin_w * Cout_w * 9 * KD, s);
-  const hipError_t e = conv3d_run_(x, wpack, y, vol, KD, Cin_w, Cout_w, dgrad, math, s, ws,
-                                   stats, dpart, wmax, bst);
-  pr.end(s);
-  return e;
+  return conv3d_run_(x, wpack, y, vol, KD, Cin_w, Cout_w, dgrad, math, s, ws, stats, dpart, wmax,
+                     bst);
 }
 static hipError_t conv3d_run_(const Src2& x, const void* wpack, const Dst2& y, Vol vol, int KD,
                               int Cin_w, int Cout_w, bool dgrad, int math, hipStream_t s,

@@ -342,11 +342,10 @@ hipError_t loss_fwd(const float* logits, const int64_t* labels, int64_t V, int K
   hipLaunchKernelGGL(k_loss<true>, dim3(LOSS_GRID), dim3(LOSS_T), loss_lds(K), s, logits, labels,
                      V, K, ignore, cptr, dlogits, reinterpret_cast<unsigned long long*>(conf),
                      part, nullptr, class_w, clamp1);  // (bad labels: conf column K)
-  kern.end(s);
+  kern.end();  // here, not at scope end: class 4 is k_loss alone
   if ((e = hipGetLastError()) != hipSuccess) return e;
   hipLaunchKernelGGL(k_loss_final, dim3(1), dim3(LOSS_T), 0, s, part, LOSS_GRID, cptr,
                      reinterpret_cast<unsigned long long*>(conf), K, smooth, out4, clamp1);
-  whole.end(s);
   return hipGetLastError();
 }
 

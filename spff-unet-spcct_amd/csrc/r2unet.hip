@@ -35,7 +35,6 @@
 // Saved for backward per block: x1, y_k (raw conv outputs), a_k, s, o, the statistics and
 // the pool argmax bytes.
 #include "plan_ops.h"
-#include "swin_internal.h"
 
 #include <algorithm>
 #include <string>
@@ -375,7 +374,7 @@ int spff_r2u_saved_tensor(const spff_r2u* p, void* ws, const char* name, const f
 }
 
 size_t spff_r2u_dice_loss_ws_bytes(int batch, int num_classes) {
-  return r2u_dice_ws_bytes(batch, num_classes);
+  return dice_ce_ws_bytes(batch, num_classes);
 }
 
 int spff_r2u_dice_loss(const float* logits, const int64_t* labels, int batch,
@@ -385,8 +384,9 @@ int spff_r2u_dice_loss(const float* logits, const int64_t* labels, int batch,
   if (batch < 1 || vox_per_sample < 1) return plan_fail(SPFF_EINVAL, "invalid batch / vox_per_sample");
   if (num_classes < 2 || num_classes > 32)
     return plan_fail(SPFF_EINVAL, "num_classes must be 2..32 (the sigmoid branch, K = 1, is not built)");
-  PLAN_HIPCK(r2u_dice_loss(logits, labels, batch, vox_per_sample, num_classes, use_ignore,
-                       ignore_index, out4, dlogits, ws, static_cast<hipStream_t>(stream)));
+  PLAN_HIPCK(soft_dice_loss({DICE_R2U}, logits, labels, batch, vox_per_sample, num_classes,
+                        use_ignore, ignore_index, out4, dlogits, ws,
+                        static_cast<hipStream_t>(stream)));
   return SPFF_OK;
 }
 

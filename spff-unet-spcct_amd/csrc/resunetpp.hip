@@ -37,7 +37,6 @@
 // Order of every accumulation is fixed (single stream, ordered partial sums): two runs give
 // the same bits.
 #include "plan_ops.h"
-#include "swin_internal.h"
 
 #include <algorithm>
 #include <string>
@@ -1090,7 +1089,7 @@ int spff_rupp_saved_tensor(const spff_rupp* p, void* ws, const char* name, const
 }
 
 size_t spff_rupp_loss_ws_bytes(int batch, int num_classes) {
-  return rupp_loss_ws_bytes(batch, num_classes);
+  return dice_ce_ws_bytes(batch, num_classes);
 }
 
 int spff_rupp_loss(const float* logits, const int64_t* labels, int batch, int64_t vox_per_sample,
@@ -1100,9 +1099,9 @@ int spff_rupp_loss(const float* logits, const int64_t* labels, int batch, int64_
   if (!logits || !labels || !out4 || !dlogits || !ws) return plan_fail(SPFF_EINVAL, "null argument");
   if (batch < 1 || vox_per_sample < 1) return plan_fail(SPFF_EINVAL, "invalid batch / vox_per_sample");
   if (num_classes < 2 || num_classes > 32) return plan_fail(SPFF_EINVAL, "num_classes must be 2..32");
-  PLAN_HIPCK(rupp_loss(logits, labels, batch, vox_per_sample, num_classes, use_ignore, ignore_index,
-                   include_bg, ce_weight, dice_weight, out4, dlogits, ws,
-                   static_cast<hipStream_t>(stream)));
+  PLAN_HIPCK(soft_dice_loss({DICE_RUPP, include_bg ? 0 : 1, ce_weight, dice_weight}, logits, labels,
+                        batch, vox_per_sample, num_classes, use_ignore, ignore_index, out4, dlogits,
+                        ws, static_cast<hipStream_t>(stream)));
   return SPFF_OK;
 }
 

@@ -201,8 +201,8 @@ struct CProf {
   CProf(int cls, double flops, hipStream_t s);
   CProf(const CProf&) = delete;
   CProf& operator=(const CProf&) = delete;
-  ~CProf() { end(st); }
-  void end(hipStream_t s);
+  ~CProf() { end(); }
+  void end();  // records the end event now; without it the bracket closes at scope end
 };
 void conv_prof_enable(bool on);
 hipError_t conv_prof_collect(double* out, int nclass);
@@ -589,6 +589,29 @@ hipError_t count_valid(const int64_t* labels, int64_t V, int ignore, int64_t* co
                        hipStream_t s);
 hipError_t confusion_only(const float* logits, const int64_t* labels, int64_t V, int K,
                           int ignore, int64_t* conf, hipStream_t s);
+// The variants' soft-Dice (+ CE) losses (soft_dice.hip): one statistics pass and one
+// gradient pass over channel-last rows (vps voxels per sample), with the reference's formula
+// in the finaliser between them.  dlogits [V][K] = dloss/dlogits; use_ignore = 0: no voxel
+// is masked.  K <= 32; ws >= dice_ce_ws_bytes.
+//   DICE_SWIN  LitSwinUNETR_Published._loss (K >= 1): (1 - cw) per-sample soft Dice over the
+//              classes >= sc + cw CE;  out4 = [ce, loss, dice_loss, N_valid]
+//   DICE_R2U   LitR2UNet3D_Published._dice_only_loss_with_logits, multi-class branch (K >= 2):
+//              foreground-only soft Dice over the samples that have a valid foreground voxel;
+//              out4 = [dice_mean, loss, kept_samples, N_valid]; no sample kept: loss = dice = 0
+//              and dlogits = 0
+//   DICE_RUPP  LitResUNetPP3D_Published._loss (dice_ce_loss_with_metrics, K >= 2): dw soft
+//              Dice with I, P, G pooled over the whole batch (classes >= sc) + cw mean CE over
+//              the valid voxels;  out4 = [ce, loss, dice_mean, N_valid]
+enum DiceKind { DICE_SWIN, DICE_R2U, DICE_RUPP };
+struct DiceFinal {
+  DiceKind kind;
+  int sc = 1;                // first class of the Dice mean (0: background included)
+  double cw = 0.0, dw = 0.0; // CE weight; Dice weight (DICE_RUPP)
+};
+size_t dice_ce_ws_bytes(int B, int K);
+hipError_t soft_dice_loss(const DiceFinal& f, const float* logits, const int64_t* labels, int B,
+                          int64_t vps, int K, int use_ignore, int ignore, float* out4,
+                          float* dlogits, void* ws, hipStream_t s);
 
 // ------------------------------------------------ wave-staged voxel rows --
 // The loss kernels read [V][K] channel-last rows (K = 13: 52 B per voxel).  A

@@ -508,8 +508,9 @@ int spff_swin_loss(const float* logits, const int64_t* labels, int batch, int64_
                    int num_classes, int ignore_index, int include_bg, double ce_weight,
                    float* out4, float* dlogits, void* ws, void* stream) {
   if (!logits || !labels || !out4 || !dlogits || !ws) return plan_fail(SPFF_EINVAL, "null argument");
-  PLAN_HIPCK(dice_ce_loss(logits, labels, batch, vox_per_sample, num_classes, ignore_index, include_bg,
-                      ce_weight, out4, dlogits, ws, static_cast<hipStream_t>(stream)));
+  PLAN_HIPCK(soft_dice_loss({DICE_SWIN, include_bg ? 0 : 1, ce_weight}, logits, labels, batch,
+                        vox_per_sample, num_classes, 1, ignore_index, out4, dlogits, ws,
+                        static_cast<hipStream_t>(stream)));
   return SPFF_OK;
 }
 

@@ -42,29 +42,6 @@ hipError_t col_reduce(const float* part, int n, int64_t stride, int count, float
 hipError_t col_reduce_map(const float* part, int n, int64_t stride, int count, float* out,
                           int acc, int mode, int R, int nh, int hd, int C, hipStream_t s);
 
-// ------------------------------------------------------------- loss --
-size_t dice_ce_ws_bytes(int B, int K);
-// LitSwinUNETR_Published._loss: out4 = [ce, loss, dice_loss, N_valid], dlogits
-// [V][K] = dloss/dlogits (channel-last rows, vps voxels per sample)
-hipError_t dice_ce_loss(const float* logits, const int64_t* labels, int B, int64_t vps, int K,
-                        int ignore, int include_bg, double ce_weight, float* out4, float* dlogits,
-                        void* ws, hipStream_t s);
-// LitR2UNet3D_Published._dice_only_loss_with_logits, multi-class branch (r2unet.hip): the
-// foreground-only soft Dice over the samples that have a valid foreground voxel, on the same
-// statistics and gradient kernels.  out4 = [dice_mean, loss, kept_samples, N_valid]; no
-// sample kept: loss = dice = 0 and dlogits = 0.  use_ignore = 0: no voxel is masked.
-size_t r2u_dice_ws_bytes(int B, int K);
-hipError_t r2u_dice_loss(const float* logits, const int64_t* labels, int B, int64_t vps, int K,
-                         int use_ignore, int ignore, float* out4, float* dlogits, void* ws,
-                         hipStream_t s);
-// LitResUNetPP3D_Published._loss (dice_ce_loss_with_metrics, resunetpp.hip): soft Dice with
-// I, P, G pooled over the whole batch plus the mean CE over valid voxels, on the same
-// kernels.  out4 = [ce, loss, dice_mean, N_valid]; use_ignore = 0: no voxel is masked.
-size_t rupp_loss_ws_bytes(int B, int K);
-hipError_t rupp_loss(const float* logits, const int64_t* labels, int B, int64_t vps, int K,
-                     int use_ignore, int ignore, int include_bg, double ce_weight,
-                     double dice_weight, float* out4, float* dlogits, void* ws, hipStream_t s);
-
 // ---------------------------------------------------- window attention --
 // One unshifted Swin window-attention layer over a token grid [B][D][H][W]:
 // windows of ws = min(w, dim) per axis (zero-padded after norm1, so padded

@@ -325,7 +325,6 @@ int forward(spff_unetr* p, const float* x, float* logits) {
     CProf pr(PROF_RESAMPLE, 0.0, st);
     PLAN_HIPCK(resize3d_ncdhw_in(x, p->F(p->x_cl), p->ldx, B, c.in_ch, c.depth, c.height, c.width,
                              v0.D, v0.H, v0.W, st));
-    pr.end(st);
   } else {
     PLAN_HIPCK(ncdhw_to_ndhwc(x, p->F(p->x_cl), v0, c.in_ch, p->ldx, st));
   }
@@ -340,7 +339,7 @@ int forward(spff_unetr* p, const float* x, float* logits) {
   for (int i = 0; i < NBLK; ++i) PLAN_CK(block_fwd(p, p->blk[i], block_in(p, i)));
   PLAN_HIPCK(ln_fwd(p->F(p->blk[NBLK - 1].x2), Hd, Hd, p->P(p->nfw), p->P(p->nfb), p->F(p->hN), Hd,
                 p->F(p->nmu), p->F(p->nrs), T, st));
-  pv.end(st);
+  pv.end();
   PLAN_CK(prep_convs(p, p->rb, NRB));
   RB* R = p->rb;
   UpConv* U = p->up;
@@ -373,7 +372,6 @@ int forward(spff_unetr* p, const float* x, float* logits) {
   if (p->resample) {
     CProf pr(PROF_RESAMPLE, 0.0, st);
     PLAN_HIPCK(resize3d_fwd(net, logits, B, p->K, v0.D, v0.H, v0.W, c.depth, c.height, c.width, st));
-    pr.end(st);
   }
   return SPFF_OK;
 }
@@ -393,7 +391,6 @@ int backward(spff_unetr* p, const float* dl) {
     CProf pr(PROF_RESAMPLE, 0.0, st);
     PLAN_HIPCK(resize3d_bwd(dl, p->F(p->d_lg), B, p->K, v0.D, v0.H, v0.W, c.depth, c.height, c.width,
                         st));
-    pr.end(st);
     dl = p->F(p->d_lg);
   }
   PLAN_HIPCK(linear_wgrad(p->F(R[7].out), f, f, dl, p->K, p->K, p->DP(p->head.w), p->DP(p->head.b),
@@ -447,7 +444,6 @@ int backward(spff_unetr* p, const float* dl) {
   PLAN_HIPCK(linear_wgrad(p->F(p->rows), p->pe.K, p->pe.K, A, Hd, Hd, p->DP(p->pe.w), p->DP(p->pe.b),
                       T, wg, st));
   PLAN_HIPCK(col_reduce(A, B, (int64_t)n * Hd, n * Hd, p->DP(p->pos), 0, st));
-  pv.end(st);
   return SPFF_OK;
 }
 

@@ -880,39 +880,6 @@ def get_swin_plan(owner=None, tag: str = "", **kw) -> SwinPlan:
     return _get_variant_plan(SwinPlan, owner, tag, kw)
 
 
-def _variant_loss(what: str, entry: str, logits_cl: torch.Tensor, labels: torch.Tensor, K: int,
-                  *tail):
-    """A variant's loss on its HIP kernels (``entry`` and ``entry``_ws_bytes): returns
-    (out4, dlogits_cl).  ``tail``: the loss's own arguments between K and out4."""
-    require_device(logits_cl, what + " loss")
-    logits_cl = logits_cl.contiguous()
-    B = logits_cl.shape[0]
-    labels = labels.to(device=logits_cl.device, dtype=torch.int64).contiguous()
-    V = labels.numel()
-    if logits_cl.numel() != V * K or V % B:
-        raise SpffError(f"logits ({tuple(logits_cl.shape)}) / labels ({tuple(labels.shape)}) mismatch")
-    dev = logits_cl.device
-    out4 = torch.empty(4, dtype=torch.float32, device=dev)
-    dl = torch.empty_like(logits_cl)
-    L = lib()
-    ws = torch.empty(int(getattr(L, entry + "_ws_bytes")(B, K)), dtype=torch.uint8, device=dev)
-    check(getattr(L, entry)(_ptr(logits_cl), _ptr(labels), B, V // B, K, *tail, _ptr(out4),
-                            _ptr(dl), _ptr(ws), _stream(dev)), entry)
-    return out4, dl
-
-
-def _ignore_args(ignore_index: Optional[int]) -> Tuple[int, int]:
-    """(use_ignore, ignore_index); None: no voxel is masked"""
-    return int(ignore_index is not None), int(ignore_index) if ignore_index is not None else 0
-
-
-def swin_loss_forward(logits_cl: torch.Tensor, labels: torch.Tensor, K: int, ignore_index: int,
-                      include_bg: bool, ce_weight: float):
-    """LitSwinUNETR_Published._loss on the HIP kernels: returns (out4, dlogits_cl)."""
-    return _variant_loss("SwinUNETR", "spff_swin_loss", logits_cl, labels, K, int(ignore_index),
-                         int(bool(include_bg)), float(ce_weight))
-
-
 class UNETRPlan(_PlanBase):
     """One spff_unetr plan (UNETR variant) + its workspace.  The plan's input is the padded
     volume [B, Cin, depth, height, width]; when that differs from ``img`` the engine resamples
@@ -1032,15 +999,6 @@ def get_r2u_plan(owner=None, tag: str = "", **kw) -> R2UPlan:
     return _get_variant_plan(R2UPlan, owner, tag, kw)
 
 
-def r2u_dice_loss_forward(logits_cl: torch.Tensor, labels: torch.Tensor, K: int,
-                          ignore_index: Optional[int]):
-    """LitR2UNet3D_Published._dice_only_loss_with_logits (multi-class branch) on the HIP
-    kernels: returns (out4 = [dice, loss, kept_samples, N_valid], dlogits_cl).
-    ``ignore_index`` None: no voxel is masked."""
-    return _variant_loss("R2UNet3D", "spff_r2u_dice_loss", logits_cl, labels, K,
-                         *_ignore_args(ignore_index))
-
-
 class RUPPPlan(_PlanBase):
     """Engine plan of the ResUNet++ variant (include/spff.h spff_rupp_*): residual units,
     ASPP bottleneck, SE and attention-gated skips + the 1x1x1 head of
@@ -1060,17 +1018,6 @@ class RUPPPlan(_PlanBase):
 
 def get_rupp_plan(owner=None, tag: str = "", **kw) -> RUPPPlan:
     return _get_variant_plan(RUPPPlan, owner, tag, kw)
-
-
-def rupp_loss_forward(logits_cl: torch.Tensor, labels: torch.Tensor, K: int,
-                      ignore_index: Optional[int], include_bg: bool = False,
-                      ce_weight: float = 1.0, dice_weight: float = 1.0):
-    """dice_ce_loss_with_metrics (LitResUNetPP3D_Published._loss) on the HIP kernels:
-    returns (out4 = [ce, loss, dice_mean, N_valid], dlogits_cl).  Dice sums are pooled over
-    the whole batch; ``ignore_index`` None: no voxel is masked."""
-    return _variant_loss("ResUNet++", "spff_rupp_loss", logits_cl, labels, K,
-                         *_ignore_args(ignore_index), int(bool(include_bg)), float(ce_weight),
-                         float(dice_weight))
 
 
 # ------------------------------------------------------------- data path ops --
@@ -1122,24 +1069,37 @@ def loss_ws(device) -> torch.Tensor:
     return torch.empty(n, dtype=torch.uint8, device=device)
 
 
+def _loss_io(what: str, logits_cl: torch.Tensor, labels: torch.Tensor, K: int):
+    """A loss op's inputs as the kernels read them and its outputs: (contiguous logits rows,
+    int64 labels on their device, out4, dlogits_cl)."""
+    require_device(logits_cl, what)
+    logits_cl = logits_cl.contiguous()
+    labels = labels.to(device=logits_cl.device, dtype=torch.int64).contiguous()
+    if logits_cl.numel() != labels.numel() * K:
+        raise SpffError(f"logits ({tuple(logits_cl.shape)}) / labels ({tuple(labels.shape)}) mismatch")
+    out4 = torch.empty(4, dtype=torch.float32, device=logits_cl.device)
+    return logits_cl, labels, out4, torch.empty_like(logits_cl)
+
+
+def _ce_loss(what: str, entry: str, logits_cl: torch.Tensor, labels: torch.Tensor, K: int,
+             ignore_index: int, smooth: float, count_override: Optional[torch.Tensor], *mid):
+    """spff_loss / spff_loss_ex (``mid``: the latter's arguments between count_override and
+    out4): returns (out4, dlogits_cl, conf[K, K+1])."""
+    logits_cl, labels, out4, dl = _loss_io(what, logits_cl, labels, K)
+    dev = logits_cl.device
+    conf = torch.empty(K * (K + 1), dtype=torch.int64, device=dev)
+    ws = loss_ws(dev)
+    check(getattr(lib(), entry)(_ptr(logits_cl), _ptr(labels), labels.numel(), K,
+                                int(ignore_index), float(smooth), _ptr(count_override), *mid,
+                                _ptr(out4), _ptr(dl), _ptr(conf), _ptr(ws), _stream(dev)), entry)
+    return out4, dl, conf.view(K, K + 1)
+
+
 def ce_dice_forward(logits_cl: torch.Tensor, labels: torch.Tensor, K: int, ignore_index: int,
                     smooth: float, count_override: Optional[torch.Tensor] = None):
     """Returns (out4, dlogits_cl, conf[K, K+1])."""
-    require_device(logits_cl, "ce_plus_macro_dice_loss")
-    logits_cl = logits_cl.contiguous()
-    labels = labels.to(device=logits_cl.device, dtype=torch.int64).contiguous()
-    V = labels.numel()
-    if logits_cl.numel() != V * K:
-        raise SpffError(f"logits ({tuple(logits_cl.shape)}) / labels ({tuple(labels.shape)}) mismatch")
-    dev = logits_cl.device
-    out4 = torch.empty(4, dtype=torch.float32, device=dev)
-    dl = torch.empty_like(logits_cl)
-    conf = torch.empty(K * (K + 1), dtype=torch.int64, device=dev)
-    ws = loss_ws(dev)
-    check(lib().spff_loss(_ptr(logits_cl), _ptr(labels), V, K, int(ignore_index), float(smooth),
-                          _ptr(count_override), _ptr(out4), _ptr(dl), _ptr(conf), _ptr(ws),
-                          _stream(dev)), "spff_loss")
-    return out4, dl, conf.view(K, K + 1)
+    return _ce_loss("ce_plus_macro_dice_loss", "spff_loss", logits_cl, labels, K, ignore_index,
+                    smooth, count_override)
 
 
 def weighted_ce_forward(logits_cl: torch.Tensor, labels: torch.Tensor, K: int, ignore_index: int,
@@ -1147,26 +1107,60 @@ def weighted_ce_forward(logits_cl: torch.Tensor, labels: torch.Tensor, K: int, i
                         count_override: Optional[torch.Tensor] = None):
     """The 3DUNet wrapper's _weighted_softmax_ce (models.py:779-799):
     sum_v w[y_v] nll_v / max(N_valid, 1).  Returns (out4, dlogits_cl, conf)."""
-    require_device(logits_cl, "weighted softmax CE")
-    logits_cl = logits_cl.contiguous()
-    labels = labels.to(device=logits_cl.device, dtype=torch.int64).contiguous()
-    V = labels.numel()
-    if logits_cl.numel() != V * K:
-        raise SpffError(f"logits ({tuple(logits_cl.shape)}) / labels ({tuple(labels.shape)}) mismatch")
-    dev = logits_cl.device
     cw = None
     if class_weights is not None:
-        cw = class_weights.to(device=dev, dtype=torch.float32).contiguous()
+        cw = class_weights.to(device=logits_cl.device, dtype=torch.float32).contiguous()
         if cw.numel() != K:
             raise SpffError(f"class_weights has {cw.numel()} entries, expected {K}")
-    out4 = torch.empty(4, dtype=torch.float32, device=dev)
-    dl = torch.empty_like(logits_cl)
-    conf = torch.empty(K * (K + 1), dtype=torch.int64, device=dev)
-    ws = loss_ws(dev)
-    check(lib().spff_loss_ex(_ptr(logits_cl), _ptr(labels), V, K, int(ignore_index), 1e-6,
-                             _ptr(count_override), _ptr(cw), 1, _ptr(out4), _ptr(dl), _ptr(conf),
-                             _ptr(ws), _stream(dev)), "spff_loss_ex")
-    return out4, dl, conf.view(K, K + 1)
+    return _ce_loss("weighted softmax CE", "spff_loss_ex", logits_cl, labels, K, ignore_index,
+                    1e-6, count_override, _ptr(cw), 1)
+
+
+def _variant_loss(what: str, entry: str, logits_cl: torch.Tensor, labels: torch.Tensor, K: int,
+                  *tail):
+    """A variant's loss on the soft-Dice kernels (``entry`` and ``entry``_ws_bytes): returns
+    (out4, dlogits_cl).  ``tail``: the loss's own arguments between K and out4."""
+    logits_cl, labels, out4, dl = _loss_io(what + " loss", logits_cl, labels, K)
+    B, V, dev = logits_cl.shape[0], labels.numel(), logits_cl.device
+    if V % B:
+        raise SpffError(f"logits ({tuple(logits_cl.shape)}) / labels ({tuple(labels.shape)}) mismatch")
+    L = lib()
+    ws = torch.empty(int(getattr(L, entry + "_ws_bytes")(B, K)), dtype=torch.uint8, device=dev)
+    check(getattr(L, entry)(_ptr(logits_cl), _ptr(labels), B, V // B, K, *tail, _ptr(out4),
+                            _ptr(dl), _ptr(ws), _stream(dev)), entry)
+    return out4, dl
+
+
+def _ignore_args(ignore_index: Optional[int]) -> Tuple[int, int]:
+    """(use_ignore, ignore_index); None: no voxel is masked"""
+    return int(ignore_index is not None), int(ignore_index) if ignore_index is not None else 0
+
+
+def swin_loss_forward(logits_cl: torch.Tensor, labels: torch.Tensor, K: int, ignore_index: int,
+                      include_bg: bool, ce_weight: float):
+    """LitSwinUNETR_Published._loss on the HIP kernels: returns (out4, dlogits_cl)."""
+    return _variant_loss("SwinUNETR", "spff_swin_loss", logits_cl, labels, K, int(ignore_index),
+                         int(bool(include_bg)), float(ce_weight))
+
+
+def r2u_dice_loss_forward(logits_cl: torch.Tensor, labels: torch.Tensor, K: int,
+                          ignore_index: Optional[int]):
+    """LitR2UNet3D_Published._dice_only_loss_with_logits (multi-class branch) on the HIP
+    kernels: returns (out4 = [dice, loss, kept_samples, N_valid], dlogits_cl).
+    ``ignore_index`` None: no voxel is masked."""
+    return _variant_loss("R2UNet3D", "spff_r2u_dice_loss", logits_cl, labels, K,
+                         *_ignore_args(ignore_index))
+
+
+def rupp_loss_forward(logits_cl: torch.Tensor, labels: torch.Tensor, K: int,
+                      ignore_index: Optional[int], include_bg: bool = False,
+                      ce_weight: float = 1.0, dice_weight: float = 1.0):
+    """dice_ce_loss_with_metrics (LitResUNetPP3D_Published._loss) on the HIP kernels:
+    returns (out4 = [ce, loss, dice_mean, N_valid], dlogits_cl).  Dice sums are pooled over
+    the whole batch; ``ignore_index`` None: no voxel is masked."""
+    return _variant_loss("ResUNet++", "spff_rupp_loss", logits_cl, labels, K,
+                         *_ignore_args(ignore_index), int(bool(include_bg)), float(ce_weight),
+                         float(dice_weight))
 
 
 def confusion(logits_cl: torch.Tensor, labels: torch.Tensor, K: int,

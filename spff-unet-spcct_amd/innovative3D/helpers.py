@@ -41,34 +41,49 @@ def _logits_cl(logits: torch.Tensor) -> torch.Tensor:
     return logits.permute(0, 2, 3, 4, 1).contiguous()
 
 
-class _CEDice(torch.autograd.Function):
-    """Outputs (loss, conf, ce): loss = ce + 0.5 * hard-Dice term (out4[1]); conf
-    [K, K+1] and the CE share ce (out4[0]) carry no gradient."""
+class _DeviceLoss(torch.autograd.Function):
+    """Base of the losses whose HIP forward pass also writes dloss/dlogits.  A subclass
+    gives ``WHAT`` (its name in messages) and ``run(logits_cl, labels, *args)`` ->
+    (dlogits_cl, loss, *extras): the call into the engine on channel-last logits.  apply
+    takes (logits [B,K,D,H,W] or [B,K,H,W], labels, *args) and returns loss, or
+    (loss, *extras) with the extras carrying no gradient."""
 
-    @staticmethod
-    def forward(ctx, logits, labels, K, ignore_index, smooth, count_override):
-        lcl = _logits_cl(logits)
-        out4, dl, conf = E.ce_dice_forward(lcl, labels, K, ignore_index, smooth, count_override)
-        ctx.dl = dl
-        ctx.ndim = logits.ndim
-        ce = out4[0]
-        ctx.mark_non_differentiable(conf, ce)
-        return out4[1], conf, ce
+    WHAT = "device loss"
 
-    @staticmethod
-    def backward(ctx, g, _gconf=None, _gce=None):
+    @classmethod
+    def forward(cls, ctx, logits, labels, *args):
+        dl, loss, *extras = cls.run(_logits_cl(logits), labels, *args)
+        ctx.dl, ctx.ndim, ctx.nin = dl, logits.ndim, 2 + len(args)
+        ctx.mark_non_differentiable(*extras)
+        return (loss, *extras) if extras else loss
+
+    @classmethod
+    def backward(cls, ctx, g, *_gextras):
         # scaled in place (no second logits-sized buffer: 7 GB at 5 x 512^3) and handed
         # out exactly once; a retained-graph second backward would see a scaled tensor
         dl = ctx.dl
         if dl is None:
-            raise RuntimeError("ce_plus_macro_dice_loss: backward ran twice through the same "
-                               "graph (retain_graph); recompute the loss for a second backward")
+            raise RuntimeError(f"{cls.WHAT}: backward ran twice through the same graph "
+                               "(retain_graph); recompute the loss for a second backward")
         ctx.dl = None
         E.scale_(dl, g.reshape(1))
         d = dl.permute(0, 4, 1, 2, 3)
         if ctx.ndim == 4:
             d = d.squeeze(2)
-        return d, None, None, None, None, None
+        return (d,) + (None,) * (ctx.nin - 1)
+
+
+class _CEDice(_DeviceLoss):
+    """(logits, labels, K, ignore_index, smooth, count_override) -> (loss, conf, ce):
+    loss = ce + 0.5 * hard-Dice term (out4[1]); conf [K, K+1] and the CE share ce (out4[0])
+    carry no gradient."""
+
+    WHAT = "ce_plus_macro_dice_loss"
+
+    @staticmethod
+    def run(lcl, labels, *args):
+        out4, dl, conf = E.ce_dice_forward(lcl, labels, *args)
+        return dl, out4[1], conf, out4[0]
 
 
 def ce_dice_parts(logits, labels, num_classes, ignore_index=255, smooth=1e-6,

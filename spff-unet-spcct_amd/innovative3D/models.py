@@ -30,9 +30,9 @@ import torch.nn.functional as F
 
 from . import _engine as E
 from .config import BEST_LR, IGNORE_INDEX, NUM_CLASSES, NUM_FRAMES  # noqa: F401
-from .helpers import (LOSS_REGISTRY, ce_plus_macro_dice_loss, ce_dice_with_confusion,  # noqa: F401
-                      fast_simple_metrics, metrics_from_confusion, per_class_metrics_2d,
-                      per_class_metrics_3d, ranking_metrics)
+from .helpers import (LOSS_REGISTRY, _DeviceLoss, ce_plus_macro_dice_loss,  # noqa: F401
+                      ce_dice_with_confusion, fast_simple_metrics, metrics_from_confusion,
+                      per_class_metrics_2d, per_class_metrics_3d, ranking_metrics)
 from .lightning_compat import pl
 
 # ----------------------------------------------------------------- utilities --
@@ -40,6 +40,11 @@ from .lightning_compat import pl
 
 def _pick_first_if_seq(x):
     return x[0] if isinstance(x, (list, tuple)) else x
+
+
+def _image_label(batch):
+    """(image, label) of an (x, y) pair or an {"image", "label"} dict batch"""
+    return batch if isinstance(batch, (list, tuple)) else (batch["image"], batch["label"])
 
 
 def _canonicalize_targets_2d(lbls):
@@ -435,7 +440,7 @@ class BaseLitModel(pl.LightningModule):
         return ce_plus_macro_dice_loss(logits, labels, self.hparams.num_classes, ignore_index=IGNORE_INDEX)
 
     def _shared_step(self, batch, prefix):
-        imgs, lbls = batch if isinstance(batch, (list, tuple)) else (batch["image"], batch["label"])
+        imgs, lbls = _image_label(batch)
         imgs = _pick_first_if_seq(imgs)
         lbls = _pick_first_if_seq(lbls)
         if not self.is_3d:
@@ -647,7 +652,7 @@ class Cicek3DUNet(_FlatParamMixin, nn.Module):
         bufs = self._ensure_bufs(plan, x.device)
         plan.workspace(x.device)
         # data parallelism with synchronised BatchNorm: ``self.sync_bn`` = a collective with
-        # allreduce(t) / world over the group (innovative3D.distributed.SyncBNGroup); None:
+        # allreduce(t) / world over the group (distributed.sync_batchnorm's TorchDepthColl); None:
         # per-replica statistics (DDP without SyncBN, the reference's Lightning default)
         sync = getattr(self, "sync_bn", None)
         if getattr(plan, "_sync_impl", None) is not sync:
@@ -664,20 +669,15 @@ class Cicek3DUNet(_FlatParamMixin, nn.Module):
         return self.run(x, 0)
 
 
-class _WeightedCE(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, logits, labels, K, ignore_index, class_weights):
-        lcl = logits.permute(0, 2, 3, 4, 1).contiguous()
-        out4, dl, conf = E.weighted_ce_forward(lcl, labels, K, ignore_index, class_weights)
-        ctx.dl = dl
-        ctx.mark_non_differentiable(conf)
-        return out4[0], conf
+class _WeightedCE(_DeviceLoss):
+    """(logits, labels, K, ignore_index, class_weights) -> (loss, conf [K, K+1])"""
+
+    WHAT = "weighted softmax CE"
 
     @staticmethod
-    def backward(ctx, g, _gconf=None):
-        dl = ctx.dl
-        E.scale_(dl, g.reshape(1))
-        return dl.permute(0, 4, 1, 2, 3), None, None, None, None
+    def run(lcl, labels, *args):
+        out4, dl, conf = E.weighted_ce_forward(lcl, labels, *args)
+        return dl, out4[0], conf
 
 
 class LitCicek3DUNet_DepthAdapter_Published(pl.LightningModule):
@@ -936,19 +936,15 @@ class SwinUNETR_Published(nn.Module):
         return self.model(x)
 
 
-class _SwinLoss(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, logits, labels, K, ignore_index, include_bg, ce_weight):
-        lcl = logits.permute(0, 2, 3, 4, 1).contiguous()
-        out4, dl = E.swin_loss_forward(lcl, labels, K, ignore_index, include_bg, ce_weight)
-        ctx.dl = dl
-        return out4[1]
+class _SwinLoss(_DeviceLoss):
+    """(logits, labels, K, ignore_index, include_bg, ce_weight) -> loss"""
+
+    WHAT = "SwinUNETR loss"
 
     @staticmethod
-    def backward(ctx, g):
-        dl = ctx.dl
-        E.scale_(dl, g.reshape(1))
-        return dl.permute(0, 4, 1, 2, 3), None, None, None, None, None
+    def run(lcl, labels, *args):
+        out4, dl = E.swin_loss_forward(lcl, labels, *args)
+        return dl, out4[1]
 
 
 class _DiceCEWarmupLit(pl.LightningModule):
@@ -989,7 +985,7 @@ class _DiceCEWarmupLit(pl.LightningModule):
         self._iters_done += 1
 
     def _step(self, batch, stage):
-        imgs, lbls = batch if isinstance(batch, (list, tuple)) else (batch["image"], batch["label"])
+        imgs, lbls = _image_label(batch)
         logits = self(imgs)
         tgt = _canonicalize_targets_3d(lbls).to(logits.device)
         loss = self._loss(logits, tgt)
@@ -1282,25 +1278,55 @@ class R2UNet3D_backbone(nn.Module):
                                   "backbone and head together (LitR2UNet3D_Published.forward)")
 
 
-class _R2UDiceLoss(torch.autograd.Function):
-    """(loss, dice) of the foreground-only soft Dice; dice carries no gradient."""
+class _R2UDiceLoss(_DeviceLoss):
+    """(logits, labels, K, ignore_index) -> (loss, out4 = [dice, loss, kept, N_valid]) of the
+    foreground-only soft Dice; only the loss carries a gradient."""
+
+    WHAT = "R2UNet3D loss"
 
     @staticmethod
-    def forward(ctx, logits, labels, K, ignore_index):
-        lcl = logits.permute(0, 2, 3, 4, 1).contiguous()
-        out4, dl = E.r2u_dice_loss_forward(lcl, labels, K, ignore_index)
-        ctx.dl = dl
-        ctx.mark_non_differentiable(out4)
-        return out4[1].clone(), out4
-
-    @staticmethod
-    def backward(ctx, g, _g4=None):
-        dl = ctx.dl
-        E.scale_(dl, g.reshape(1))
-        return dl.permute(0, 4, 1, 2, 3), None, None, None
+    def run(lcl, labels, *args):
+        out4, dl = E.r2u_dice_loss_forward(lcl, labels, *args)
+        return dl, out4[1].clone(), out4
 
 
-class LitR2UNet3D_Published(_FlatParamMixin, pl.LightningModule):
+class _PadCropPlanLit(_FlatParamMixin, pl.LightningModule):
+    """What LitR2UNet3D_Published and LitResUNetPP3D_Published share: replicate-pad D, H, W
+    to multiples of ``hparams.pad_multiple`` -> ``backbone`` and ``head`` as one engine plan
+    -> centre crop; the step methods and Adam.  Subclasses build backbone and head and give
+    ``_get_plan(**kw)`` (their E.get_*_plan with their own keywords added) and ``_step``."""
+
+    def _plan(self, x):
+        B, C, D, H, W = x.shape
+        if C != self.backbone.in_channels:
+            raise ValueError(f"expected {self.backbone.in_channels} input channels, got {C}")
+        return self._get_plan(batch=B, in_ch=C, depth=D, height=H, width=W,
+                              num_classes=int(self.hparams.num_classes), device=x.device,
+                              math=getattr(self, "math", None), owner=self)
+
+    def forward(self, x):
+        x = _pick_first_if_seq(x)
+        E.require_device(x, f"{type(self).__name__}.forward")
+        if x.ndim == 4:
+            x = x.unsqueeze(1)
+        m = int(self.hparams.pad_multiple)
+        if m % 16:
+            raise NotImplementedError("pad_multiple must be a multiple of 16 (four poolings)")
+        x_pad, orig = _pad_to_mult_3d(x.float(), m)
+        return _center_crop_3d(self._run_plan(self._plan(x_pad), x_pad), orig)
+
+    def training_step(self, batch, _):
+        return self._step(batch, "train")
+
+    def validation_step(self, batch, _):
+        return self._step(batch, "val")
+
+    def configure_optimizers(self):
+        return torch.optim.Adam(self.parameters(), lr=self.hparams.lr,
+                                weight_decay=self.hparams.weight_decay)
+
+
+class LitR2UNet3D_Published(_PadCropPlanLit):
     """Registry "R2UNet3D": replicate-pad D, H, W to multiples of ``pad_multiple`` ->
     R2UNet3D_backbone -> 1x1x1 head -> centre crop (padding and cropping are torch
     plumbing, backbone and head one engine plan); foreground-only soft-Dice loss over the
@@ -1324,25 +1350,8 @@ class LitR2UNet3D_Published(_FlatParamMixin, pl.LightningModule):
         self.head = nn.Conv3d(self.backbone.out_ch, num_classes, 1)
         self._flat = None
 
-    def _plan(self, x):
-        B, C, D, H, W = x.shape
-        bb = self.backbone
-        if C != bb.in_channels:
-            raise ValueError(f"expected {bb.in_channels} input channels, got {C}")
-        return E.get_r2u_plan(batch=B, in_ch=C, depth=D, height=H, width=W,
-                              num_classes=int(self.hparams.num_classes), base=bb.base, t=bb.t,
-                              device=x.device, math=getattr(self, "math", None), owner=self)
-
-    def forward(self, x):
-        x = _pick_first_if_seq(x)
-        E.require_device(x, "LitR2UNet3D_Published.forward")
-        if x.ndim == 4:
-            x = x.unsqueeze(1)
-        m = int(self.hparams.pad_multiple)
-        if m % 16:
-            raise NotImplementedError("pad_multiple must be a multiple of 16 (four poolings)")
-        x_pad, orig = _pad_to_mult_3d(x.float(), m)
-        return _center_crop_3d(self._run_plan(self._plan(x_pad), x_pad), orig)
+    def _get_plan(self, **kw):
+        return E.get_r2u_plan(base=self.backbone.base, t=self.backbone.t, **kw)
 
     @staticmethod
     def _dice_only_loss_with_logits(logits, y, ignore_index=None, eps=1e-6):
@@ -1359,7 +1368,7 @@ class LitR2UNet3D_Published(_FlatParamMixin, pl.LightningModule):
         return loss, out4[0]
 
     def _step(self, batch, stage):
-        x, y = batch if isinstance(batch, (list, tuple)) else (batch["image"], batch["label"])
+        x, y = _image_label(batch)
         logits = self(x)
         y = torch.as_tensor(y).to(logits.device)
         loss, dice = self._dice_only_loss_with_logits(logits, y,
@@ -1367,16 +1376,6 @@ class LitR2UNet3D_Published(_FlatParamMixin, pl.LightningModule):
         self.log(f"{stage}_loss", loss, on_epoch=True, prog_bar=True, sync_dist=True)
         self.log(f"{stage}_macro_dice", dice, on_epoch=True, prog_bar=True, sync_dist=True)
         return loss
-
-    def training_step(self, batch, _):
-        return self._step(batch, "train")
-
-    def validation_step(self, batch, _):
-        return self._step(batch, "val")
-
-    def configure_optimizers(self):
-        return torch.optim.Adam(self.parameters(), lr=self.hparams.lr,
-                                weight_decay=self.hparams.weight_decay)
 
 
 # ============================================================================
@@ -1475,26 +1474,19 @@ class ResUNetPP3D_backbone(nn.Module):
                                   "(LitResUNetPP3D_Published.forward)")
 
 
-class _RUPPLoss(torch.autograd.Function):
-    """(loss, out4 = [ce, loss, dice_mean, N_valid]); only the loss carries a gradient."""
+class _RUPPLoss(_DeviceLoss):
+    """(logits, labels, K, ignore_index, include_bg, ce_weight, dice_weight) ->
+    (loss, out4 = [ce, loss, dice_mean, N_valid]); only the loss carries a gradient."""
+
+    WHAT = "ResUNet++ loss"
 
     @staticmethod
-    def forward(ctx, logits, labels, K, ignore_index, include_bg, ce_weight, dice_weight):
-        lcl = logits.permute(0, 2, 3, 4, 1).contiguous()
-        out4, dl = E.rupp_loss_forward(lcl, labels, K, ignore_index, include_bg, ce_weight,
-                                       dice_weight)
-        ctx.dl = dl
-        ctx.mark_non_differentiable(out4)
-        return out4[1].clone(), out4
-
-    @staticmethod
-    def backward(ctx, g, _g4=None):
-        dl = ctx.dl
-        E.scale_(dl, g.reshape(1))
-        return dl.permute(0, 4, 1, 2, 3), None, None, None, None, None, None
+    def run(lcl, labels, *args):
+        out4, dl = E.rupp_loss_forward(lcl, labels, *args)
+        return dl, out4[1].clone(), out4
 
 
-class LitResUNetPP3D_Published(_FlatParamMixin, pl.LightningModule):
+class LitResUNetPP3D_Published(_PadCropPlanLit):
     """Registry "ResUNet++": replicate-pad D, H, W to multiples of ``pad_multiple`` ->
     ResUNetPP3D_backbone -> 1x1x1 head -> centre crop (padding and cropping are torch
     plumbing, backbone and head one engine plan); batch-pooled soft Dice + CE on the HIP loss
@@ -1521,22 +1513,8 @@ class LitResUNetPP3D_Published(_FlatParamMixin, pl.LightningModule):
         self.head = nn.Conv3d(self.backbone.out_ch, num_classes, 1)
         self._flat = None
 
-    def _plan(self, x):
-        B, C, D, H, W = x.shape
-        bb = self.backbone
-        if C != bb.in_channels:
-            raise ValueError(f"expected {bb.in_channels} input channels, got {C}")
-        return E.get_rupp_plan(batch=B, in_ch=C, depth=D, height=H, width=W,
-                               num_classes=int(self.hparams.num_classes), base=bb.base,
-                               device=x.device, math=getattr(self, "math", None), owner=self)
-
-    def forward(self, x):
-        x = _pick_first_if_seq(x)
-        E.require_device(x, "LitResUNetPP3D_Published.forward")
-        if x.ndim == 4:
-            x = x.unsqueeze(1)
-        x_pad, orig = _pad_to_mult_3d(x.float(), int(self.hparams.pad_multiple))
-        return _center_crop_3d(self._run_plan(self._plan(x_pad), x_pad), orig)
+    def _get_plan(self, **kw):
+        return E.get_rupp_plan(base=self.backbone.base, **kw)
 
     def _loss(self, logits, y):
         """dice_ce_loss_with_metrics: (loss, macro_dice, ce); Dice sums pooled over the batch."""
@@ -1550,20 +1528,10 @@ class LitResUNetPP3D_Published(_FlatParamMixin, pl.LightningModule):
         return loss, out4[2], out4[0]
 
     def _step(self, batch, stage):
-        x, y = batch if isinstance(batch, (list, tuple)) else (batch["image"], batch["label"])
+        x, y = _image_label(batch)
         logits = self(x)
         y = torch.as_tensor(y).to(logits.device)
         loss, macro_dice, _ = self._loss(logits, y)
         self.log(f"{stage}_loss", loss, on_epoch=True, prog_bar=True, sync_dist=True)
         self.log(f"{stage}_macro_dice", macro_dice, on_epoch=True, prog_bar=True, sync_dist=True)
         return loss
-
-    def training_step(self, batch, _):
-        return self._step(batch, "train")
-
-    def validation_step(self, batch, _):
-        return self._step(batch, "val")
-
-    def configure_optimizers(self):
-        return torch.optim.Adam(self.parameters(), lr=self.hparams.lr,
-                                weight_decay=self.hparams.weight_decay)

@@ -9,6 +9,8 @@ gradient within max(1e-3, 16 x the fp32 oracle's error) of max|g| per tensor,
 against a kink-consistent oracle: the residual blocks' LeakyReLUs take the
 engine's own sign pattern (its saved a1 / out tensors), since an input within
 fp32 rounding of the kink may legitimately take either slope (1 vs 0.01)."""
+import math
+
 import numpy as np
 import pytest
 import torch
@@ -105,6 +107,57 @@ def engine_act_masks(m, xshape):
             t = t.view(B, D >> lvl, H >> lvl, W >> lvl, C).permute(0, 4, 1, 2, 3)
             out[f"{name}.{act}"] = (t > 0).contiguous()
     return out
+
+
+# (K, B, (D, H, W), fraction of voxels at 255, include_bg, ce_weight, classes drawn)
+LOSS_CASES = {
+    "a": (13, 2, (3, 5, 7), 0.1, False, 0.5, 13),  # the registry setting; a partial last group
+    "b": (3, 2, (2, 8, 9), 0.0, True, 0.3, 3),     # 64 % K != 0: idle column lanes; none ignored
+    "c": (32, 1, (1, 9, 9), 0.1, False, 0.5, 32),  # the largest K: two row sets per wave
+    "d": (5, 2, (4, 4, 5), 0.1, True, 0.5, 3),     # classes 3, 4 in no label; a 16-voxel tail
+}
+
+
+def loss_case(case):
+    """(logits [B, K, D, H, W] of scale 3, labels, K, include_bg, ce_weight) on the CPU"""
+    K, B, dhw, p_ign, include_bg, w, kdraw = LOSS_CASES[case]
+    g = torch.Generator().manual_seed(11 + ord(case))
+    lg = 3.0 * torch.randn(B, K, *dhw, generator=g)
+    y = torch.randint(0, kdraw, (B, *dhw), generator=g)
+    y[torch.rand(B, *dhw, generator=g) < p_ign] = 255
+    assert (y != 255).any() and bool((y == 255).any()) == (p_ign > 0)
+    return lg, y, K, include_bg, w
+
+
+@pytest.mark.parametrize("case", sorted(LOSS_CASES))
+def test_swin_loss_kernel(case):
+    """The soft-Dice + CE loss kernels alone (M._SwinLoss forward + backward) against
+    oracle.swin_oracle.lit_loss in fp64: loss within 1e-5 relative, dlogits within
+    max(8 x the fp32 oracle's own error, (3K + 8) 2^-24) of max|dlogits| (one fp32 rounding
+    per exp, sum, divide and the K-term inner product), as test_r2u_dice_loss_kernel."""
+    lg, y, K, include_bg, w = loss_case(case)
+    cfg = S.SwinCfg(num_classes=K, ce_weight=w, include_bg_in_dice=include_bg, ignore_index=255)
+    ref = {}
+    for dt in (torch.float64, torch.float32):
+        t = lg.to(dt, copy=True).requires_grad_(True)
+        loss = S.lit_loss(t, y, cfg)
+        loss.backward()
+        ref[dt] = (float(loss.detach()), t.grad.double().numpy())
+    r_loss, r_dl = ref[torch.float64]
+    x = lg.to(DEV).requires_grad_(True)
+    loss = M._SwinLoss.apply(x, y.to(DEV), K, 255, include_bg, w)
+    loss.backward()
+    torch.cuda.synchronize()
+    dl = x.grad.double().cpu().numpy()
+    scale = float(np.abs(r_dl).max())
+    e32 = float(np.abs(ref[torch.float32][1] - r_dl).max()) / scale
+    e_gpu = float(np.abs(dl - r_dl).max()) / scale
+    tol = max(8 * e32, (3 * K + 8) * 2.0 ** -24)
+    loss = float(loss.detach())
+    print(f"case {case}: loss {loss:.8f} vs {r_loss:.8f}  dlogits gpu {e_gpu:.2e} "
+          f"fp32-oracle {e32:.2e} tol {tol:.2e}")
+    assert math.isclose(loss, r_loss, rel_tol=1e-5)
+    assert float(np.abs(dl - r_dl).max()) <= tol * scale
 
 
 def test_swin_registry_forward_pads_to_32():
