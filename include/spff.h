@@ -251,6 +251,10 @@ int spff_conv3d_wgrad(const float* x, int ldx, const float* dy, float* dw, int B
 int spff_conv3d_wgrad_ex(const float* x, int ldx, const float* dy, float* dw, int B, int D,
                          int H, int W, int cin, int cout, int ksd, int math, void* ws,
                          void* stream);
+/* the same with dy's channel stride lddy >= cout (a multiple of 4), so cout need not be one */
+int spff_conv3d_wgrad_ld(const float* x, int ldx, const float* dy, int lddy, float* dw, int B,
+                         int D, int H, int W, int cin, int cout, int ksd, int math, void* ws,
+                         void* stream);
 /* Op-level ConvTranspose3d(cin -> cout, kernel = stride = (1,2,2)) + bias (reference
  * models.py:668-672, the decoder up-convolutions) on channel-last tensors: x [B][D][H][W][cin]
  * low resolution, y [B][D][2H][2W][cout]; weight W[cin][cout][1][2][2], bias [cout].

@@ -393,49 +393,125 @@ __global__ __launch_bounds__(256, 2) void k_conv3d_wgrad_x16(
   // stages its other KD - 1 planes synchronously.
   float4 hreg[NP], yreg[NY];
   float4 xal = make_float4(1.f, 1.f, 1.f, 1.f), xde = make_float4(0.f, 0.f, 0.f, 0.f);
-  struct TileXY { int d0, b, h0, w0; };
-  auto tile_xy = [&](int tile) {
-    TileXY r;
-    int t = tile;
-    r.d0 = t % D; t /= D;
-    const int twi = t % tilesW; t /= tilesW;
-    const int thi = t % tilesH;
-    r.b = t / tilesH;
-    r.h0 = thi * WX_TH;
-    r.w0 = twi * WX_TW;
-    return r;
+  const int tbeg = split * tps;
+  const int tend = min(ntiles, tbeg + tps);
+  // The tile the register pipeline fetches, walked incrementally: decoded once, then d0 + 1
+  // per tile and a roll-over to the next (b, h, w) column by compares and adds (uniform).
+  int wb, wthi, wtwi, wd0;
+  {
+    int t = tbeg;
+    wd0 = t % D; t /= D;
+    wtwi = t % tilesW; t /= tilesW;
+    wthi = t % tilesH;
+    wb = t / tilesH;
+  }
+  // Column-invariant load state.  Within a column only the depth plane moves, so every
+  // h / w / channel test, the Src2 pointer choice and the in-plane offsets are taken once
+  // per column (set_column): a lane's x loads are xcol (its batch, source and channel quad)
+  // + plane * xpl + xo[k], its dy loads the uniform ycol + plane * ypl (+ a uniform row
+  // stride per k) + yo.  Invalid positions load from a clamped valid address of the same
+  // column and are zeroed at the stash (hmc / yl, ymk), depth validity is uniform: no load
+  // is conditional.  (Byte offsets in 32 bits: the host checks the plane sizes.)
+  constexpr int YC4 = CO / 4;                  // dy float4 per voxel
+  constexpr int YRS = 256 / YC4 / WX_TW;       // tile rows between a thread's dy loads
+  const int yrw = __builtin_amdgcn_readfirstlane(tid / (YC4 * WX_TW));  // its first row
+  const char* xcol = nullptr;
+  const char* ycol = nullptr;
+  const char* rlc = nullptr;   // HR: the boundary rows of this column's batch
+  const char* rhc = nullptr;
+  int xpl = 0;                 // bytes per depth plane of this lane's x source
+  const int ypl = H * W * lddy * 4;
+  const int yrs = YRS * W * lddy * 4;
+  uint32_t xo[NP], yo = 0;
+  unsigned hmc = 0;            // bit k: load k is a valid (not padding) position
+  unsigned rlm = 0, rhm = 0;   // HR: bit k: load k reads x.rlo / x.rhi
+  unsigned ymk = 0;            // bit k: dy load k is a row inside the volume (uniform)
+  bool yl = false;             // this lane's dy column and channels are inside
+  auto set_column = [&]() {
+    const int b = wb, h0 = wthi * WX_TH, w0 = wtwi * WX_TW;
+    const int c = ci_base + 4 * (tid % CQ);
+    const bool cv = c < Cin;
+    const int cc = cv ? c : 0;
+    const bool s0 = cc < x.split;
+    const int ldl = s0 ? x.ld0 : x.ld1;
+    xcol = reinterpret_cast<const char*>((s0 ? x.p0 + cc : x.p1 + (cc - x.split)) +
+                                         (int64_t)b * D * H * W * ldl);
+    xpl = H * W * ldl * 4;
+    if constexpr (HR) {
+      rlc = reinterpret_cast<const char*>(x.rlo + (int64_t)b * D * W * x.ldr);
+      rhc = reinterpret_cast<const char*>(x.rhi + (int64_t)b * D * W * x.ldr);
+    }
+    if constexpr (ACT) {
+      // the fused activation's coefficients of this column's batch and this thread's 4
+      // channels (a clamped channel where c >= Cin)
+      const int64_t o = (int64_t)b * x.ld0 + cc;
+      xal = *reinterpret_cast<const float4*>(x.al + o);
+      xde = *reinterpret_cast<const float4*>(x.de + o);
+    }
+    hmc = 0; rlm = 0; rhm = 0;
+#pragma unroll
+    for (int k = 0; k < NP; ++k) {
+      const int i = tid + 256 * k;
+      const int pos = i / CQ;
+      const int hw = pos % HWD, hh = pos / HWD;
+      const int gh = h0 + hh - 1, gw = w0 + hw - 1;
+      const bool wc = i < PPOS * CQ && (unsigned)gw < (unsigned)W && cv;
+      uint32_t o = (uint32_t)((h0 * W + w0) * ldl * 4);  // (the tile's first voxel: valid)
+      if (wc && (unsigned)gh < (unsigned)H) {
+        o = (uint32_t)((gh * W + gw) * ldl * 4);
+        hmc |= 1u << k;
+      }
+      if constexpr (HR) {
+        if (wc && ((gh == -1 && x.rlo) || (gh == H && x.rhi))) {
+          o = (uint32_t)((gw * x.ldr + c) * 4);
+          hmc |= 1u << k;
+          if (gh < 0) rlm |= 1u << k; else rhm |= 1u << k;
+        }
+      }
+      xo[k] = o;
+    }
+    // dy: voxel kv = tid / YC4 + k * (256 / YC4) = row yrw + k YRS, column (tid / YC4) % 16
+    const int hv = min(WX_TH, H - h0);
+    const int col = (tid / YC4) % WX_TW, c4 = tid % YC4;
+    const bool wv = w0 + col < W, ov = co0 + 4 * c4 < Cout;
+    yl = wv && ov;
+    yo = (uint32_t)(((min(yrw, hv - 1) * W + (wv ? col : 0)) * lddy + (ov ? 4 * c4 : 0)) * 4);
+    ymk = 0;
+#pragma unroll
+    for (int k = 0; k < NY; ++k)
+      if (yrw + YRS * k < hv) ymk |= 1u << k;
+    ycol = reinterpret_cast<const char*>(dy + ((((int64_t)b * D) * H + h0) * W + w0) * lddy + co0);
+  };
+  // the walker's next tile; true where it starts a new column
+  auto advance = [&]() {
+    if (++wd0 < D) return false;
+    wd0 = 0;
+    if (++wtwi == tilesW) {
+      wtwi = 0;
+      if (++wthi == tilesH) { wthi = 0; ++wb; }
+    }
+    return true;
   };
   // (the fused input activation is applied at the store, not here: applied to each load as
   // it arrived, it made the prefetch wait for every load in turn before the MFMAs)
   unsigned hm = 0;  // bit k: hreg[k] is a valid (not padding) position
-  auto load_plane = [&](const TileXY& tx, int gd, float4 (&r)[NP], unsigned& m) {
-    m = 0;
+  // depth plane gd of the walker's column (a clamped plane where gd is padding: m = 0)
+  auto load_plane = [&](int gd, float4 (&r)[NP], unsigned& m) {
+    const bool dv = (unsigned)(gd + vol.dh) < (unsigned)(D + 2 * vol.dh) &&
+                    !((gd < 0 && x.zlo) || (gd >= D && x.zhi));
+    const int gdc = dv ? gd : min(max(gd, 0), D - 1);
+    const char* xt = xcol + (int64_t)gdc * xpl;
 #pragma unroll
     for (int k = 0; k < NP; ++k) {
-      const int i = tid + 256 * k;
-      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (i < PPOS * CQ) {
-        const int c4 = i % CQ, pos = i / CQ;
-        const int hw = pos % HWD, hh = pos / HWD;
-        const int b = tx.b, gh = tx.h0 + hh - 1, gw = tx.w0 + hw - 1;
-        const int c = ci_base + 4 * c4;
-        bool hin = (unsigned)gh < (unsigned)H;
-        if constexpr (HR) hin = hin || (gh == -1 && x.rlo) || (gh == H && x.rhi);
-        if ((unsigned)(gd + vol.dh) < (unsigned)(D + 2 * vol.dh) && hin &&
-            (unsigned)gw < (unsigned)W && c < Cin && !((gd < 0 && x.zlo) || (gd >= D && x.zhi))) {
-          const int64_t vox = (((int64_t)b * D + gd) * H + gh) * W + gw;
-          const float* p =
-              c < x.split ? x.p0 + vox * x.ld0 + c : x.p1 + vox * x.ld1 + (c - x.split);
-          if constexpr (HR) {
-            if ((unsigned)gh >= (unsigned)H)
-              p = (gh < 0 ? x.rlo : x.rhi) + (((int64_t)b * D + gd) * W + gw) * x.ldr + c;
-          }
-          v = *reinterpret_cast<const float4*>(p);
-          m |= 1u << k;
-        }
+      const char* p = xt;
+      if constexpr (HR) {
+        const int64_t ro = (int64_t)gdc * (W * x.ldr * 4);
+        if ((rlm >> k) & 1u) p = rlc + ro;
+        if ((rhm >> k) & 1u) p = rhc + ro;
       }
-      r[k] = v;
+      r[k] = *reinterpret_cast<const float4*>(p + xo[k]);
     }
+    m = dv ? hmc : 0u;
   };
   auto store_plane = [&](int gd, const float4 (&r)[NP], unsigned m) {
     unsigned short* dst = Xs + (R4 ? ((gd + 4) & 3) : ((gd + 3) % KD)) * PPOS * CI;
@@ -445,12 +521,14 @@ __global__ __launch_bounds__(256, 2) void k_conv3d_wgrad_x16(
       if (i < PPOS * CQ) {
         uint2 o[NPL];
         float4 v = r[k];
-        if (ACT && ((m >> k) & 1u)) {  // lrelu(IN(y)) of valid positions (padding stays 0)
+        if constexpr (ACT) {  // lrelu(IN(y)) (of valid positions: padding is zeroed below)
           v.x = v.x * xal.x + xde.x; v.x = v.x > 0.f ? v.x : 0.01f * v.x;
           v.y = v.y * xal.y + xde.y; v.y = v.y > 0.f ? v.y : 0.01f * v.y;
           v.z = v.z * xal.z + xde.z; v.z = v.z > 0.f ? v.z : 0.01f * v.z;
           v.w = v.w * xal.w + xde.w; v.w = v.w > 0.f ? v.w : 0.01f * v.w;
         }
+        // padding positions were loaded from a clamped address: zero
+        if (!((m >> k) & 1u)) v = make_float4(0.f, 0.f, 0.f, 0.f);
         if constexpr (HF) v = make_float4(v.x * sx, v.y * sx, v.z * sx, v.w * sx);
         split4<NS>(v, o);
 #pragma unroll
@@ -459,31 +537,14 @@ __global__ __launch_bounds__(256, 2) void k_conv3d_wgrad_x16(
       }
     }
   };
-  auto fetch = [&](int tile) {
-    const TileXY tx = tile_xy(tile);
-    if constexpr (ACT) {
-      // the fused activation's coefficients of this tile's batch and this thread's 4
-      // channels, loaded unconditionally from a clamped channel, so no branch merge waits
-      // for them here -- store_plane does
-      const int c = ci_base + 4 * (tid % CQ);
-      const int64_t o = (int64_t)tx.b * x.ld0 + (c < Cin ? c : 0);
-      xal = *reinterpret_cast<const float4*>(x.al + o);
-      xde = *reinterpret_cast<const float4*>(x.de + o);
-    }
-    load_plane(tx, tx.d0 + KD / 2, hreg, hm);
-    const int b = tx.b, d0 = tx.d0, h0 = tx.h0, w0 = tx.w0;
+  // the walker's tile: its new plane and its dy, from a uniform base + the lane's offset
+  auto fetch = [&]() {
+    load_plane(wd0 + KD / 2, hreg, hm);
+    const char* yt = ycol + (int64_t)wd0 * ypl;
 #pragma unroll
     for (int k = 0; k < NY; ++k) {
-      const int i = tid + 256 * k;
-      const int c4 = i % (CO / 4), kv = i / (CO / 4);
-      const int gh = h0 + kv / WX_TW, gw = w0 + kv % WX_TW;
-      const int c = co0 + 4 * c4;
-      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (gh < H && gw < W && c < Cout) {
-        const int64_t vox = (((int64_t)b * D + d0) * H + gh) * W + gw;
-        v = *reinterpret_cast<const float4*>(dy + vox * lddy + c);
-      }
-      yreg[k] = v;
+      const char* yk = yt + (((ymk >> k) & 1u) ? k * yrs : 0);  // (rows past H: row 0)
+      yreg[k] = *reinterpret_cast<const float4*>(yk + yo);
     }
   };
   auto stash = [&](int d0, bool negate, int yb) {
@@ -494,7 +555,9 @@ __global__ __launch_bounds__(256, 2) void k_conv3d_wgrad_x16(
       const int c4 = i % (CO / 4), kv = i / (CO / 4);
       uint2 o[NPL];
       const float ys = HF ? (negate ? -sy : sy) : (negate ? -1.f : 1.f);
-      const float4 yv = make_float4(yreg[k].x * ys, yreg[k].y * ys, yreg[k].z * ys, yreg[k].w * ys);
+      // (voxels and channels outside were loaded from a clamped address: zero)
+      const float4 yr = (yl && ((ymk >> k) & 1u)) ? yreg[k] : make_float4(0.f, 0.f, 0.f, 0.f);
+      const float4 yv = make_float4(yr.x * ys, yr.y * ys, yr.z * ys, yr.w * ys);
       split4<NS>(yv, o);
       const int off = kv * CO + (((c4 >> 1) ^ (CO == 32 ? ((kv >> 2) & 1) << 1 : 0)) << 3) + 4 * (c4 & 1);
 #pragma unroll
@@ -559,28 +622,26 @@ __global__ __launch_bounds__(256, 2) void k_conv3d_wgrad_x16(
     }
   };
 
-  const int tbeg = split * tps;
-  const int tend = min(ntiles, tbeg + tps);
-  // first tile of a column: its other planes d0 - KD / 2 .. d0 + KD / 2 - 1
-  auto stage_column = [&](int tile, int d0) {
-    const TileXY tx = tile_xy(tile);
+  // first tile of a column (the walker's): its other planes d0 - KD / 2 .. d0 + KD / 2 - 1
+  auto stage_column = [&](int d0) {
 #pragma unroll
     for (int hd = 0; hd < KD - 1; ++hd) {
       float4 r[NP];
       unsigned m;
-      load_plane(tx, d0 + hd - KD / 2, r, m);
+      load_plane(d0 + hd - KD / 2, r, m);
       store_plane(d0 + hd - KD / 2, r, m);
     }
   };
+  // Every iteration fetches unconditionally: after the last tile the walker stays where it
+  // is, and the dummy fetch reloads that tile (valid addresses, never stashed).
+  set_column();
   if constexpr (R4) {
     // tile t computes from ring slots and dy buffer (t - tbeg) & 1, while tile t + 1's
     // plane / dy are fetched and stored to the slot / buffer it does not read; a new
     // column's two extra planes overwrite slots the tile before may read: one more barrier
-    if (tbeg < tend) {
-      fetch(tbeg);
-      stage_column(tbeg, tbeg % D);
-      stash(tbeg % D, false, 0);
-    }
+    fetch();
+    stage_column(wd0);
+    stash(wd0, false, 0);
     for (int tile = tbeg; tile < tend; ++tile) {
       if (tile != tbeg) {
 #pragma unroll
@@ -589,22 +650,27 @@ __global__ __launch_bounds__(256, 2) void k_conv3d_wgrad_x16(
           for (int cb = 0; cb < NCB; ++cb) acc[j][cb] = -acc[j][cb];
       }
       __syncthreads();  // this tile's plane / dy visible; every wave is past tile - 1
-      const int d0 = tile % D;
+      const int d0 = wd0;
       ybuf = (tile - tbeg) & 1;
-      if (tile + 1 < tend) fetch(tile + 1);
+      const bool more = tile + 1 < tend;
+      bool newcol = false;
+      if (more) {
+        newcol = advance();
+        if (newcol) set_column();
+      }
+      fetch();
       if (nj == NJMAX) compute(std::integral_constant<int, NJMAX>{}, d0);
       else if constexpr (NJMAX > 1) compute(std::integral_constant<int, NJMAX - 1>{}, d0);
-      if (tile + 1 < tend) {
-        const int d1 = (tile + 1) % D;
-        if (d1 == 0) {
+      if (more) {
+        if (newcol) {
           __syncthreads();  // every wave is past this tile's reads of the ring
-          stage_column(tile + 1, d1);
+          stage_column(wd0);
         }
-        stash(d1, ((tile + 1 - tbeg) & 1) != 0, ybuf ^ 1);
+        stash(wd0, ((tile + 1 - tbeg) & 1) != 0, ybuf ^ 1);
       }
     }
   } else {
-  if (tbeg < tend) fetch(tbeg);
+  fetch();
   for (int tile = tbeg; tile < tend; ++tile) {
     // sign-alternating accumulation (conv3d_x.hip)
     if (tile != tbeg) {
@@ -614,11 +680,12 @@ __global__ __launch_bounds__(256, 2) void k_conv3d_wgrad_x16(
         for (int cb = 0; cb < NCB; ++cb) acc[j][cb] = -acc[j][cb];
     }
     __syncthreads();  // previous compute done reading LDS
-    const int d0 = tile % D;
-    if (KD > 1 && (tile == tbeg || d0 == 0)) stage_column(tile, d0);
+    const int d0 = wd0;
+    if (KD > 1 && (tile == tbeg || d0 == 0)) stage_column(d0);
     stash(d0, ((tile - tbeg) & 1) != 0, 0);
     __syncthreads();
-    if (tile + 1 < tend) fetch(tile + 1);
+    if (tile + 1 < tend && advance()) set_column();
+    fetch();
     if (nj == NJMAX) compute(std::integral_constant<int, NJMAX>{}, d0);
     else if constexpr (NJMAX > 1) compute(std::integral_constant<int, NJMAX - 1>{}, d0);
   }
@@ -711,7 +778,10 @@ WxPlan wx_plan(Vol vol, int Cin, int Cout) {
   p.tilesW = cdiv(vol.W, WX_TW);
   p.ntiles = vol.B * vol.D * p.tilesH * p.tilesW;
   const int nout = (p.kpad / p.ci) * (p.npad / p.co);
-  // two workgroups per CU: aim at 2 rounds of 512, >= 4 tiles per workgroup
+  // two workgroups per CU: aim at 2 rounds of 512, >= 4 tiles per workgroup.  A workgroup
+  // runs tiles [split tps, split tps + tps) depth-fastest: it decodes its first tile once,
+  // walks on by d0 + 1 / column roll-over, and re-derives its lanes' load offsets and masks
+  // only where a column starts (k_conv3d_wgrad_x16: set_column)
   int nsplit = std::max(1, cdiv(1024, nout));
   nsplit = std::min(nsplit, std::max(1, p.ntiles / 4));
   p.tps = cdiv(p.ntiles, nsplit);
@@ -733,6 +803,9 @@ hipError_t conv3d_wgrad_x(const Src2& x, const float* dy, int lddy, float* dw, V
                           int Cin, int Cout, int math, float* ws, hipStream_t s,
                           const unsigned* xmax, const unsigned* ymax) {
   if (lddy % 4) return hipErrorInvalidValue;
+  // k_conv3d_wgrad_x16 keeps a lane's byte offsets inside one depth plane in 32 bits
+  const int64_t ldmax = std::max<int64_t>({x.ld0, x.ld1, lddy, x.rows() ? x.ldr : 0});
+  if ((int64_t)vol.H * vol.W * ldmax * 4 >= ((int64_t)1 << 31)) return hipErrorInvalidValue;
   WxPlan p = wx_plan(vol, Cin, Cout);
   const WxTable tb = make_table(KD, p.ci);
   dim3 grid(8 * cdiv(p.nsplit, 8) * (p.kpad / p.ci) * (p.npad / p.co));

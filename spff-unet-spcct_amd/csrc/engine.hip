@@ -1645,17 +1645,24 @@ int spff_conv3d_dgrad(const float* dy, const float* w, float* dx, int B, int D, 
   return spff_conv3d_dgrad_ex(dy, w, dx, B, D, H, W, cin, cout, ksd, SPFF_MATH_F32, ws, stream);
 }
 
-int spff_conv3d_wgrad_ex(const float* x, int ldx, const float* dy, float* dw, int B, int D,
-                         int H, int W, int cin, int cout, int ksd, int math, void* ws,
+int spff_conv3d_wgrad_ld(const float* x, int ldx, const float* dy, int lddy, float* dw, int B,
+                         int D, int H, int W, int cin, int cout, int ksd, int math, void* ws,
                          void* stream) {
   if (!x || !dy || !dw || !ws) return fail(SPFF_EINVAL, "null argument");
-  if (ldx % 4 || ldx < cin || cout % 4) return fail(SPFF_EINVAL, "bad channel strides");
+  if (ldx % 4 || ldx < cin || lddy % 4 || lddy < cout)
+    return fail(SPFF_EINVAL, "bad channel strides");
   if (math < SPFF_MATH_F32 || math > SPFF_MATH_F16X3) return fail(SPFF_EINVAL, "bad math");
   hipStream_t s = static_cast<hipStream_t>(stream);
   float* part = static_cast<float*>(ws) + conv_op_pack_floats(cin, cout, ksd) + 64;
-  HIPCK(conv3d_wgrad(src1(x, ldx), dy, cout, dw, Vol{B, D, H, W}, ksd, cin, cout, math, part,
+  HIPCK(conv3d_wgrad(src1(x, ldx), dy, lddy, dw, Vol{B, D, H, W}, ksd, cin, cout, math, part,
                      s));
   return SPFF_OK;
+}
+
+int spff_conv3d_wgrad_ex(const float* x, int ldx, const float* dy, float* dw, int B, int D,
+                         int H, int W, int cin, int cout, int ksd, int math, void* ws,
+                         void* stream) {
+  return spff_conv3d_wgrad_ld(x, ldx, dy, cout, dw, B, D, H, W, cin, cout, ksd, math, ws, stream);
 }
 
 int spff_conv3d_wgrad(const float* x, int ldx, const float* dy, float* dw, int B, int D, int H,
