@@ -88,6 +88,15 @@ typedef struct spff_cfg {
    * defaults (32, 16, off: what _DoubleConvSpectral_Novel builds).  hidden 1..64,
    * pe_dims 2..32 ((hidden + pe_dims) * depth * 4 B of LDS <= 160 KiB) */
   int efilm_hidden, efilm_pe_dims, fgate_learn_phase;
+  /* UNet3D_SpectralCore(use_spatial, use_skip_gate) (models.py:654-682): CBAM spatial
+   * attention after each encoder stage's Spectral-SE / Channel-SE (parameters
+   * sa.{0..3}.conv.weight [1][2][3][7][7]) and attention gates g3, g2, g1 on the skips (the
+   * gate multiplies the up-conv output; the decoder reads [up | gated up]).  0, 0: the plans
+   * as before.  Either flag: unsharded plans only (SPFF_EINVAL otherwise), never the lean
+   * layout (SPFF_MEM_LEAN: SPFF_EINVAL; SPFF_MEM_AUTO resolves to the full one);
+   * use_skip_gate needs H and W multiples of 8 (SPFF_ESHAPE: where the reference's _cat
+   * would resize, its gate fails on the mismatched shapes). */
+  int use_spatial, use_skip_gate;
 } spff_cfg;
 
 #define SPFF_SHARD_DEPTH 0
@@ -268,6 +277,21 @@ int spff_upconv_dgrad(const float* dy, const float* w, float* dx, int B, int D, 
                       int cin, int cout, int math, void* ws, void* stream);
 int spff_upconv_wgrad(const float* x, const float* dy, float* dw, float* db, int B, int D, int H,
                       int W, int cin, int cout, int math, void* ws, void* stream);
+/* Op-level CBAM spatial attention (reference SpatialAttention3D, models.py:434-446) on
+ * channel-last fp32 x, y, dy, dx [B][D][H][W][C], C a multiple of 8; w is conv.weight
+ * [1][2][3][7][7] (no bias).  fwd: map [V][2] = (mean_c x, max_c x), idx [V] = the lowest
+ * channel that holds the max, attn [V] = sigmoid(conv3d(map, w, zero padding (1,3,3))),
+ * y = x * attn (V = B D H W).  bwd takes what fwd wrote and gives dx and dw [294]
+ * (overwritten; dx may be dy, y may be x).  Every sum has a fixed order: two calls give the same bits.
+ * x, y, dy, dx, map and ws are 16-byte aligned; ws >= spff_spatial_attn_ws_bytes(...) for
+ * bwd (fwd does not touch it and takes NULL). */
+size_t spff_spatial_attn_ws_bytes(int B, int D, int H, int W, int C);
+int spff_spatial_attn_fwd(const float* x, const float* w, int B, int D, int H, int W, int C,
+                          float* y, float* attn, float* map, int32_t* idx, void* ws,
+                          void* stream);
+int spff_spatial_attn_bwd(const float* dy, const float* x, const float* w, const float* attn,
+                          const float* map, const int32_t* idx, int B, int D, int H, int W, int C,
+                          float* dx, float* dw, void* ws, void* stream);
 
 /* ---------------------------------------------------------------------------
  * 3D U-Net baseline variant (BASELINE config 3; registry entry "3DUNet",

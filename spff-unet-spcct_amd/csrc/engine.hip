@@ -91,6 +91,11 @@ struct Blk {
   bool fout = false;  // out never stored: its GEMM consumers apply it to y2 (ActRows)
   size_t pk[4] = {0, 0, 0, 0};  // batched conv images: c1 fwd, c2 fwd, c2 dgrad, c1 dgrad
   size_t PT = 0, QT = 0;  // fout + gates: P, Q as [B][D][C]
+  // use_spatial (encoder stages): out = z a with z = lrelu(IN(y2)) P + Q; the conv weight
+  // and the saved a [V], (mean, max) [V][2], argmax [V] (int32)
+  bool sa = false;
+  int64_t saw = -1;
+  size_t sa_a = 0, sa_m = 0, sa_i = 0;
   bool tail() const { return efilm || fgate || post_se || post_spec; }
 };
 
@@ -105,6 +110,13 @@ struct UpL {
   size_t raw = 0;
 };
 
+// use_skip_gate: the attention gate of one skip (attn_gate.hip), s = up psi
+struct GateL {
+  int C, I, lvl;
+  int64_t wx = -1, bx = -1, wg = -1, bg = -1, wpsi = -1, bpsi = -1;
+  size_t wcat = 0, bcat = 0, pk = 0, att = 0, psi = 0, s = 0, dwcat = 0, dbcat = 0;
+};
+
 }  // namespace
 
 struct spff_plan : PlanBase {
@@ -116,6 +128,9 @@ struct spff_plan : PlanBase {
                       // gradient scratch and are recomputed in the backward
   Blk blk[7];
   UpL up[3];  // up3, up2, up1
+  bool gated = false;   // use_skip_gate
+  GateL gate[3];        // g3, g2, g1 (beside up3, up2, up1)
+  size_t ag_part = 0, sa_ws = 0;  // the gates' psi partial sums; the sa backward's scratch
   int64_t out_w = -1, out_b = -1;
   size_t head_pk = 0;
   size_t x_cl = 0, pool[3] = {0, 0, 0}, pidx[3] = {0, 0, 0};
@@ -261,8 +276,15 @@ int build_plan(spff_plan* p) {
   if (c.efilm_hidden < 0 || c.efilm_pe_dims < 0 || p->efh > EFH_MAX || p->efp < 2 ||
       p->efp > EFP_MAX)
     return fail(SPFF_EINVAL, "efilm_hidden must be 1..64 and efilm_pe_dims 2..32 (0: 32, 16)");
+  const bool attn = c.use_spatial != 0 || c.use_skip_gate != 0;
+  if (attn && c.shard_world > 1)
+    return fail(SPFF_EINVAL, "use_spatial / use_skip_gate: unsharded plans only (the 3x7x7 "
+                             "stencil needs depth and row halos the collectives do not carry)");
+  if (attn && c.memory_mode == SPFF_MEM_LEAN)
+    return fail(SPFF_EINVAL, "use_spatial / use_skip_gate: the lean layout does not recompute "
+                             "them; use SPFF_MEM_FULL or SPFF_MEM_AUTO");
   p->lean = c.memory_mode == SPFF_MEM_LEAN ||
-            (c.memory_mode == SPFF_MEM_AUTO &&
+            (c.memory_mode == SPFF_MEM_AUTO && !attn &&
              (int64_t)c.batch * c.depth * c.height * c.width >= (int64_t(1) << 26));
   const int world = c.shard_world > 1 ? c.shard_world : 1;
   const bool hsh = world > 1 && c.shard_axis == SPFF_SHARD_HEIGHT;
@@ -305,10 +327,12 @@ int build_plan(spff_plan* p) {
     b.novel = b.efilm || b.fgate;
     b.post_se = i < 4 && c.use_se;
     b.post_spec = i < 4 && c.use_specse;
+    b.sa = i < 4 && c.use_spatial != 0;
     b.fa = conv3d_fuses_act(c.math, b.C);
     // the bottleneck and decoder outputs feed only the up-convs and the head (GEMMs)
+    // (a stage with spatial attention stores its output: the GEMMs cannot apply the stencil)
     b.fout = (SPFF_OUTFUSE >= 2 ? i >= 3 : SPFF_OUTFUSE == 1 && i == 6) && !p->lean &&
-             b.C % 4 == 0;
+             b.C % 4 == 0 && !b.sa;
     conv_dims(b.c1, b.Cin, b.C);
     conv_dims(b.c2, b.C, b.C);
   }
@@ -345,6 +369,31 @@ int build_plan(spff_plan* p) {
       b.sw2 = p->reg(pre + "2.weight", {C, h, 1, 1, 1});
       b.sb2 = p->reg(pre + "2.bias", {C});
       b.se1 = p->nparam;
+    }
+  }
+  // (sp has no parameters) sa.0..3, then g3, g2, g1: models.py:676-682
+  if (c.use_spatial)
+    for (int i = 0; i < 4; ++i)
+      p->blk[i].saw = p->reg("sa." + std::to_string(i) + ".conv.weight", {1, 2, 3, 7, 7});
+  p->gated = c.use_skip_gate != 0;
+  if (p->gated) {
+    const char* gn[3] = {"g3", "g2", "g1"};
+    for (int u = 0; u < 3; ++u) {
+      if (p->up[u].rs)
+        return fail(SPFF_ESHAPE, "use_skip_gate: H and W must be multiples of 8 (an up-conv "
+                                 "output and its skip differ where a pooled extent is odd, and "
+                                 "the reference's gate fails on them)");
+      GateL& g = p->gate[u];
+      g.C = p->up[u].Cout;
+      g.I = g.C / 2;
+      g.lvl = p->up[u].lvl_low - 1;
+      const std::string n = gn[u];
+      g.wx = p->reg(n + ".W_x.weight", {g.I, g.C, 1, 1, 1});
+      g.bx = p->reg(n + ".W_x.bias", {g.I});
+      g.wg = p->reg(n + ".W_g.weight", {g.I, g.C, 1, 1, 1});
+      g.bg = p->reg(n + ".W_g.bias", {g.I});
+      g.wpsi = p->reg(n + ".psi.weight", {1, g.I, 1, 1, 1});
+      g.bpsi = p->reg(n + ".psi.bias", {1});
     }
   }
 
@@ -428,6 +477,34 @@ int build_plan(spff_plan* p) {
   }
   p->head_pk = p->alloc(head_pack_floats(f, p->K) * sizeof(float));
   wg = std::max(wg, head_wgrad_ws_bytes(nvox(v0), f, p->K));
+  if (c.use_spatial) {
+    size_t sw = 0;
+    for (int i = 0; i < 4; ++i) {
+      Blk& b = p->blk[i];
+      const int64_t V = nvox(p->vol[b.lvl]);
+      b.sa_a = p->alloc(V * sizeof(float));
+      b.sa_m = p->alloc(2 * V * sizeof(float));
+      b.sa_i = p->alloc(V * sizeof(int));
+      sw = std::max(sw, sa_bwd_ws_bytes(p->vol[b.lvl]));
+    }
+    p->sa_ws = p->alloc(sw);
+  }
+  if (p->gated) {
+    for (int u = 0; u < 3; ++u) {
+      GateL& g = p->gate[u];
+      const int64_t M = nvox(p->vol[g.lvl]);
+      g.wcat = p->alloc((size_t)g.I * 2 * g.C * sizeof(float));
+      g.dwcat = p->alloc((size_t)g.I * 2 * g.C * sizeof(float));
+      g.bcat = p->alloc((size_t)g.I * sizeof(float));
+      g.dbcat = p->alloc((size_t)g.I * sizeof(float));
+      g.pk = p->alloc(head_pack_floats(2 * g.C, g.I) * sizeof(float));
+      g.att = p->alloc(M * g.I * sizeof(float));
+      g.psi = p->alloc(M * sizeof(float));
+      g.s = p->alloc(M * g.C * sizeof(float));
+      wg = std::max(wg, linear_wgrad_ws_bytes(M, 2 * g.C, g.I));
+    }
+    p->ag_part = p->alloc((size_t)AG_NB * (2 * f + 1) * sizeof(float));
+  }
   p->red_ws = p->alloc(red_ws);
   p->red_out = p->alloc(red_out);
   p->red_out4 = p->alloc(red_out4);
@@ -931,6 +1008,24 @@ int fwd_block(spff_plan* p, Blk& b, const Src2& in, int pool = -1) {
   }
   const float* P = b.tail() ? p->F(b.P) : nullptr;
   const float* Q = b.tail() ? p->F(b.Q) : nullptr;
+  if (b.sa) {
+    // z = lrelu(IN(y2)) P + Q into out, then out = z a in place: the pool, the up-conv and the
+    // skip read the attended output.  (F16_OUT holds max |z| >= max |z a|: a lies in (0, 1).)
+    const int64_t Vn = nvox(v);
+    PROFB(p, 5, 0.0, 8.0 * (double)Vn * C,
+          act_apply(p->F(b.y2), p->F(b.out), p->F(b.al2), p->F(b.de2), P, Q, v, C, p->st, 0.01f,
+                    f16_slot(p, b, F16_OUT)));
+    int* idx = reinterpret_cast<int*>(p->ws + b.sa_i);
+    PROFB(p, 5, 0.0, 4.0 * (double)Vn * (C + 3),
+          sa_stats(p->F(b.out), Vn, C, p->F(b.sa_m), idx, p->st));
+    PROFB(p, 5, 0.0, 12.0 * (double)Vn, sa_attn(p->F(b.sa_m), p->P(b.saw), v, p->F(b.sa_a), p->st));
+    PROFB(p, 5, 0.0, 4.0 * (double)Vn * (2 * C + 1),
+          sa_scale(p->F(b.out), p->F(b.sa_a), Vn, C, p->F(b.out), p->st));
+    if (pool >= 0)
+      HIPCK(maxpool_fwd(p->F(b.out), p->F(p->pool[pool]),
+                        reinterpret_cast<uint8_t*>(p->ws + p->pidx[pool]), v, C, p->st));
+    return SPFF_OK;
+  }
   if (b.fout && !p->keep_out) return SPFF_OK;  // applied by the up-conv / head GEMMs
   if (pool >= 0 && !((v.H | v.W) & 1)) {
     // read y2, write out + pooled + argmax bytes: 4C + 4C + C + C / 4 bytes per voxel
@@ -1165,6 +1260,43 @@ int grad_ready(spff_plan* p, int64_t a, int64_t b) {
   if (p->grad_fn(p->grad_ctx, a, b - a, p->st) != 0) return fail(SPFF_EHIP, "gradient hook failed");
   return SPFF_OK;
 }
+
+// use_spatial: the gradient de at stage b's attended output (materialised, [V][C]) -> dz at
+// z = lrelu(IN(y2)) P + Q in place, before the block's own backward; z is recomputed from y2
+// into G_dy2, which the block writes only later.  The conv weight's gradient is final here.
+int sa_bwd_step(spff_plan* p, const Blk& b, float* de) {
+  const Vol& v = p->vol[b.lvl];
+  float* z = p->F(p->G_dy2);
+  if (de == z) return fail(SPFF_EINVAL, "spatial attention: de aliases the z scratch");
+  PROFB(p, 5, 0.0, 8.0 * (double)nvox(v) * b.C,
+        act_apply(p->F(b.y2), z, p->F(b.al2), p->F(b.de2), b.tail() ? p->F(b.P) : nullptr,
+                  b.tail() ? p->F(b.Q) : nullptr, v, b.C, p->st));
+  PROFB(p, 6, 0.0, 16.0 * (double)nvox(v) * b.C,
+        sa_bwd(de, z, p->P(b.saw), p->F(b.sa_a), p->F(b.sa_m),
+               reinterpret_cast<const int*>(p->ws + b.sa_i), v, b.C, de, p->DP(b.saw),
+               p->ws + p->sa_ws, p->st));
+  return grad_ready(p, b.saw, b.saw + 294);
+}
+
+// use_skip_gate: gate u's tensors for attn_gate.hip.  Its backward runs after the decoder
+// block's, when G_da1 is dead: dhid [M][I] and dpp [M] live there (I = C / 2).
+AttnGate gate_view(const spff_plan* p, const GateL& g) {
+  AttnGate a{};
+  a.C = g.C; a.I = g.I; a.M = nvox(p->vol[g.lvl]);
+  a.wx = p->P(g.wx); a.bx = p->P(g.bx); a.wg = p->P(g.wg); a.bg = p->P(g.bg);
+  a.wpsi = p->P(g.wpsi); a.bpsi = p->P(g.bpsi);
+  if (p->dprm) {
+    a.dwx = p->DP(g.wx); a.dbx = p->DP(g.bx); a.dwg = p->DP(g.wg); a.dbg = p->DP(g.bg);
+    a.dwpsi = p->DP(g.wpsi); a.dbpsi = p->DP(g.bpsi);
+  }
+  a.wcat = p->F(g.wcat); a.bcat = p->F(g.bcat); a.pk = p->F(g.pk); a.att = p->F(g.att);
+  a.psi = p->F(g.psi); a.s = p->F(g.s); a.dwcat = p->F(g.dwcat); a.dbcat = p->F(g.dbcat);
+  a.dhid = p->F(p->G_da1);
+  a.dpp = a.dhid + a.M * g.I;
+  a.part = p->F(p->ag_part);
+  a.wgs = p->F(p->wg_ws);
+  return a;
+}
 int block_grads_ready(spff_plan* p, const Blk& b) {
   CK(grad_ready(p, b.pr0, b.pr1));
   return grad_ready(p, b.se0, b.se1);
@@ -1203,7 +1335,13 @@ int forward(spff_plan* p, const float* x, float* logits) {
     Blk& d = B[4 + u];
     const Blk& skip = B[2 - u];
     CK(upconv_out(p, U, *prev, f16_slot(p, d, F16_IN), f16_slot(p, skip, F16_OUT)));
-    CK(fwd_block(p, d, src2(p->F(U.out), p->F(skip.out), U.Cout)));
+    const float* sk = p->F(skip.out);
+    if (p->gated) {  // the decoder reads [up | up psi]; |up psi| <= |up|, so F16_IN bounds it
+      const AttnGate g = gate_view(p, p->gate[u]);
+      PROF(p, 3, 2.0 * g.M * 2.0 * g.C * g.I, attn_gate_fwd(g, p->F(U.out), sk, p->st));
+      sk = g.s;
+    }
+    CK(fwd_block(p, d, src2(p->F(U.out), sk, U.Cout)));
     prev = &d;
   }
   float* hp = p->F(p->head_pk);
@@ -1258,10 +1396,22 @@ int backward(spff_plan* p, const float* dl) {
     UpL& U = p->up[ui];
     const int C = d.C;             // = U.Cout = skip channels
     const int lvl = d.lvl;
-    Dst2 dx{p->F(p->G_dx), p->F(p->dskip[lvl]), C, C, C};
-    CK(bwd_block(p, d, p->F(p->G_out), &dx, src2(p->F(U.out), p->F(B[lvl].out), C), bi, {},
+    // gated skips: the second half of the input gradient is ds, into G_dy2 (dead once the
+    // block's last dgrad runs); the gate's backward adds its share to dd in G_dx and writes
+    // the encoder output's skip gradient
+    Dst2 dx{p->F(p->G_dx), p->F(p->gated ? p->G_dy2 : p->dskip[lvl]), C, C, C};
+    const float* sk = p->gated ? p->F(p->gate[ui].s) : p->F(B[lvl].out);
+    CK(bwd_block(p, d, p->F(p->G_out), &dx, src2(p->F(U.out), sk, C), bi, {},
                  fold && k == 0 ? &hsrc : nullptr));
     CK(block_grads_ready(p, d));
+    if (p->gated) {
+      const GateL& gl = p->gate[ui];
+      const AttnGate g = gate_view(p, gl);
+      PROF(p, 3, 4.0 * g.M * 2.0 * g.C * g.I,
+           attn_gate_bwd(g, p->F(U.out), p->F(B[lvl].out), p->F(p->G_dy2), p->F(p->G_dx),
+                         p->F(p->dskip[lvl]), p->st));
+      CK(grad_ready(p, gl.wx, gl.bpsi + 1));
+    }
     if (p->dbg_stop == k + 1) return SPFF_OK;
     const Blk& ub = (ui == 0) ? B[3] : B[bi - 1];  // the up-conv's input block
     const ActRows uact = act_rows(p, ub);
@@ -1287,6 +1437,7 @@ int backward(spff_plan* p, const float* dl) {
   // bottleneck + encoder
   {
     Dst2 dx = dst1(p->F(p->G_dx), 4 * f);
+    if (B[3].sa) CK(sa_bwd_step(p, B[3], p->F(p->G_out)));
     CK(bwd_block(p, B[3], p->F(p->G_out), &dx, src1(p->F(p->pool[2]), 4 * f)));
     CK(block_grads_ready(p, B[3]));
   }
@@ -1297,11 +1448,13 @@ int backward(spff_plan* p, const float* dl) {
     PoolAdd pa;
     pa.dp = p->F(p->G_dx);
     pa.idx = reinterpret_cast<const uint8_t*>(p->ws + p->pidx[l]);
-    if (!p->pool_fold) {
+    // (spatial attention needs the materialised gradient: it turns it into dz first)
+    if (!p->pool_fold || B[l].sa) {
       HIPCK(maxpool_bwd_add(pa.dp, pa.idx, p->F(p->dskip[l]), C, p->F(p->dskip[l]), p->vol[l], C,
                             p->st));
       pa = PoolAdd{};
     }
+    if (B[l].sa) CK(sa_bwd_step(p, B[l], p->F(p->dskip[l])));
     if (l > 0) {
       Dst2 dx = dst1(p->F(p->G_dx), C / 2);
       CK(bwd_block(p, B[l], p->F(p->dskip[l]), &dx, src1(p->F(p->pool[l - 1]), C / 2), -1, pa));
@@ -1447,6 +1600,20 @@ int spff_saved_tensor(const spff_plan* p, void* ws, const char* name, const floa
     if (n == b.name + ".de1") return ret(b.de1, bv, b.C);
     if (n == b.name + ".al2") return ret(b.al2, bv, b.C);
     if (n == b.name + ".de2") return ret(b.de2, bv, b.C);
+    // use_spatial: the attention map a [V] and the channel argmax [V] (int32 words)
+    if (b.sa && n == b.name + ".sa") return ret(b.sa_a, v, 1);
+    if (b.sa && n == b.name + ".sa.map") return ret(b.sa_m, v, 2);
+    if (b.sa && n == b.name + ".sa.idx") return ret(b.sa_i, v, 1);
+  }
+  if (p->gated) {  // use_skip_gate: relu(hidden) [V][I], psi [V], s = up psi [V][C]
+    const char* gn[3] = {"g3", "g2", "g1"};
+    for (int u = 0; u < 3; ++u) {
+      const GateL& g = p->gate[u];
+      const std::string nm = gn[u];
+      if (n == nm + ".att") return ret(g.att, p->vol[g.lvl], g.I);
+      if (n == nm + ".psi") return ret(g.psi, p->vol[g.lvl], 1);
+      if (n == nm + ".s") return ret(g.s, p->vol[g.lvl], g.C);
+    }
   }
   for (int l = 0; l < 3; ++l) {
     if (n == "pool" + std::to_string(l + 1)) return ret(p->pool[l], p->vol[l + 1], p->f << l);

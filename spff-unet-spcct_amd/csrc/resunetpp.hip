@@ -20,15 +20,15 @@
 // conv3d_wgrad in the plan's SPFF_MATH_*, slab_reduce + in_mean / in_rstd, act_apply,
 // linear_*, maxpool3_*, upconv_*, head_*); [u | s] is read through two-source views.  New
 // here: the dilated conv (forward / input gradient / weight gradient, fp32 MFMA under every
-// math: it runs at 1/16 resolution), the residual tail and its mask, the SE gate and the
-// attention gate's per-voxel part.
+// math: it runs at 1/16 resolution), the residual tail and its mask and the SE gate.  The
+// attention gate is attn_gate.hip's, shared with the SPFF plan's gated skips.
 //
 // Residual tail backward.  dz = dout [out > 0] is written once (k_rupp_mask): it is the
 // skip path's gradient and, being already masked by the block's output, enters IN2's
 // backward as a plain gradient -- RED_BWD_IN / in_bwd_apply with slope 1 on both sides of
 // zero, so no mask of IN2(y2) is applied.
 //
-// Attention gate.  The hidden row is one GEMM over the two-source view [u | se(e)] with the
+// Attention gate (attn_gate.hip).  The hidden row is one GEMM over the two-source view [u | se(e)] with the
 // weight [W_x | W_g] and the bias b_x + b_g; its ReLU output att [V][C/2] is stored, as is
 // psi (one float per voxel).  The backward forms dpsi per voxel, reduces psi's weight
 // gradient in a fixed two-stage order, forms the hidden row's gradient from att's signs
@@ -47,7 +47,6 @@ using namespace spff;
 namespace {
 
 constexpr int NLVL = 5, NUNIT = 10, NUP = 4, NBR = 4, NSE = 4, NAG = 3;
-constexpr int AG_NB = 256;  // blocks of the psi weight-gradient partial sums
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -401,158 +400,6 @@ __global__ __launch_bounds__(256) void k_se_bwd_apply(float* __restrict__ g,
   }
 }
 
-// ------------------------------------------------------------ attention gate --
-// wcat [I][2C] = [W_x | W_g], bcat = b_x + b_g
-__global__ __launch_bounds__(256) void k_ag_cat(const float* __restrict__ wx,
-                                                const float* __restrict__ wg,
-                                                const float* __restrict__ bx,
-                                                const float* __restrict__ bg,
-                                                float* __restrict__ wcat, float* __restrict__ bcat,
-                                                int I, int C) {
-  const int n = I * 2 * C;
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-    const int j = i / (2 * C), c = i - j * 2 * C;
-    wcat[i] = c < C ? wx[j * C + c] : wg[j * C + c - C];
-    if (i < I) bcat[i] = bx[i] + bg[i];
-  }
-}
-// the reverse for the gradients: dW_x, dW_g from dwcat; db_x = db_g = dbcat
-__global__ __launch_bounds__(256) void k_ag_split(const float* __restrict__ dwcat,
-                                                  const float* __restrict__ dbcat,
-                                                  float* __restrict__ dwx, float* __restrict__ dwg,
-                                                  float* __restrict__ dbx, float* __restrict__ dbg,
-                                                  int I, int C) {
-  const int n = I * 2 * C;
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-    const int j = i / (2 * C), c = i - j * 2 * C;
-    if (c < C) dwx[j * C + c] = dwcat[i];
-    else dwg[j * C + c - C] = dwcat[i];
-    if (i < I) { dbx[i] = dbcat[i]; dbg[i] = dbcat[i]; }
-  }
-}
-// per voxel: att = relu(hidden row) in place, psi = sigmoid(w_psi . att + b_psi),
-// s = u psi
-__global__ __launch_bounds__(256) void k_ag_fwd(float* __restrict__ att,
-                                                const float* __restrict__ wpsi,
-                                                const float* __restrict__ bpsi,
-                                                const float* __restrict__ u,
-                                                float* __restrict__ psi, float* __restrict__ s,
-                                                int64_t V, int I, int C) {
-  for (int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; v < V;
-       v += (int64_t)gridDim.x * blockDim.x) {
-    float4* a = reinterpret_cast<float4*>(att + v * I);
-    float t = bpsi[0];
-    for (int j = 0; j < I / 4; ++j) {
-      float4 q = a[j];
-      q.x = fmaxf(q.x, 0.f); q.y = fmaxf(q.y, 0.f); q.z = fmaxf(q.z, 0.f); q.w = fmaxf(q.w, 0.f);
-      a[j] = q;
-      t += wpsi[4 * j] * q.x;
-      t += wpsi[4 * j + 1] * q.y;
-      t += wpsi[4 * j + 2] * q.z;
-      t += wpsi[4 * j + 3] * q.w;
-    }
-    const float p = 1.f / (1.f + expf(-t));
-    psi[v] = p;
-    const float4* ur = reinterpret_cast<const float4*>(u + v * C);
-    float4* sr = reinterpret_cast<float4*>(s + v * C);
-    for (int c = 0; c < C / 4; ++c) {
-      float4 q = ur[c];
-      q.x *= p; q.y *= p; q.z *= p; q.w *= p;
-      sr[c] = q;
-    }
-  }
-}
-// per voxel: du += ds psi;  dpp = (ds . u) psi (1 - psi)
-__global__ __launch_bounds__(256) void k_ag_bwd_vox(const float* __restrict__ ds,
-                                                    const float* __restrict__ u,
-                                                    float* __restrict__ du,
-                                                    const float* __restrict__ psi,
-                                                    float* __restrict__ dpp, int64_t V, int C) {
-  for (int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; v < V;
-       v += (int64_t)gridDim.x * blockDim.x) {
-    const float p = psi[v];
-    const float4* dr = reinterpret_cast<const float4*>(ds + v * C);
-    const float4* ur = reinterpret_cast<const float4*>(u + v * C);
-    float4* gr = reinterpret_cast<float4*>(du + v * C);
-    float t = 0.f;
-    for (int c = 0; c < C / 4; ++c) {
-      const float4 a = dr[c], q = ur[c];
-      float4 g = gr[c];
-      t += a.x * q.x; t += a.y * q.y; t += a.z * q.z; t += a.w * q.w;
-      g.x += a.x * p; g.y += a.y * p; g.z += a.z * p; g.w += a.w * p;
-      gr[c] = g;
-    }
-    dpp[v] = t * p * (1.f - p);
-  }
-}
-// part[blk][j] = sum over the block's voxels of dpp[v] att[v][j] (j < I), part[blk][I] =
-// sum dpp[v]: thread (g, j) walks voxels g, g + ngc, ... of the block's chunk, then the
-// groups are added in order
-__global__ __launch_bounds__(256) void k_ag_wpsi_part(const float* __restrict__ att,
-                                                      const float* __restrict__ dpp,
-                                                      float* __restrict__ part, int64_t V, int I) {
-  __shared__ float sh[256];
-  __shared__ float sb[256];
-  const int64_t chunk = (V + gridDim.x - 1) / gridDim.x;
-  const int64_t vb = (int64_t)blockIdx.x * chunk, ve = min(V, vb + chunk);
-  for (int j0 = 0; j0 < I; j0 += 256) {
-    const int Ic = min(I - j0, 256);
-    const int g = threadIdx.x / Ic, j = threadIdx.x - g * Ic;
-    const int ngc = max(1, 256 / Ic);
-    float s = 0.f, sp = 0.f;
-    if (g < ngc) {
-      for (int64_t v = vb + g; v < ve; v += ngc) {
-        const float d = dpp[v];
-        s += d * att[v * I + j0 + j];
-        sp += d;
-      }
-    }
-    sh[threadIdx.x] = s;
-    sb[threadIdx.x] = sp;
-    __syncthreads();
-    if (threadIdx.x < Ic) {
-      float t = 0.f;
-      for (int q = 0; q < ngc; ++q) t += sh[q * Ic + threadIdx.x];
-      part[(int64_t)blockIdx.x * (I + 1) + j0 + threadIdx.x] = t;
-      if (j0 == 0 && threadIdx.x == 0) {
-        float tb = 0.f;
-        for (int q = 0; q < ngc; ++q) tb += sb[q * Ic];
-        part[(int64_t)blockIdx.x * (I + 1) + I] = tb;
-      }
-    }
-    __syncthreads();
-  }
-}
-// dwpsi[j] = sum_blk part[blk][j], dbpsi = sum_blk part[blk][I], in block order
-__global__ __launch_bounds__(256) void k_ag_wpsi_fin(const float* __restrict__ part, int nblk,
-                                                     float* __restrict__ dwpsi,
-                                                     float* __restrict__ dbpsi, int I) {
-  for (int j = blockIdx.x * blockDim.x + threadIdx.x; j <= I; j += gridDim.x * blockDim.x) {
-    float s = 0.f;
-    for (int q = 0; q < nblk; ++q) s += part[(int64_t)q * (I + 1) + j];
-    if (j < I) dwpsi[j] = s;
-    else dbpsi[0] = s;
-  }
-}
-// dhid[v][j] = dpp[v] w_psi[j] [att > 0]: the hidden row's gradient
-__global__ __launch_bounds__(256) void k_ag_dhid(const float* __restrict__ att,
-                                                 float* __restrict__ dhid,
-                                                 const float* __restrict__ dpp,
-                                                 const float* __restrict__ wpsi, int64_t n4,
-                                                 int I4) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4;
-       i += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t v = i / I4;
-    const int j = (int)(i - v * I4) * 4;
-    const float d = dpp[v];
-    const float4 w = *reinterpret_cast<const float4*>(wpsi + j);
-    float4 a = reinterpret_cast<const float4*>(att)[i];
-    a.x = a.x > 0.f ? d * w.x : 0.f; a.y = a.y > 0.f ? d * w.y : 0.f;
-    a.z = a.z > 0.f ? d * w.z : 0.f; a.w = a.w > 0.f ? d * w.w : 0.f;
-    reinterpret_cast<float4*>(dhid)[i] = a;
-  }
-}
-
 struct PUnit {
   std::string name;
   int lvl, Cin, C;
@@ -875,42 +722,33 @@ int se_bwd(spff_rupp* p, PSe& s, const float* x, float* g) {
   return SPFF_OK;
 }
 
+// the gate's tensors for the shared implementation (attn_gate.hip); the unit's backward is
+// done with G_1 / G_2 when the gate's runs, so they hold its scratch
+AttnGate ag_view(const spff_rupp* p, const PAg& a) {
+  AttnGate g{};
+  g.C = a.C; g.I = a.I; g.M = nvox(p->vol[a.lvl]);
+  g.wx = p->P(a.wx); g.bx = p->P(a.bx); g.wg = p->P(a.wg); g.bg = p->P(a.bg);
+  g.wpsi = p->P(a.wpsi); g.bpsi = p->P(a.bpsi);
+  if (p->dprm) {
+    g.dwx = p->DP(a.wx); g.dbx = p->DP(a.bx); g.dwg = p->DP(a.wg); g.dbg = p->DP(a.bg);
+    g.dwpsi = p->DP(a.wpsi); g.dbpsi = p->DP(a.bpsi);
+  }
+  g.wcat = p->F(a.wcat); g.bcat = p->F(a.bcat); g.pk = p->F(a.pk); g.att = p->F(a.att);
+  g.psi = p->F(a.psi); g.s = p->F(a.s); g.dwcat = p->F(a.dwcat); g.dbcat = p->F(a.dbcat);
+  g.dhid = p->F(p->G_1); g.dpp = p->F(p->G_2); g.part = p->F(p->ag_part);
+  g.wgs = p->F(p->wg_ws);
+  return g;
+}
+
 int ag_fwd(spff_rupp* p, PAg& a, const float* u, const float* g) {
-  const int64_t M = nvox(p->vol[a.lvl]);
-  const int C = a.C, I = a.I;
-  EW(k_ag_cat, (int64_t)I * 2 * C, p->P(a.wx), p->P(a.wg), p->P(a.bx), p->P(a.bg), p->F(a.wcat),
-     p->F(a.bcat), I, C);
-  float* pk = p->F(a.pk);
-  PLAN_HIPCK(head_pack(p->F(a.wcat), pk, pk + head_pack_dgrad_offset(2 * C, I), 2 * C, I, p->st));
-  PLAN_HIPCK(linear_fwd2(Src2{u, g, C, C, C}, 2 * C, pk, p->F(a.bcat), p->F(a.att), I, I, M, p->st));
-  EW(k_ag_fwd, M, p->F(a.att), p->P(a.wpsi), p->P(a.bpsi), u, p->F(a.psi), p->F(a.s), M, I, C);
+  PLAN_HIPCK(attn_gate_fwd(ag_view(p, a), u, g, p->st));
   return SPFF_OK;
 }
 
 // ds (the gradient at s = u psi) -> du += (its share), dg (written), parameter gradients
 int ag_bwd(spff_rupp* p, PAg& a, const float* u, const float* g, const float* ds, float* du,
            float* dg) {
-  const int64_t M = nvox(p->vol[a.lvl]);
-  const int C = a.C, I = a.I;
-  float* wgs = p->F(p->wg_ws);
-  float* dhid = p->F(p->G_1);  // (the unit's backward is done with G_1 / G_2)
-  float* dpp = p->F(p->G_2);
-  EW(k_ag_bwd_vox, M, ds, u, du, p->F(a.psi), dpp, M, C);
-  const int nb = (int)std::min<int64_t>(AG_NB, (M + 255) / 256);
-  hipLaunchKernelGGL(k_ag_wpsi_part, dim3(nb), dim3(256), 0, p->st, p->F(a.att), dpp,
-                     p->F(p->ag_part), M, I);
-  PLAN_HIPCK(hipGetLastError());
-  hipLaunchKernelGGL(k_ag_wpsi_fin, dim3(1), dim3(256), 0, p->st, p->F(p->ag_part), nb,
-                     p->DP(a.wpsi), p->DP(a.bpsi), I);
-  PLAN_HIPCK(hipGetLastError());
-  EW(k_ag_dhid, M * I / 4, p->F(a.att), dhid, dpp, p->P(a.wpsi), M * I / 4, I / 4);
-  const Src2 in{u, g, C, C, C};
-  PLAN_HIPCK(linear_wgrad2(in, 2 * C, dhid, I, I, p->F(a.dwcat), p->F(a.dbcat), M, wgs, p->st));
-  EW(k_ag_split, (int64_t)I * 2 * C, p->F(a.dwcat), p->F(a.dbcat), p->DP(a.wx), p->DP(a.wg),
-     p->DP(a.bx), p->DP(a.bg), I, C);
-  PLAN_HIPCK(spff::zero_async(dg, M * C * sizeof(float), p->st));
-  PLAN_HIPCK(linear_dgrad2(dhid, I, I, p->F(a.pk) + head_pack_dgrad_offset(2 * C, I),
-                       Dst2{du, dg, C, C, C}, 2 * C, M, 1, p->st));
+  PLAN_HIPCK(attn_gate_bwd(ag_view(p, a), u, g, ds, du, dg, p->st));
   return SPFF_OK;
 }
 

@@ -269,6 +269,18 @@ hipError_t upconv_wgrad(const float* x, const float* dy, int lddy, float* dw, fl
                         int math = SPFF_MATH_F32, const ActRows* act = nullptr);
 size_t upconv_pack_floats(int Cin, int Cout, int ns = 4);
 size_t upconv_pack_dgrad_offset(int Cin, int Cout, int ns = 4);
+// spatial_attn.hip: CBAM spatial attention on rows x [V][C] (C a multiple of 8).
+// sa_stats: map [V][2] = (mean_c, max_c), idx [V] = the lowest argmax; sa_attn: attn [V] =
+// sigmoid of the 2 -> 1 channel 3x7x7 stencil of map (w [2][3][7][7]); sa_scale: y = x attn
+// (y may be x).  sa_bwd: dx (may be dy) and dw [294] from dy and what the forward wrote;
+// ws >= sa_bwd_ws_bytes(v).  Fixed summation orders, no atomics.
+hipError_t sa_stats(const float* x, int64_t V, int C, float* map, int* idx, hipStream_t s);
+hipError_t sa_attn(const float* map, const float* w, Vol v, float* attn, hipStream_t s);
+hipError_t sa_scale(const float* x, const float* attn, int64_t V, int C, float* y, hipStream_t s);
+size_t sa_bwd_ws_bytes(Vol v);
+hipError_t sa_bwd(const float* dy, const float* x, const float* w, const float* attn,
+                  const float* map, const int* idx, Vol v, int C, float* dx, float* dw, void* ws,
+                  hipStream_t s);
 // 1x1x1 conv head: y[v][K] = x[v][:Cin] . W[K][Cin] + b  (wf/wd from head_pack)
 hipError_t head_pack(const float* w, float* wf, float* wd, int Cin, int K, hipStream_t s);
 size_t head_pack_floats(int Cin, int K);
@@ -317,6 +329,27 @@ hipError_t linear_wgrad2(const Src2& x, int K, const float* dy, int lddy, int N,
 hipError_t patch_embed_wgrad(const float* x, int ldx, int Cin, int D, int H, int W, int B,
                              const float* dy, int N, float* dw, float* db, float* ws,
                              hipStream_t s);
+
+// ---------------------------------------------------------- attention gate --
+// attn_gate.hip: s = u sigmoid(w_psi . relu(W_x u + W_g g + b_x + b_g) + b_psi) on rows
+// u, g [M][C] with I hidden channels (I a multiple of 4), for every plan with gated skips.
+constexpr int AG_NB = 256;  // blocks of the psi weight-gradient partial sums
+struct AttnGate {
+  int C, I;
+  int64_t M;
+  const float *wx, *bx, *wg, *bg, *wpsi, *bpsi;     // W_x [I][C], b_x [I], W_g, b_g, psi [I], [1]
+  float *dwx, *dbx, *dwg, *dbg, *dwpsi, *dbpsi;     // their gradients (backward: overwritten)
+  // workspace: [W_x | W_g] [I][2C] and b_x + b_g, their linear_* image (head_pack_floats(2C, I)),
+  // saved att = relu(hidden) [M][I], psi [M], s [M][C]; the concatenated gradients
+  float *wcat, *bcat, *pk, *att, *psi, *s, *dwcat, *dbcat;
+  // backward scratch: dhid [M][I], dpp [M], part [AG_NB][I + 1], wgs >= linear_wgrad_ws_bytes(M, 2C, I)
+  float *dhid, *dpp, *part, *wgs;
+};
+hipError_t attn_gate_fwd(const AttnGate& a, const float* u, const float* g, hipStream_t s);
+// ds (the gradient at s) -> du += its share through s and the hidden row, dg written,
+// parameter gradients written
+hipError_t attn_gate_bwd(const AttnGate& a, const float* u, const float* g, const float* ds,
+                         float* du, float* dg, hipStream_t s);
 
 // ------------------------------------------------------------- norm/gates --
 // Per-(b,d,c) reductions over (h,w) with per-(b,c) affine/recompute ops.

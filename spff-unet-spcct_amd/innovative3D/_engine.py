@@ -42,7 +42,8 @@ class spff_cfg(ctypes.Structure):
         ("math", ctypes.c_int), ("shard_world", ctypes.c_int), ("shard_rank", ctypes.c_int),
         ("memory_mode", ctypes.c_int), ("shard_axis", ctypes.c_int),
         ("efilm_hidden", ctypes.c_int), ("efilm_pe_dims", ctypes.c_int),
-        ("fgate_learn_phase", ctypes.c_int),
+        ("fgate_learn_phase", ctypes.c_int), ("use_spatial", ctypes.c_int),
+        ("use_skip_gate", ctypes.c_int),
     ]
 
 
@@ -188,6 +189,9 @@ _SIGS = {
     "spff_upconv_fwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
     "spff_upconv_dgrad": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
     "spff_upconv_wgrad": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
+    "spff_spatial_attn_ws_bytes": (_S, [_I, _I, _I, _I, _I]),
+    "spff_spatial_attn_fwd": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
+    "spff_spatial_attn_bwd": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
     "spff_unet3d_set_sync_bn": (_I, [_P, _P, _I]),
     "spff_conv_prof_enable": (_I, [_I]),
     "spff_conv_prof_collect": (_I, [ctypes.POINTER(ctypes.c_double), _I]),
@@ -424,27 +428,32 @@ class Plan(_PlanBase):
     def __init__(self, batch, in_ch, depth, height, width, num_classes, base=32, ksd=3,
                  efilm=True, fgate=True, se=True, specse=True, device=None, math=None,
                  shard_world=1, shard_rank=0, memory=None, shard_axis=0, efilm_hidden=32,
-                 efilm_pe_dims=16, fgate_learn_phase=False):
+                 efilm_pe_dims=16, fgate_learn_phase=False, spatial=False, skip_gate=False):
         super().__init__(batch, in_ch, depth, height, width, num_classes, device, math,
                          base=base, ksd=ksd, efilm=efilm, fgate=fgate, se=se, specse=specse,
                          shard=(int(shard_world), int(shard_rank), int(shard_axis)),
                          memory=memory, efilm_hidden=efilm_hidden, efilm_pe_dims=efilm_pe_dims,
-                         fgate_learn_phase=fgate_learn_phase)
+                         fgate_learn_phase=fgate_learn_phase, spatial=spatial,
+                         skip_gate=skip_gate)
         self.key = (batch, in_ch, depth, height, width, num_classes, base, ksd, bool(efilm),
                     bool(fgate), bool(se), bool(specse), self.math, self.shard, self.memory,
-                    int(efilm_hidden), int(efilm_pe_dims), bool(fgate_learn_phase))
+                    int(efilm_hidden), int(efilm_pe_dims), bool(fgate_learn_phase),
+                    bool(spatial), bool(skip_gate))
 
     def _fill_cfg(self, cfg, base, ksd, efilm, fgate, se, specse, shard, memory, efilm_hidden,
-                  efilm_pe_dims, fgate_learn_phase):
+                  efilm_pe_dims, fgate_learn_phase, spatial=False, skip_gate=False):
         memory = default_memory() if memory is None else memory
         if memory not in MEMORY_MODES:
             raise SpffError(f"memory={memory!r}: expected one of {sorted(MEMORY_MODES)}")
         cfg.memory_mode = MEMORY_MODES[memory]
         self.memory = memory
+        # UNet3D_SpectralCore(use_spatial, use_skip_gate): unsharded, never the lean layout
+        cfg.use_spatial, cfg.use_skip_gate = int(bool(spatial)), int(bool(skip_gate))
+        attn = bool(spatial) or bool(skip_gate)
         # the layout the engine resolves (engine.hip build_plan: lean from 2^26 voxels on auto)
         voxels = cfg.batch * cfg.depth * cfg.height * cfg.width
-        self.layout = ("lean" if memory == "lean" or (memory == "auto" and voxels >= 1 << 26)
-                       else "full")
+        self.layout = ("lean" if memory == "lean" or
+                       (memory == "auto" and voxels >= 1 << 26 and not attn) else "full")
         # axis 0 = SPFF_SHARD_DEPTH (BASELINE config 4), 1 = SPFF_SHARD_HEIGHT (registry layout)
         cfg.shard_world, cfg.shard_rank, cfg.shard_axis = self.shard = shard
         cfg.base, cfg.ksd = base, ksd
@@ -640,7 +649,11 @@ class Plan(_PlanBase):
         check(lib().spff_debug_set(self._h, int(key), int(value)), "spff_debug_set")
 
     def saved(self, name: str) -> torch.Tensor:
-        """As _PlanBase.saved; uint8 for the max-pool argmax bytes "poolN.idx"."""
+        """As _PlanBase.saved; uint8 for the max-pool argmax bytes "poolN.idx", int32 for the
+        spatial attention's channel argmax "<stage>.sa.idx"."""
+        if name.endswith(".sa.idx"):
+            b, nv, ch = self._saved_view(name)
+            return b[:4 * nv * ch].view(torch.int32).view(nv, ch).clone()
         if name.endswith(".idx"):
             b, nv, ch = self._saved_view(name)
             return b[:nv * ch].view(nv, ch).clone()
@@ -766,7 +779,8 @@ def get_plan(owner=None, tag: str = "", **kw) -> Plan:
            bool(kw.get("fgate", True)), bool(kw.get("se", True)), bool(kw.get("specse", True)),
            kw.get("math") or default_math(), shard_key(kw.get("shard", (1, 0))),
            kw.get("memory") or default_memory(), int(kw.get("efilm_hidden", 32)),
-           int(kw.get("efilm_pe_dims", 16)), bool(kw.get("fgate_learn_phase", False)))
+           int(kw.get("efilm_pe_dims", 16)), bool(kw.get("fgate_learn_phase", False)),
+           bool(kw.get("spatial", False)), bool(kw.get("skip_gate", False)))
 
     def make():
         kk = dict(kw)
@@ -977,6 +991,64 @@ def resize3d_bwd(dy_cl: torch.Tensor, in_size) -> torch.Tensor:
     check(lib().spff_resize3d_bwd(_ptr(dy_cl), _ptr(dx), B, C, D, H, W, Do, Ho, Wo,
                                   _stream(dy_cl.device)), "spff_resize3d_bwd")
     return dx
+
+
+def _sa_rows(what: str, x_cl: torch.Tensor) -> Tuple[int, int, int, int, int]:
+    require_device(x_cl, what)
+    if x_cl.ndim != 5 or x_cl.dtype != torch.float32 or x_cl.shape[4] % 8 or not x_cl.numel():
+        raise SpffError(f"{what}: expected fp32 [B, D, H, W, C] with C a multiple of 8; got "
+                        f"{x_cl.dtype} {tuple(x_cl.shape)}")
+    return tuple(int(v) for v in x_cl.shape)
+
+
+def _sa_weight(what: str, w: torch.Tensor, device) -> torch.Tensor:
+    if tuple(w.shape) != (1, 2, 3, 7, 7) or w.dtype != torch.float32 or w.device != device:
+        raise SpffError(f"{what}: conv.weight must be fp32 [1, 2, 3, 7, 7] on {device}; got "
+                        f"{w.dtype} {tuple(w.shape)} on {w.device}")
+    return w.contiguous()
+
+
+def spatial_attn_fwd(x_cl: torch.Tensor, w: torch.Tensor):
+    """CBAM spatial attention (reference SpatialAttention3D) of channel-last fp32
+    x [B, D, H, W, C] with conv.weight w [1, 2, 3, 7, 7] -> (y = x * attn, attn [B, D, H, W],
+    map [B, D, H, W, 2] = (channel mean, channel max), idx [B, D, H, W] int32 = the lowest
+    channel that holds the max)."""
+    B, D, H, W, C = _sa_rows("spatial_attn_fwd", x_cl)
+    x_cl, dev = x_cl.contiguous(), x_cl.device
+    w = _sa_weight("spatial_attn_fwd", w, dev)
+    y = torch.empty_like(x_cl)
+    attn = torch.empty((B, D, H, W), dtype=torch.float32, device=dev)
+    amap = torch.empty((B, D, H, W, 2), dtype=torch.float32, device=dev)
+    idx = torch.empty((B, D, H, W), dtype=torch.int32, device=dev)
+    check(lib().spff_spatial_attn_fwd(_ptr(x_cl), _ptr(w), B, D, H, W, C, _ptr(y), _ptr(attn),
+                                      _ptr(amap), _ptr(idx), None, _stream(dev)),
+          "spff_spatial_attn_fwd")
+    return y, attn, amap, idx
+
+
+def spatial_attn_bwd(dy_cl: torch.Tensor, x_cl: torch.Tensor, w: torch.Tensor,
+                     attn: torch.Tensor, amap: torch.Tensor, idx: torch.Tensor):
+    """The backward of spatial_attn_fwd from what it returned: -> (dx like x, dw like w)."""
+    B, D, H, W, C = _sa_rows("spatial_attn_bwd", x_cl)
+    x_cl, dev = x_cl.contiguous(), x_cl.device
+    w = _sa_weight("spatial_attn_bwd", w, dev)
+    for what, t, shape, dt in (("dy", dy_cl, (B, D, H, W, C), torch.float32),
+                               ("attn", attn, (B, D, H, W), torch.float32),
+                               ("map", amap, (B, D, H, W, 2), torch.float32),
+                               ("idx", idx, (B, D, H, W), torch.int32)):
+        if tuple(t.shape) != shape or t.dtype != dt or t.device != dev:
+            raise SpffError(f"spatial_attn_bwd: {what} must be {dt} {shape} on {dev}; got "
+                            f"{t.dtype} {tuple(t.shape)} on {t.device}")
+    dy_cl, attn, amap, idx = dy_cl.contiguous(), attn.contiguous(), amap.contiguous(), \
+        idx.contiguous()
+    dx = torch.empty_like(x_cl)
+    dw = torch.empty_like(w)
+    ws = torch.empty(int(lib().spff_spatial_attn_ws_bytes(B, D, H, W, C)), dtype=torch.uint8,
+                     device=dev)
+    check(lib().spff_spatial_attn_bwd(_ptr(dy_cl), _ptr(x_cl), _ptr(w), _ptr(attn), _ptr(amap),
+                                      _ptr(idx), B, D, H, W, C, _ptr(dx), _ptr(dw), _ptr(ws),
+                                      _stream(dev)), "spff_spatial_attn_bwd")
+    return dx, dw
 
 
 class R2UPlan(_PlanBase):

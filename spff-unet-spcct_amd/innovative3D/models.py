@@ -132,6 +132,36 @@ class _SpectralSE(nn.Module):
     pass
 
 
+class SpatialAttention3D(nn.Module):
+    """CBAM-style spatial attention (models.py:434-446): parameter container; the engine
+    runs mean / max over the channels, the 2 -> 1 channel stencil, the sigmoid and the
+    product."""
+
+    def __init__(self, kernel_size=(3, 7, 7)):
+        super().__init__()
+        if tuple(kernel_size) != (3, 7, 7):
+            raise NotImplementedError("SpatialAttention3D: the engine's stencil is (3, 7, 7)")
+        self.conv = nn.Conv3d(2, 1, kernel_size=(3, 7, 7), padding=(1, 3, 3), bias=False)
+        self.sigmoid = nn.Sigmoid()
+
+
+class AttentionGate(nn.Module):
+    """3D attention gate for skip connections (models.py:627-640): parameter container.
+    forward(x_skip, g) = x_skip * sigmoid(psi(relu(W_x x_skip + W_g g))): the gate multiplies
+    its first argument."""
+
+    def __init__(self, F_skip, F_g, F_int=None):
+        super().__init__()
+        if F_int is None:
+            F_int = min(F_skip, F_g)
+        self.W_x = nn.Conv3d(F_skip, F_int, 1, 1, 0, bias=True)
+        self.W_g = nn.Conv3d(F_g, F_int, 1, 1, 0, bias=True)
+        self.psi = nn.Conv3d(F_int, 1, 1, 1, 0, bias=True)
+        nn.init.constant_(self.psi.bias, 0.0)
+        self.relu = nn.ReLU(inplace=True)
+        self.sigmoid = nn.Sigmoid()
+
+
 class _DoubleConvSpectral(nn.Module):
     def __init__(self, cin, cout, ksd=1, norm="instance", act="lrelu"):
         super().__init__()
@@ -289,13 +319,11 @@ class UNet3D_SpectralCore(_FlatParamMixin, nn.Module):
                  use_specse=False, use_spatial=False, use_skip_gate=False, norm="instance",
                  act="lrelu"):
         super().__init__()
-        if use_spatial or use_skip_gate:
-            raise NotImplementedError("use_spatial/use_skip_gate are off on every SPCT registry "
-                                      "entry (config.py:417-418) and not on the engine path")
         f = int(base)
         P = (1, 2, 2)
         self.in_channels, self.num_classes, self.base, self.ksd = int(in_channels), int(num_classes), f, int(ksd)
         self.use_se, self.use_specse = bool(use_se), bool(use_specse)
+        self.use_spatial, self.use_skip_gate = bool(use_spatial), bool(use_skip_gate)
         self.enc1 = _DoubleConvSpectral(in_channels, f, ksd, norm, act)
         self.pool1 = nn.MaxPool3d(P)
         self.enc2 = _DoubleConvSpectral(f, 2 * f, ksd, norm, act)
@@ -312,8 +340,13 @@ class UNet3D_SpectralCore(_FlatParamMixin, nn.Module):
         self.out = nn.Conv3d(f, num_classes, 1)
         self.se = nn.ModuleList([_SEChannelLite(c) if use_se else nn.Identity() for c in (f, 2 * f, 4 * f, 8 * f)])
         self.sp = nn.ModuleList([_SpectralSE() if use_specse else nn.Identity() for _ in range(4)])
-        self.sa = nn.ModuleList([nn.Identity() for _ in range(4)])
-        self.g3 = self.g2 = self.g1 = None
+        self.sa = nn.ModuleList([SpatialAttention3D() if use_spatial else nn.Identity()
+                                 for _ in range(4)])
+        # gated skips: the SPCT core's gates are the base AttentionGate called as
+        # (g_c, x_c, inter_c) -> (F_skip = x_c, F_g = g_c, F_int) (models.py:642-645)
+        self.g3 = AttentionGate(4 * f, 4 * f, 2 * f) if use_skip_gate else None
+        self.g2 = AttentionGate(2 * f, 2 * f, f) if use_skip_gate else None
+        self.g1 = AttentionGate(f, f, f // 2) if use_skip_gate else None
         self._plan = None
         self._flat = None
         self._infer_plan = None
@@ -356,6 +389,16 @@ class UNet3D_SpectralCore(_FlatParamMixin, nn.Module):
         # depth D * world (axis 0), or its H-slab of a volume of height H * world
         # (axis 1, the registry layout); the FourierGate acts on the full depth
         shard = E.shard_key(getattr(self, "shard", (1, 0)))
+        if self.use_spatial or self.use_skip_gate:  # before any device call
+            if shard[0] > 1:
+                raise E.SpffError("use_spatial / use_skip_gate run on unsharded modules only: the "
+                                  "3x7x7 stencil needs halos the shard collectives do not carry")
+            if getattr(self, "memory", None) == "lean":
+                raise E.SpffError("use_spatial / use_skip_gate: the lean layout does not "
+                                  "recompute them; use memory 'full' or 'auto'")
+            if self.use_skip_gate and (H % 8 or W % 8):
+                raise E.SpffError("use_skip_gate needs H and W multiples of 8: the reference's "
+                                  "gate fails where an up-conv output and its skip differ")
         if fgate:
             for b in self._blocks():
                 b.fgate._ensure_mask(D * (shard[0] if shard[2] == 0 else 1), x.device)
@@ -363,7 +406,8 @@ class UNet3D_SpectralCore(_FlatParamMixin, nn.Module):
                           num_classes=self.num_classes, base=self.base, ksd=self.ksd,
                           efilm=efilm, fgate=fgate, se=self.use_se, specse=self.use_specse,
                           device=x.device, math=getattr(self, "math", None), shard=shard,
-                          memory=getattr(self, "memory", None),
+                          memory=getattr(self, "memory", None), spatial=self.use_spatial,
+                          skip_gate=self.use_skip_gate,
                           owner=self, tag=tag, **self._gate_settings())
         if shard[0] > 1:
             coll = getattr(self, "shard_coll", None)
