@@ -2,7 +2,7 @@
 """Build a variant of libspff_hip.so with extra compile flags (kernel tuning
 experiments), e.g.
 
-    python scripts/build_variant.py variants/libspff_iglp0.so -DSPFF_XIGLP=0
+    python scripts/build_variant.py variants/libspff_xstamp.so -DSPFF_XSTAMP=1
 
 Select it at run time with SPFF_LIB=<path> (innovative3D._engine.lib_path)."""
 import concurrent.futures as cf

@@ -75,7 +75,6 @@ __device__ __forceinline__ float exp2i(int e) { return __uint_as_float((unsigned
 typedef __bf16 spff_bf16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 spff_f16x8 __attribute__((ext_vector_type(8)));
 typedef float spff_f32x4 __attribute__((ext_vector_type(4)));
-typedef float spff_f32x16 __attribute__((ext_vector_type(16)));
 template <bool HF>
 __device__ __forceinline__ spff_f32x4 mfma16x32(spff_bf16x8 a, spff_bf16x8 b, spff_f32x4 c) {
   if constexpr (HF)
@@ -83,14 +82,6 @@ __device__ __forceinline__ spff_f32x4 mfma16x32(spff_bf16x8 a, spff_bf16x8 b, sp
                                                   __builtin_bit_cast(spff_f16x8, b), c, 0, 0, 0);
   else
     return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-template <bool HF>
-__device__ __forceinline__ spff_f32x16 mfma32x16(spff_bf16x8 a, spff_bf16x8 b, spff_f32x16 c) {
-  if constexpr (HF)
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(spff_f16x8, a),
-                                                  __builtin_bit_cast(spff_f16x8, b), c, 0, 0, 0);
-  else
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
 }
 
 // float4 -> NS planes of 4 bf16 (x: values 0,1; y: values 2,3); NS_F16: 2 fp16 planes

@@ -14,17 +14,27 @@
 // MFMA (an fp32 fma chain).  math = SPFF_MATH_BF16X3 keeps only h, l
 // (x = h + l, |err| <= 2^-17) and hh, hl, lh: 2x faster, ~1e-5 relative.
 //
-// Structure (gfx950, 8 waves = 512 threads, one workgroup per CU):
-//  * output tile 2 x 16 x 16 = 512 voxels x BN out channels; MFMA
-//    v_mfma_f32_32x32x16_bf16, rows = voxels, cols = out channels,
-//    k = (tap parity, 8 input channels): per input-channel chunk of 8 the 27
-//    taps are walked as 14 tap pairs (lane half h takes tap 2j+h; tap 27 is a
-//    zero weight row).
+// Structure (gfx950):
+//  * MFMA v_mfma_f32_16x16x32_bf16 (f16x3: _f16), rows = voxels, cols = out
+//    channels, k = (4 lane groups, 8 input channels): per input-channel chunk of
+//    8 the taps are walked as tap quads, lane group g at its own tap (x_quads:
+//    7 quads for the 27 taps of KD = 3, 3 for the 9 of KD = 1; spare slots take
+//    the zero weight row).  A 16-row block is one W-row of 16 voxels; a wave
+//    owns 2 MB row blocks x BN / 16 column blocks, a workgroup of NW waves a
+//    tile of TD x TH x 16 voxels, TD TH = 2 NW MB.
+//  * tiles per BN (xt_td / xt_mb / xt_nw):
+//      BN 64, bf16x6 / bf16x3: 2 x 16 x 16, 8 waves, one workgroup per CU;
+//      BN 64, f16x3:           2 x 8 x 16, 4 waves, two workgroups per CU;
+//      BN 32, bf16x6 / bf16x3: 2 x 8 x 16, 4 waves, two workgroups per CU;
+//      BN 32, f16x3:           4 x 8 x 16, 4 waves, two workgroups per CU
+//                              (D mod 4 = 1 or 2: 2 x 8 x 16, three per CU);
+//      BN 16 (Cout <= 16):     2 x 8 x 16, 4 waves, two workgroups per CU
+//                              (f16x3: three).
+//    With two or three workgroups on a CU one's chunk-boundary staging overlaps
+//    the others' MFMAs.
 //  * LDS: halo [plane][pos][8ch] and weight slab [plane][tap][co][8ch], 16-byte
-//    units read with ds_read_b128.  Lanes of one ds_read_b128 group must hit
-//    distinct pos mod 16: a 32-row block covers two W-rows of 16 voxels and the
-//    second row is rotated by 2 (tw = (r + 14) mod 16), which cancels the halo
-//    row pitch 18 = 2 mod 16 -- conflict-free without padding.
+//    units read with ds_read_b128, conflict-free without padding by the row ->
+//    voxel mapping and the tap pairing described at x_quads.
 //  * sign-alternating accumulation.  The bf16 MFMA adds products much smaller
 //    than its fp32 accumulator (the hm / mh / hl / lh / mm terms) with a bias
 //    toward -infinity of a few thousandths of an ulp per instruction (measured:
@@ -43,109 +53,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
-#include <type_traits>
 #include <vector>
-
-#ifndef SPFF_XDIAG
-#define SPFF_XDIAG 0  // timing diagnostics only: 1 = no restaging, 2 = no MFMA loop,
-                      // 3 = halo restaged but weights staged once, 4 = weights restaged,
-                      // halo staged once (results wrong: kernel timing only)
-#endif
-#ifndef SPFF_XCDMAP
-#define SPFF_XCDMAP 1  // 0: tile-fastest block order (A/B diagnostics)
-#endif
-#ifndef SPFF_XDFAST
-#define SPFF_XDFAST 1  // 1: tiles depth-fastest (per batch sample), 0: W-fastest
-#endif
-#ifndef SPFF_X32T
-// 1: 32-wide tiles are 4 x 16 x 16 voxels (MB 4), 0: 2 x 16 x 16 (MB 2).  Measured (with the
-// depth-fastest order): 4-deep tiles -0.45 ms/step, but the 32-wide launches read 1.42 -> 2.35 GB
-#define SPFF_X32T 0
-#endif
-#ifndef SPFF_X16
-#define SPFF_X16 1  // 1: v_mfma_f32_16x16x32_bf16 tap-quad schedule, 0: 32x32x16 tap pairs
-#endif
-#ifndef SPFF_X32NW
-// waves per 32-wide workgroup: 4 (default since round 3: a 2 x 8 x 16 tile in 78 KB of
-// LDS, two workgroups per CU, so one's chunk-boundary staging overlaps the other's MFMAs
-// -- the level-0 launches 6-8 % faster, -0.46 ms/step A/B) or 8 (one 2 x 16 x 16 tile,
-// one workgroup per CU).  The 4-wave tiles change only the fused statistics' per-tile
-// summation order; the round-2 sharded-test failure that held them back was a LeakyReLU
-// input on its kink taking the other slope (an engine-vs-engine comparison without
-// branch consistency), and both variants agree with the branch-consistent fp64 oracle
-// (profiles/r02/ab_x32nw_branch_consistent.log; tests/test_gpu_sharded.py now judges that way)
-#define SPFF_X32NW 4
-#endif
-#ifndef SPFF_X64NW
-// waves per 64-wide f16x3 workgroup: 4 (a 2 x 8 x 16 tile in 80 KB of LDS -- two fp16 planes
-// leave room for two workgroups per CU, as the 32-wide tiles) or 8 (one 2 x 16 x 16 tile)
-#define SPFF_X64NW 4
-#endif
-#ifndef SPFF_X32D4
-// 32-wide f16x3 tiles 4 x 8 x 16 voxels (4 waves x 8 row blocks, 75 KB, two workgroups per
-// CU) instead of 2 x 8 x 16: 2.1 instead of 2.8 staged halo positions per output voxel
-#define SPFF_X32D4 1
-#endif
-#ifndef SPFF_X32WG
-// workgroups per CU the 16/32-wide f16x3 kernels are compiled for (their 52 KB image
-// allows 3; 3 caps them at 168 VGPRs)
-#define SPFF_X32WG 3
-#endif
-#ifndef SPFF_XSCALE_LATE
-// f16x3 per-(tile, chunk) input scale: 1 = each wave publishes its max of the next chunk's
-// halo late in the current chunk and the halo is split after the chunk-boundary barrier;
-// 0 = a workgroup barrier in the middle of the chunk, the split beside the MFMAs
-#define SPFF_XSCALE_LATE 0
-#endif
-#ifndef SPFF_XSCALEJ
-// (SPFF_XSCALE_LATE 0) the k-step of the chunk at which the workgroup takes the next
-// chunk's max and starts splitting its halo; -1 = the middle (NJ / 2)
-#define SPFF_XSCALEJ -1
-#endif
-#ifndef SPFF_XIGLP
-#define SPFF_XIGLP -1
-#endif
-#ifndef SPFF_XPRIO
-#define SPFF_XPRIO 1
-#endif
-#ifndef SPFF_XFPIN
-// 1: the next chunk's halo loads (and the fused activation's coefficients) are issued right
-// after the chunk-boundary barrier, pinned there by a scheduling barrier.  Without it the
-// compiler sank them to the last k-step before the mid-chunk scale barrier (ISA: the loads
-// at MFMA 100-144 of the 144 before the vmcnt waits), so every wave waited out their whole
-// latency at that barrier
-#define SPFF_XFPIN 1
-#endif
-#ifndef SPFF_XPIPE
-// 1: the 16/32-wide X16 k-loop is software-pipelined by one row block: the A fragments of
-// row block rb + 1 (and, at the last row block, the next quad's B fragments and first A
-// fragments) are read from LDS before row block rb's MFMAs, kept in that order by
-// scheduling-group barriers.  Without it the compiler read each A fragment two MFMAs
-// (32 cycles) before its use and waited lgkmcnt(0) there, i.e. most of the LDS latency
-// exposed at every row block
-#define SPFF_XPIPE 1
-#endif
-#ifndef SPFF_XPIPE64
-#define SPFF_XPIPE64 1  // the XPIPE row-block pipeline in the 64-wide tiles too (A/B 35.53 -> 35.40; 0: 32-wide only)
-#endif
-#ifndef SPFF_XEARLYW
-// 1: the first chunk's weight DMA is issued at the kernel start, before the first halo
-// fetch, so its L2 latency overlaps the halo's HBM latency instead of following it at the
-// first chunk-boundary barrier (in-kernel stamps: prologue 9-13 us per tile, of which
-// 1-1.5 us that barrier and ~0.7 us the DMA issue)
-#define SPFF_XEARLYW 1
-#endif
-#ifndef SPFF_XSTORE
-// 1: the output tile goes through LDS (conflict-free [row][BN + 4] image in MFMA row order)
-// and leaves as 16-byte row stores, instead of one 4-byte store per accumulator element
-#define SPFF_XSTORE 1
-#endif
-
-#ifndef SPFF_XBSTAT
-// 1: the input-gradient conv into da1 also forms the IN-backward sums of its output in the
-// epilogue (BStat), replacing a RED_BWD_IN slab_reduce pass (0: that pass, A/B)
-#define SPFF_XBSTAT 1
-#endif
 
 #ifndef SPFF_XSTAMP
 // timing diagnostics only (variant builds): per workgroup of k_conv3d_fwd_x, s_memtime at
@@ -160,7 +68,6 @@ constexpr int XSTAMP_N = 1 << 15, XSTAMP_W = 16;
 __device__ unsigned long long g_xstamp[XSTAMP_N * XSTAMP_W];
 #endif
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
@@ -182,7 +89,7 @@ __device__ __forceinline__ void split_bf16(float x, unsigned short (&o)[NS]) {
   }
 }
 
-// 16x16x32 tap-quad schedule (X16): k = 4 lane groups x 8 channels, lane group g
+// 16x16x32 tap-quad schedule: k = 4 lane groups x 8 channels, lane group g
 // at its own tap.  A ds_read_b128 lane group mixes rows {0-3, 12-15} of k-group
 // 0 (2) with rows 4-11 of k-group 1 (3): with the rows of a block mapped to the
 // W-row's voxels as rows 4-11 -> even w, the rest -> odd w, every such group
@@ -298,9 +205,9 @@ __global__ __launch_bounds__(256) void k_conv_pack_many(PackJobs J) {
 
 // ------------------------------------------------------------ fwd / dgrad --
 namespace {
-constexpr int XT_D = 2, XT_H = 16, XT_W = 16, XT_THREADS = 512;
-// NW waves x MB 32-row blocks per wave: tile TD x TH x 16 voxels with TD TH = 2 NW MB
-// (TD = 2 except the 32-wide 16x16x32 tiles, SPFF_X32T: 4 x 16 x 16)
+constexpr int XT_D = 2, XT_H = 16, XT_W = 16;
+// NW waves x 2 MB 16-row blocks per wave: tile TD x TH x 16 voxels with TD TH = 2 NW MB
+// (TD = 2 except the 32-wide f16x3 tiles, xt_d4: 4 x 8 x 16)
 template <int KD, int TD, int TH>
 __host__ __device__ constexpr int xt_npos() {
   return (TD + KD - 1) * (TH + 2) * (XT_W + 2);
@@ -314,26 +221,32 @@ constexpr size_t xt_lds_bytes() {
   // operand images; the epilogue reuses the space for the output tile [TD TH 16][BN + 4]
   // fp32 plus the fused statistics' two [NW][BN] partial-sum tables
   const size_t ops = (size_t)nplanes(NS) * (xt_npos<KD, TD, TH>() + xt_t2<KD>() * BN) * 16;
-  const size_t out = SPFF_XSTORE ? (size_t)TD * TH * 16 * (BN + 4) * 4 + 16 * BN * 4 : 0;
+  const size_t out = (size_t)TD * TH * 16 * (BN + 4) * 4 + 16 * BN * 4;
   return ops > out ? ops : out;
 }
+// waves per 16/32-wide workgroup: a 2 x 8 x 16 tile in 78 KB of LDS, two workgroups per CU,
+// so one's chunk-boundary staging overlaps the other's MFMAs -- the level-0 launches 6-8 %
+// faster than one 8-wave 2 x 16 x 16 tile per CU, -0.46 ms/step A/B.  The 4-wave tiles
+// change only the fused statistics' per-tile summation order; both tile shapes agree with
+// the branch-consistent fp64 oracle (profiles/r02/ab_x32nw_branch_consistent.log, the way
+// tests/test_gpu_sharded.py judges)
+constexpr int X32NW = 4;
+// waves per 64-wide f16x3 workgroup: a 2 x 8 x 16 tile in 80 KB of LDS -- two fp16 planes
+// leave room for two workgroups per CU, as the 32-wide tiles
+constexpr int X64NW = 4;
+// workgroups per CU the 2-deep 16/32-wide f16x3 kernels are compiled for (their 52 KB image
+// allows 3; 3 caps them at 168 VGPRs)
+constexpr int X32WG = 3;
+// 32-wide f16x3 tiles are 4 x 8 x 16 voxels (4 waves x 8 row blocks, 75 KB, two workgroups
+// per CU) instead of 2 x 8 x 16: 2.1 instead of 2.8 staged halo positions per output voxel
+constexpr bool xt_d4(int BN, int NS) { return BN == 32 && NS == NS_F16; }
 // tile depth of a BN-wide launch (host side: launches, fused-statistics layout)
-constexpr bool xt_d4(int BN, int NS) {
-  return BN == 32 && NS == NS_F16 && SPFF_X16 && SPFF_X32D4 && !SPFF_X32T;
-}
-constexpr int xt_td(int BN, int NS) {
-  return ((BN == 32 && SPFF_X16 && SPFF_X32T) || xt_d4(BN, NS)) ? 4 : XT_D;
-}
-constexpr int xt_mb(int BN, int NS) {
-  return ((BN == 32 && SPFF_X16 && SPFF_X32T) || xt_d4(BN, NS)) ? 4 : 2;
-}
-// waves of a BN-wide workgroup (4-wave 32-wide tiles: SPFF_X32NW, 2-deep tiles only)
+constexpr int xt_td(int BN, int NS) { return xt_d4(BN, NS) ? 4 : XT_D; }
+constexpr int xt_mb(int BN, int NS) { return xt_d4(BN, NS) ? 4 : 2; }
+// waves of a BN-wide workgroup
 // (16-wide tiles, Cout <= 16 -- the SwinUNETR's C = 12 convs: also 4 waves, 2 WGs / CU)
-// (64-wide f16x3 tiles: SPFF_X64NW)
 constexpr int xt_nw(int BN, int NS) {
-  return (BN <= 32 && SPFF_X16 && !(BN == 32 && SPFF_X32T)) ? SPFF_X32NW
-         : (BN == 64 && NS == NS_F16 && SPFF_X16)             ? SPFF_X64NW
-                                                                : 8;
+  return BN <= 32 ? X32NW : (BN == 64 && NS == NS_F16) ? X64NW : 8;
 }
 }  // namespace
 // template plane count of a math mode
@@ -352,8 +265,8 @@ __device__ __forceinline__ int x16_w(int r) {
 // HR: height-sharded input -- stencil rows h = -1 / h = H read the neighbours' boundary
 // rows (Src2::rlo / rhi; zero where null) instead of zero padding (hshard.hip).  A
 // separate instantiation, so the unsharded kernels' register budget is unchanged.
-template <int BN, int KD, int NS, int MB, int NW, bool X16, int TD, bool HR>
-__global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : (BN <= 32 && NS == NS_F16 && TD == 2 ? SPFF_X32WG : 2)) void k_conv3d_fwd_x(
+template <int BN, int KD, int NS, int MB, int NW, int TD, bool HR>
+__global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : (BN <= 32 && NS == NS_F16 && TD == 2 ? X32WG : 2)) void k_conv3d_fwd_x(
     Src2 x, const uint4* __restrict__ wp, Dst2 y, Vol vol, int Cin, int nkc, int Cout, int npad,
     int tilesD, int tilesH, int tilesW, float* __restrict__ part, int kps,
     float* __restrict__ stats, int ntiles, int td0, int tds, int th0, int ths,
@@ -371,29 +284,27 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : (BN <= 32 && NS == NS_F16 &&
   // planes per operand; HF: two fp16 planes of the scaled operands (NS_F16, bf16split.h)
   constexpr int NP = nplanes(NS);
   constexpr bool HF = NS == NS_F16;
-  constexpr int TH = X16 ? 2 * NW * MB / TD : NW * MB, TW = XT_W;
-  static_assert(X16 || TD == 2, "32x32x16 schedule: 2-deep tiles");
+  constexpr int TH = 2 * NW * MB / TD, TW = XT_W;
   constexpr int HH = TH + 2, HWD = TW + 2;
   constexpr int NPOS = xt_npos<KD, TD, TH>();
-  constexpr int T = KD * 9, T2 = xt_t2<KD>();
-  // MFMA blocking: 32x32x16 -- MB 32-row blocks x BN/32 col blocks per wave, a k-step
-  // per tap pair; 16x16x32 -- 2 MB 16-row blocks x BN/16, a k-step per tap quad
-  constexpr int RB = X16 ? 2 * MB : MB, CB = X16 ? BN / 16 : BN / 32;
-  constexpr int NCOL = X16 ? 16 : 32, NREG = X16 ? 4 : 16;
+  constexpr int T2 = xt_t2<KD>();
+  // MFMA blocking (16x16x32): 2 MB 16-row blocks x BN/16 col blocks per wave, a k-step per
+  // tap quad
+  constexpr int RB = 2 * MB, CB = BN / 16;
+  constexpr int NCOL = 16, NREG = 4;
   constexpr XQuads<KD> QT = x_quads<KD>();
-  constexpr int NJ = X16 ? QT.nq : T2 / 2;
-  using AccT = typename std::conditional<X16, f32x4, f32x16>::type;
+  constexpr int NJ = QT.nq;
   constexpr int NHX = NPOS * 2;  // halo float4 per chunk (8 channels = 2 float4)
   constexpr int RH = (NHX + XT_THREADS - 1) / XT_THREADS;
   constexpr int NWU = NP * T2 * BN;  // pre-split weight units (16 B) per chunk
   static_assert(NWU % 64 == 0, "weight image must be whole 1 KiB DMA pieces");
-  static_assert(!X16 || TD * TH == NW * RB, "X16: one W-row per 16-row block");
+  static_assert(TD * TH == NW * RB, "one W-row per 16-row block");
   // the epilogue's two fused-statistics tables [NW][CB][NCOL] (= NW BN floats each) live in
   // the 16 BN floats xt_lds_bytes reserves beside the output tile
   static_assert(NW <= 8, "fused-statistics tables: at most 8 waves");
   // the k-step from which the next chunk's halo is split (HF: after its block max), and the
   // halo float4 split per k-step from there on
-  constexpr int J0 = (NS == NS_F16 && SPFF_XSCALEJ >= 0 && SPFF_XSCALEJ < NJ) ? SPFF_XSCALEJ : NJ / 2;
+  constexpr int J0 = NJ / 2;
   constexpr int SPJ = (RH + (NJ - J0) - 1) / (NJ - J0);
   constexpr int NPC = NWU / 64;
   extern __shared__ uint4 lds4[];
@@ -414,8 +325,7 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : (BN <= 32 && NS == NS_F16 &&
 
   const int tid = threadIdx.x;
   const int lane = tid & 63, wave = tid >> 6;
-  const int khalf = lane >> 5, l32 = lane & 31, kg = lane >> 4, l16 = lane & 15;
-  const int lcol = X16 ? l16 : l32;
+  const int kg = lane >> 4, l16 = lane & 15;
   // XCD-aware order: blocks b and b + 8 share an XCD (and its L2), so XCD group
   // b % 8 walks a contiguous run of tiles, the npad / BN output-channel blocks of a
   // tile back to back -- neighbouring tiles' halos and a tile's input for its other
@@ -423,22 +333,16 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : (BN <= 32 && NS == NS_F16 &&
   const int nnb = npad / BN;
   const int per = (ntiles + 7) >> 3;
   const int grp = blockIdx.x & 7, rk = blockIdx.x >> 3;
-  const int tile = SPFF_XCDMAP ? grp * per + rk / nnb : (int)(blockIdx.x % (8 * per));
-  const int nbk = SPFF_XCDMAP ? rk % nnb : (int)(blockIdx.x / (8 * per));
+  const int tile = grp * per + rk / nnb;
+  const int nbk = rk % nnb;
   if (tile >= ntiles) return;  // padding block (uniform: the whole workgroup)
   int t = tile;
   int twi, thi, tdi;
-  if (SPFF_XDFAST) {
-    // depth-fastest: the ~32 tiles an XCD runs at once are D-neighbours, whose halos
-    // share KD - 1 planes -- those are L2 hits instead of a later HBM re-read
-    tdi = t % tilesD; t /= tilesD;
-    twi = t % tilesW; t /= tilesW;
-    thi = t % tilesH; t /= tilesH;
-  } else {
-    twi = t % tilesW; t /= tilesW;
-    thi = t % tilesH; t /= tilesH;
-    tdi = t % tilesD; t /= tilesD;
-  }
+  // depth-fastest: the ~32 tiles an XCD runs at once are D-neighbours, whose halos
+  // share KD - 1 planes -- those are L2 hits instead of a later HBM re-read
+  tdi = t % tilesD; t /= tilesD;
+  twi = t % tilesW; t /= tilesW;
+  thi = t % tilesH; t /= tilesH;
   const int b = t;
   tdi = td0 + tdi * tds;  // depth-tile subset (sharded halo overlap): td0 + k tds, k < tilesD
   if constexpr (HR) thi = th0 + thi * ths;  // H-tile subset (height-sharded overlap)
@@ -449,29 +353,21 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : (BN <= 32 && NS == NS_F16 &&
 
   // voxel of MFMA row r in row block q (q = wave*RB + rb)
   auto vrow = [](int q, int r, int& td, int& th, int& tw) {
-    if constexpr (X16) {
-      td = q / TH;
-      th = q % TH;
-      tw = x16_w(r);
-    } else {
-      td = q / (TH / 2);
-      th = 2 * (q % (TH / 2)) + (r >> 4);
-      tw = r < 16 ? r : ((r + 14) & 15);
-    }
+    td = q / TH;
+    th = q % TH;
+    tw = x16_w(r);
   };
   // output register r of this lane -> MFMA row
-  auto orow = [&](int r) {
-    return X16 ? 4 * kg + r : (r & 3) + 8 * (r >> 2) + 4 * khalf;
-  };
+  auto orow = [&](int r) { return 4 * kg + r; };
   int hpos[RB];
 #pragma unroll
   for (int rb = 0; rb < RB; ++rb) {
     int td, th, tw;
-    vrow(wave * RB + rb, X16 ? l16 : l32, td, th, tw);
+    vrow(wave * RB + rb, l16, td, th, tw);
     hpos[rb] = (td * HH + th) * HWD + tw;
   }
 
-  AccT acc[RB][CB];
+  f32x4 acc[RB][CB];
 #pragma unroll
   for (int rb = 0; rb < RB; ++rb)
 #pragma unroll
@@ -507,26 +403,11 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : (BN <= 32 && NS == NS_F16 &&
       pok |= ok ? (1u << k) : 0u;
     }
   }
-  // the chunk's 8 (al, de) pairs of the fused input activation, loaded once per chunk from
-  // uniform addresses (scalar loads) and selected per lane: a thread's 4 channels are the
-  // lower or upper half (XT_THREADS is even: q = tid & 1 for all k).  Loaded per halo float4
-  // they became 9 dependent vector-memory round trips, each behind a vmcnt(0)
-  auto act_coef_kc = [&](int kc, float (&a)[4], float (&e)[4]) {
-    const int64_t o = __builtin_amdgcn_readfirstlane((int)((int64_t)b * x.ld0 + kc * 8));
-    const float* ap = x.al + o;
-    const float* dp = x.de + o;
-    const bool hi = tid & 1;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const float alo = ap[j], ahi = ap[4 + j], elo = dp[j], ehi = dp[4 + j];
-      a[j] = hi ? ahi : alo;
-      e[j] = hi ? ehi : elo;
-    }
-  };
-  // (SPFF_XFPIN, HF 32-wide tiles) every chunk's coefficients staged in LDS once per tile
-  // (float4 q = the 4 channels 4q..4q+3): prep_max reads them there instead of issuing global
-  // loads of its own (which the scale barrier then waited for, or -- preloaded into registers
-  // with the halo -- which the register allocator waited for at the chunk start)
+  // (HF 32-wide tiles) every chunk's (al, de) pairs of the fused input activation staged in
+  // LDS once per tile (float4 q = the 4 channels 4q..4q+3): prep_max reads them there instead
+  // of issuing global loads of its own (which the scale barrier then waited for, or --
+  // preloaded into registers with the halo -- which the register allocator waited for at the
+  // chunk start)
   constexpr int XCF = 32;  // float4s per table: channels < 128 (launch_fwd_x checks)
   __shared__ float4 scf[2][XCF];
   // live = false: a dummy fetch (every quad invalid, loads from clamped addresses) after the
@@ -593,13 +474,9 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : (BN <= 32 && NS == NS_F16 &&
     float m = 0.f;
     float ca[4] = {1.f, 1.f, 1.f, 1.f}, ce[4] = {0.f, 0.f, 0.f, 0.f};
     if constexpr (BN == 32) if (x.al) {
-      if constexpr (HF && SPFF_XFPIN) {
-        const float4 fa = scf[0][2 * fkc + (tid & 1)], fe = scf[1][2 * fkc + (tid & 1)];
-        ca[0] = fa.x; ca[1] = fa.y; ca[2] = fa.z; ca[3] = fa.w;
-        ce[0] = fe.x; ce[1] = fe.y; ce[2] = fe.z; ce[3] = fe.w;
-      } else {
-        act_coef_kc(fkc, ca, ce);
-      }
+      const float4 fa = scf[0][2 * fkc + (tid & 1)], fe = scf[1][2 * fkc + (tid & 1)];
+      ca[0] = fa.x; ca[1] = fa.y; ca[2] = fa.z; ca[3] = fa.w;
+      ce[0] = fe.x; ce[1] = fe.y; ce[2] = fe.z; ce[3] = fe.w;
     }
 #pragma unroll
     for (int k = 0; k < RH; ++k) {
@@ -668,7 +545,6 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : (BN <= 32 && NS == NS_F16 &&
       // packed pair split (bf16split.h): -0.5 to -3 % on the 16/32-wide launches; the
       // 64-wide kernel (255 VGPRs) measured +1 to +3 % with it and keeps the per-value form
       if (!ok) v = make_float4(0.f, 0.f, 0.f, 0.f);
-      if constexpr (HF) v = make_float4(v.x * sx, v.y * sx, v.z * sx, v.w * sx);
       split4_pk<NS>(v, hs[k]);
     } else {
       unsigned short s0[NS], s1[NS], s2[NS], s3[NS];
@@ -683,20 +559,11 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : (BN <= 32 && NS == NS_F16 &&
       }
     }
   };
-  // store halo float4 k's planes (hs[k]) into the LDS image
-  auto store_one = [&](int k) {
-    const int i = tid + XT_THREADS * k;
-    if (i < NHX) {
-#pragma unroll
-      for (int p = 0; p < NP; ++p)
-        reinterpret_cast<uint2*>(Xs + p * NPOS + (i >> 1))[i & 1] = hs[k][p];
-    }
-  };
-  auto stash = [&](int kc, bool first, bool halo = true, bool wts = true) {
+  // the halo planes (hs) into the LDS image, and the chunk's weight slab
+  auto stash = [&](int kc, bool halo, bool wts) {
 #pragma unroll
     for (int k = 0; k < RH; ++k) {
       if (!halo) break;
-      if (SPFF_XDIAG == 4 && !first) break;
       const int i = tid + XT_THREADS * k;
       if (i < NHX) {
 #pragma unroll
@@ -710,7 +577,6 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : (BN <= 32 && NS == NS_F16 &&
 #pragma unroll
     for (int k = 0; k < (NPC + NW - 1) / NW; ++k) {
       if (!wts) break;
-      if (SPFF_XDIAG == 3 && !first) break;
       const int pc = wave + k * NW;
       if (k * NW + NW <= NPC || pc < NPC)
         __builtin_amdgcn_global_load_lds((const void*)(src + pc * 64),
@@ -724,11 +590,14 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : (BN <= 32 && NS == NS_F16 &&
   // writes fp32 partial sums that k_splitk_reduce adds in a fixed order
   const int kc0 = part ? blockIdx.z * kps : 0;
   const int kc1 = part ? min(nkc, kc0 + kps) : nkc;
-  // (SPFF_XEARLYW) the first chunk's weights first: the Ws image is free at the start
-  if constexpr (SPFF_XEARLYW) stash(kc0, true, false, true);
+  // the first chunk's weight DMA first, before the first halo fetch (the Ws image is free at
+  // the start): its L2 latency overlaps the halo's HBM latency instead of following it at the
+  // first chunk-boundary barrier (in-kernel stamps: prologue 9-13 us per tile, of which
+  // 1-1.5 us that barrier and ~0.7 us the DMA issue)
+  stash(kc0, false, true);
   fetch(kc0);
   // (after the halo loads are in flight: these loads overlap them)
-  if constexpr (BN == 32 && HF && SPFF_XFPIN) if (x.al) {
+  if constexpr (BN == 32 && HF) if (x.al) {
     for (int i = tid; i < 2 * XCF; i += XT_THREADS) {
       const int q = i % XCF, t = i / XCF;
       float4 v = make_float4(t ? 0.f : 1.f, t ? 0.f : 1.f, t ? 0.f : 1.f, t ? 0.f : 1.f);
@@ -748,22 +617,8 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : (BN <= 32 && NS == NS_F16 &&
   for (int k = 0; k < RH; ++k) split_one(k);
   // the second-dispatched half of the workgroup loses every issue arbitration
   // on its SIMD: one static priority bump (MI355X_MICROARCH "two waves per SIMD")
-  if (SPFF_XPRIO && wave >= NW / 2) __builtin_amdgcn_s_setprio(1);
+  if (wave >= NW / 2) __builtin_amdgcn_s_setprio(1);
   for (int kc = kc0; kc < kc1; ++kc) {
-    constexpr bool LATE = HF && SPFF_XSCALE_LATE;
-    if (LATE && kc != kc0) {
-      // every wave is past chunk kc - 1's MFMAs and has published its max of chunk kc's
-      // halo: the chunk's scale (capped 2^64 above the current one, so the rescaled
-      // accumulator cannot overflow: |acc| < 2^40 in these units), then the split
-      __syncthreads();
-      exn = min(read_scale(kc & 1), exc + 64);
-      sx = exp2i(exn);
-#pragma unroll
-      for (int k = 0; k < RH; ++k) {
-        split_one(k);
-        store_one(k);
-      }
-    }
     if (kc == kc0 + 1) XST(st_c1a);
     if (kc != kc0) {
       // sign-alternating accumulation: odd chunks carry negated weights, so the
@@ -784,24 +639,32 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : (BN <= 32 && NS == NS_F16 &&
           for (int cb = 0; cb < CB; ++cb) acc[rb][cb] = -acc[rb][cb];
       }
       exc = exn;
-      if (!LATE) __syncthreads();
+      __syncthreads();
     }
     if (kc == kc0 + 1) XST(st_c1b);
-    if (SPFF_XDIAG != 1 || kc == kc0)
-      stash(kc, kc == kc0, !(LATE && kc != kc0), !(SPFF_XEARLYW && kc == kc0));
+    stash(kc, true, kc != kc0);  // (the first chunk's weights are already on their way)
     if (kc == kc0) XST(st_pc);
     if (kc == kc0 + 1) XST(st_c1c);
     __syncthreads();  // (vmcnt(0): the weight DMA has landed)
     if (kc == kc0 + 1) XST(st_c1d);
     fetch(kc + 1 < kc1 ? kc + 1 : kc, kc + 1 < kc1);
-    // (SPFF_XFPIN) issue those loads here, a whole J0 k-steps before the scale barrier needs
-    // them -- not where the scheduler would sink them, next to that barrier
-    if constexpr (SPFF_XFPIN) __builtin_amdgcn_sched_barrier(0x7);  // (ALU may cross)
+    // the next chunk's halo loads are issued here, right after the chunk-boundary barrier and
+    // a whole J0 k-steps before the scale barrier needs them, pinned by a scheduling barrier.
+    // Unpinned, the compiler sank them to the last k-step before the mid-chunk scale barrier
+    // (ISA: the loads at MFMA 100-144 of the 144 before the vmcnt waits), so every wave waited
+    // out their whole latency at that barrier
+    __builtin_amdgcn_sched_barrier(0x7);  // (ALU may cross)
 #if SPFF_XSTAMP
     if (kc == kc0) st_t1 = __builtin_amdgcn_s_memtime();
 #endif
-    // (XPIPE) the fragments of the current row block, carried across the unrolled k-loop
-    constexpr bool XPIPE = X16 && SPFF_XPIPE && (BN <= 32 || SPFF_XPIPE64) && !HR;  // (HR: 249 -> 256 VGPRs, spills)
+    // XPIPE: the k-loop is software-pipelined by one row block: the A fragments of row block
+    // rb + 1 (and, at the last row block, the next quad's B fragments and first A fragments)
+    // are read from LDS before row block rb's MFMAs, kept in that order by scheduling-group
+    // barriers.  Unpipelined, the compiler read each A fragment two MFMAs (32 cycles) before
+    // its use and waited lgkmcnt(0) there, i.e. most of the LDS latency exposed at every row
+    // block (64-wide tiles too: 211 -> 236 VGPRs, A/B 35.53 -> 35.40 ms/step)
+    constexpr bool XPIPE = !HR;  // (HR: 249 -> 256 VGPRs, spills)
+    // the fragments of the current row block, carried across the unrolled k-loop
     const bool pg1 = kg & 1, pg2 = kg & 2;
     auto psel4 = [&](int c0, int c1, int c2, int c3) {
       const int lo = pg1 ? c1 : c0, hi = pg1 ? c3 : c2;
@@ -829,30 +692,22 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : (BN <= 32 && NS == NS_F16 &&
     };
     bf16x8 pa[NP], pb[CB][NP];
     if constexpr (XPIPE) {
-      if (SPFF_XDIAG != 2) {
-        loadB(pb, 0);
-        loadA(pa, 0, 0);
-      }
+      loadB(pb, 0);
+      loadA(pa, 0, 0);
     }
 #pragma unroll
-    for (int j = 0; j < (SPFF_XDIAG == 2 ? 0 : NJ); ++j) {
-      if constexpr (SPFF_XIGLP >= 0) __builtin_amdgcn_iglp_opt(SPFF_XIGLP);
+    for (int j = 0; j < NJ; ++j) {
       // HF: the next chunk's scale before its halo is split (uniform: kc + 1 < kc1).
       // Capped at 2^64 above the current chunk's, so the rescaled accumulator cannot
       // overflow (|acc| < 2^40 in these units)
-      if (HF && !LATE && j == J0 && kc + 1 < kc1) {
+      if (HF && j == J0 && kc + 1 < kc1) {
         exn = min(block_scale(prep_max(), (kc + 1) & 1), exc + 64);
         sx = exp2i(exn);
-      }
-      if (LATE && j == (NJ > 2 ? NJ - 2 : 0) && kc + 1 < kc1) {
-        __builtin_amdgcn_sched_barrier(0x10C);
-        wave_max_store(prep_max(), (kc + 1) & 1);
-        __builtin_amdgcn_sched_barrier(0x10C);
       }
       // split one prefetched halo float4 per k-step from the middle of the
       // chunk on; the fences keep this VALU (and its vmcnt wait) in place
       // while MFMAs and LDS reads may still move across
-      if (!LATE && j >= J0 && (j - J0) * SPJ < RH) {
+      if (j >= J0 && (j - J0) * SPJ < RH) {
         __builtin_amdgcn_sched_barrier(0x10C);
 #pragma unroll
         for (int u = 0; u < SPJ; ++u)
@@ -900,7 +755,7 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : (BN <= 32 && NS == NS_F16 &&
               for (int cb = 0; cb < CB; ++cb) pb[cb][p] = nb[cb][p];
           }
         }
-      } else if constexpr (X16) {
+      } else {
         // lane group kg takes slot 4j + kg of the quad schedule
         // (the four slots' table entries are indexed by the unrolled j only and selected per
         // lane group: a lane-varying index into the constexpr tables made the compiler load
@@ -915,7 +770,7 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : (BN <= 32 && NS == NS_F16 &&
                               toff_of(QT.src[4 * j + 2]), toff_of(QT.src[4 * j + 3]));
         const int wtap =
             sel4(QT.tap[4 * j], QT.tap[4 * j + 1], QT.tap[4 * j + 2], QT.tap[4 * j + 3]);
-        // row blocks in groups of RBH (the 4 x 16 x 16 tiles' 8 row blocks: two groups,
+        // row blocks in groups of RBH (the 4 x 8 x 16 tiles' 8 row blocks: two groups,
         // so only half of the A fragments are live at a time)
         constexpr int RBH = RB > 4 ? 4 : RB;
         bf16x8 bm[CB][NP];
@@ -951,39 +806,6 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : (BN <= 32 && NS == NS_F16 &&
             acc[rb][cb] = c;
           }
         }
-      } else {
-        // lane half h takes tap 2j+h; the padding tap (>= T) reads a valid
-        // position against a zero weight row
-        const int tp0 = 2 * j, tp1 = (2 * j + 1 < T) ? 2 * j + 1 : T - 1;
-        const int toff = khalf ? toff_of(tp1) : toff_of(tp0);
-        const int wtap = 2 * j + khalf;
-        bf16x8 a[RB][NP], bm[CB][NP];
-#pragma unroll
-        for (int p = 0; p < NP; ++p) {
-#pragma unroll
-          for (int rb = 0; rb < RB; ++rb)
-            a[rb][p] = __builtin_bit_cast(bf16x8, Xs[p * NPOS + hpos[rb] + toff]);
-#pragma unroll
-          for (int cb = 0; cb < CB; ++cb)
-            bm[cb][p] = __builtin_bit_cast(bf16x8, Ws[(p * T2 + wtap) * BN + cb * 32 + l32]);
-        }
-#pragma unroll
-        for (int rb = 0; rb < RB; ++rb)
-#pragma unroll
-          for (int cb = 0; cb < CB; ++cb) {
-            f32x16 c = acc[rb][cb];
-            if constexpr (NP == 3) {
-              c = mfma32x16<HF>(a[rb][1], bm[cb][1], c);
-              c = mfma32x16<HF>(a[rb][0], bm[cb][2], c);
-              c = mfma32x16<HF>(a[rb][2], bm[cb][0], c);
-            }
-            if constexpr (NP >= 2) {
-              c = mfma32x16<HF>(a[rb][0], bm[cb][1], c);
-              c = mfma32x16<HF>(a[rb][1], bm[cb][0], c);
-            }
-            c = mfma32x16<HF>(a[rb][0], bm[cb][0], c);
-            acc[rb][cb] = c;
-          }
       }
     }
   }
@@ -1009,8 +831,11 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : (BN <= 32 && NS == NS_F16 &&
 // ---- epilogue: C[i][j], row i = voxel (vrow mapping), col j = out channel ----
   constexpr int OP = BN + 4;  // output image pitch: 4 rows apart = 16 banks apart
   constexpr int NROW = TD * TH * TW;
-  const bool vec = SPFF_XSTORE && !part && X16 && (Cout & 3) == 0 && (y.split & 3) == 0 &&
-                   (y.ld0 & 3) == 0 && (y.ld1 & 3) == 0;
+  // vec: the output tile goes through LDS (conflict-free [row][BN + 4] image in MFMA row
+  // order) and leaves as 16-byte row stores, instead of one 4-byte store per accumulator
+  // element (split-K partials and unaligned destinations)
+  const bool vec = !part && (Cout & 3) == 0 && (y.split & 3) == 0 && (y.ld0 & 3) == 0 &&
+                   (y.ld1 & 3) == 0;
   // fused InstanceNorm statistics of this output (replaces two HBM passes): per (tile,
   // channel) the sum over the tile's valid voxels and the sum of squared deviations about
   // the tile mean; merged per (b, c) in a fixed order by k_in_stats_fin (Chan).
@@ -1021,10 +846,10 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : (BN <= 32 && NS == NS_F16 &&
   float* sred2 = sred + NW * CB * NCOL;
   const int nd = min(D - d0, TD), nh = min(H - h0, TH), nwv = min(W - w0, TW);
   const float cnt = (float)(nd * nh * nwv);
-  // lanes holding the same column: 32x32 -- l and l+32; 16x16 -- l, l+16, l+32, l+48
+  // lanes holding the same column: l, l+16, l+32, l+48
   auto colsum = [&](float v) {
     v += __shfl_xor(v, 32);
-    if constexpr (X16) v += __shfl_xor(v, 16);
+    v += __shfl_xor(v, 16);
     return v;
   };
   auto okrow = [&](int rb, int r) {
@@ -1038,7 +863,7 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : (BN <= 32 && NS == NS_F16 &&
   constexpr int Q4 = BN / 4;
   constexpr int NIT = NROW * Q4 / XT_THREADS;
   static_assert(XT_THREADS % Q4 == 0 && (NROW * Q4) % XT_THREADS == 0, "store loop shape");
-  const bool bsm = SPFF_XBSTAT && !HR && vec && bst.y != nullptr;  // (uniform; unsharded only)
+  const bool bsm = !HR && vec && bst.y != nullptr;  // (uniform; unsharded only)
   float4 byv[NIT];
   if (bsm) {
 #pragma unroll
@@ -1064,7 +889,7 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : (BN <= 32 && NS == NS_F16 &&
       for (int r = 0; r < NREG; ++r)
 #pragma unroll
         for (int cb = 0; cb < CB; ++cb)
-          ot[((wave * RB + rb) * 16 + orow(r)) * OP + cb * NCOL + lcol] = acc[rb][cb][r];
+          ot[((wave * RB + rb) * 16 + orow(r)) * OP + cb * NCOL + l16] = acc[rb][cb][r];
   }
   if (stats) {
 #pragma unroll
@@ -1075,7 +900,7 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : (BN <= 32 && NS == NS_F16 &&
 #pragma unroll
         for (int r = 0; r < NREG; ++r) sacc += okrow(rb, r) ? acc[rb][cb][r] : 0.f;
       sacc = colsum(sacc);
-      if (lane < NCOL) sred[(wave * CB + cb) * NCOL + lcol] = sacc;
+      if (lane < NCOL) sred[(wave * CB + cb) * NCOL + l16] = sacc;
     }
   }
   if (vec || stats) __syncthreads();
@@ -1167,7 +992,7 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : (BN <= 32 && NS == NS_F16 &&
       const int64_t vox = (((int64_t)b * D + gd) * H + gh) * W + gw;
 #pragma unroll
       for (int cb = 0; cb < CB; ++cb) {
-        const int n = n0 + cb * NCOL + lcol;
+        const int n = n0 + cb * NCOL + l16;
         if (n >= Cout) continue;
         if (part) {
           part[((int64_t)blockIdx.z * ((int64_t)vol.B * D * H * W) + vox) * npad + n] =
@@ -1184,7 +1009,7 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : (BN <= 32 && NS == NS_F16 &&
 #pragma unroll
     for (int cb = 0; cb < CB; ++cb) {
       float t = 0.f;
-      for (int w = 0; w < NW; ++w) t += sred[(w * CB + cb) * NCOL + lcol];
+      for (int w = 0; w < NW; ++w) t += sred[(w * CB + cb) * NCOL + l16];
       tsum[cb] = t;
       mu[cb] = t / cnt;
     }
@@ -1199,15 +1024,15 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : (BN <= 32 && NS == NS_F16 &&
           qacc += okrow(rb, r) ? dl * dl : 0.f;
         }
       qacc = colsum(qacc);
-      if (lane < NCOL) sred2[(wave * CB + cb) * NCOL + lcol] = qacc;
+      if (lane < NCOL) sred2[(wave * CB + cb) * NCOL + l16] = qacc;
     }
     __syncthreads();
     if (wave == 0 && lane < NCOL) {
 #pragma unroll
       for (int cb = 0; cb < CB; ++cb) {
         float q = 0.f;
-        for (int w = 0; w < NW; ++w) q += sred2[(w * CB + cb) * NCOL + lcol];
-        const int n = n0 + cb * NCOL + lcol;
+        for (int w = 0; w < NW; ++w) q += sred2[(w * CB + cb) * NCOL + l16];
+        const int n = n0 + cb * NCOL + l16;
         if (n < Cout) {
           stats[((int64_t)tile * npad + n) * 2 + 0] = tsum[cb];
           stats[((int64_t)tile * npad + n) * 2 + 1] = q;
@@ -1340,11 +1165,8 @@ __global__ void k_splitk_reduce(const float* __restrict__ part, int nsplit, int6
 // 2-deep 32-wide tiles where the 4-deep ones waste more depth planes: D mod 4 = 1 or 2
 // (the registry's D = 5 computes 6 planes instead of 8).  Every host-side tile count
 // (xt_ntiles: fused statistics, split-K, depth / height splits) takes the same choice.
-#ifndef SPFF_X32SHALLOW
-#define SPFF_X32SHALLOW 1
-#endif
 static bool xt_shallow(Vol vol, int BN, int ns) {
-  return SPFF_X32SHALLOW && xt_d4(BN, ns) && (vol.D % 4 == 1 || vol.D % 4 == 2);
+  return xt_d4(BN, ns) && (vol.D % 4 == 1 || vol.D % 4 == 2);
 }
 static int xt_td_v(Vol vol, int BN, int ns) { return xt_shallow(vol, BN, ns) ? XT_D : xt_td(BN, ns); }
 static int xt_mb_v(Vol vol, int BN, int ns) { return xt_shallow(vol, BN, ns) ? 2 : xt_mb(BN, ns); }
@@ -1355,7 +1177,7 @@ static hipError_t launch_fwd_xh(const Src2& x, const uint4* wx, const Dst2& y, V
                                 int nkc, int N, int npad, hipStream_t s, float* part, int nsplit,
                                 int kps, float* stats, int dpart, const unsigned* wmx,
                                 const BStat& bst) {
-  constexpr int TH = SPFF_X16 ? 2 * NW * MB / TD : NW * MB;
+  constexpr int TH = 2 * NW * MB / TD;
   static_assert(NW == 8 || TD == XT_D || xt_d4(BN, NS), "xt_ntiles: tile shape");
   constexpr size_t shm = xt_lds_bytes<BN, KD, NS, TD, TH>();
   // (+ the kernel's static tables: the fused activation's scf[2][32] float4 and the per-wave
@@ -1366,7 +1188,7 @@ static hipError_t launch_fwd_xh(const Src2& x, const uint4* wx, const Dst2& y, V
   // the 16/32-wide kernels hold halo voxel indices in 32 bits (with the halo slices)
   if (BN <= 32 && (int64_t)vol.B * (vol.D + 2 * vol.dh) * vol.H * vol.W >= (int64_t(1) << 31))
     return hipErrorInvalidValue;
-  auto kern = k_conv3d_fwd_x<BN, KD, NS, MB, NW, SPFF_X16 != 0, TD, HR>;
+  auto kern = k_conv3d_fwd_x<BN, KD, NS, MB, NW, TD, HR>;
   static bool attr = false;
   if (!attr) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
@@ -1427,7 +1249,7 @@ XDims xdims(int KD, int Cin_w, int Cout_w, bool dgrad) {
   d.N = dgrad ? Cin_w : Cout_w;
   // 16-wide tiles for narrow outputs (N <= 16, 3x3x3): the SwinUNETR's C = 12 convs
   // ran their 12 columns in 32-wide tiles (62 % of the MFMA columns padding)
-  d.BN = d.N >= 64 ? 64 : (d.N <= 16 && KD == 3 && SPFF_X16) ? 16 : 32;
+  d.BN = d.N >= 64 ? 64 : (d.N <= 16 && KD == 3) ? 16 : 32;
   d.nkc = cdiv(d.K, 8);
   d.npad = rup(d.N, d.BN);
   d.T = KD * 9;
@@ -1462,7 +1284,7 @@ bool conv3d_fuses_act(int math, int C) {
 static int64_t xt_ntiles(Vol vol, int BN, int ns) {
   const int nw = xt_nw(BN, ns);
   const int td = xt_td_v(vol, BN, ns), mb = xt_mb_v(vol, BN, ns);
-  const int th = SPFF_X16 ? 2 * nw * mb / td : nw * mb;
+  const int th = 2 * nw * mb / td;
   return (int64_t)vol.B * cdiv(vol.D, td) * cdiv(vol.H, th) * cdiv(vol.W, XT_W);
 }
 namespace {
@@ -1694,15 +1516,10 @@ bool conv3d_packs_batched(int math) {
 }
 // Blocks per job: the largest weights (the 3DUNet's 320 x 320 x 27) set the launch's time,
 // so a job's cap is several blocks per CU, not the 64 (a quarter of the CUs) of round 4.
-#ifndef SPFF_PREP_NB
-#define SPFF_PREP_NB 256
-#endif
-#ifndef SPFF_PACK_NB
-#define SPFF_PACK_NB 512
-#endif
+constexpr int PREP_NB = 256, PACK_NB = 512;
 bool prep_absmax(PrepJobs* J, const float* p, int64_t n, unsigned* slot) {
   if (J->n == 32 || n <= 0) return false;
-  const int nb = (int)std::min<int64_t>(SPFF_PREP_NB, std::max<int64_t>(1, (n + 4095) / 4096));
+  const int nb = (int)std::min<int64_t>(PREP_NB, std::max<int64_t>(1, (n + 4095) / 4096));
   J->j[J->n++] = PrepJob{p, nullptr, slot, n, 0.f, 0, J->nblk, nb};
   J->nblk += nb;
   return true;
@@ -1725,7 +1542,7 @@ bool conv3d_pack_job(PackJobs* J, const float* w, void* wpack, int KD, int Cin_w
   if (J->n == 40) return false;
   const XDims d = xdims(KD, Cin_w, Cout_w, dgrad);
   const int64_t total = (int64_t)d.nkc * d.T2 * d.npad;
-  const int nb = (int)std::min<int64_t>(SPFF_PACK_NB, (total + 255) / 256);
+  const int nb = (int)std::min<int64_t>(PACK_NB, (total + 255) / 256);
   J->j[J->n++] = PackJob{w, static_cast<uint4*>(wpack), wmax, Cout_w, Cin_w, d.T, d.T2, d.nkc,
                          d.npad, d.BN, dgrad ? 1 : 0, J->nblk, nb};
   J->nblk += nb;
@@ -1750,9 +1567,6 @@ template <int NS>
 static hipError_t run_x(const Src2& x, const uint4* wu, const Dst2& y, Vol vol, int KD,
                         const XDims& d, hipStream_t s, float* ws, float* stats, int dpart,
                         const unsigned* wmx, const BStat& bst) {
-  // (32x32x16, MB = 4, 2 x 32 x 16 tiles for Cout <= 32: fits LDS but spills 91 VGPRs)
-  // (32x32x16 schedule, NW = 4 waves, 2 x 8 x 16 tiles: measured 6 % slower; the 16x16x32
-  // schedule takes NW = 4 for BN 32 by default, SPFF_X32NW)
   SplitK k = ws ? splitk_plan(vol, d, NS) : SplitK{1, d.nkc};
   float* part = k.nsplit > 1 ? ws : nullptr;
   if (d.BN == 64)
@@ -1792,8 +1606,7 @@ bool conv3d_splits_height(Vol vol, int KD, int Cin_w, int Cout_w, bool dgrad, in
   const XDims d = xdims(KD, Cin_w, Cout_w, dgrad);
   const int nw = xt_nw(d.BN, ns_of(math));
   const int ns = ns_of(math);
-  const int th = SPFF_X16 ? 2 * nw * xt_mb_v(vol, d.BN, ns) / xt_td_v(vol, d.BN, ns)
-                          : nw * xt_mb_v(vol, d.BN, ns);
+  const int th = 2 * nw * xt_mb_v(vol, d.BN, ns) / xt_td_v(vol, d.BN, ns);
   return use_split(vol, math, dgrad) && splitk_plan(vol, d, ns_of(math)).nsplit == 1 &&
          cdiv(vol.H, th) >= 3;
 }
@@ -1803,11 +1616,11 @@ size_t conv3d_stats_bytes(Vol vol, int KD, int Cin, int Cout) {
   return (size_t)nt * (2 * d.npad + 1) * sizeof(float);
 }
 // the input gradient's epilogue with the IN-backward sums (BStat): the split kernel, one
-// launch (no split-K, unsharded), 16-B row stores (the X16 LDS-staged epilogue)
+// launch (no split-K, unsharded), 16-B row stores (the LDS-staged epilogue)
 bool conv3d_fuses_bwd_stats(Vol vol, int KD, int Cin_w, int Cout_w, int math) {
   const XDims d = xdims(KD, Cin_w, Cout_w, true);
-  return SPFF_XBSTAT && SPFF_X16 && SPFF_XSTORE && use_split(vol, math, true) && vol.dh == 0 &&
-         (d.N & 3) == 0 && splitk_plan(vol, d, ns_of(math)).nsplit == 1;
+  return use_split(vol, math, true) && vol.dh == 0 && (d.N & 3) == 0 &&
+         splitk_plan(vol, d, ns_of(math)).nsplit == 1;
 }
 // per (b, c): sum dr, sum dr xhat over the sample's tiles in a fixed order (fp64) -> k1, k2
 // (/ N) and dgamma, dbeta (summed over b) -- k_in_bwd_stats' outputs

@@ -23,14 +23,6 @@
 // head's loaders +0.14 ms/step against dec1's 0.2 ms/step level-0 pass
 #define SPFF_OUTFUSE 1
 #endif
-#ifndef SPFF_POOL_FOLD
-// 1: the encoder blocks' output gradients (skip + MaxPool backward) are formed by their two
-// readers (PoolAdd: the tail reduction, the IN-backward apply) instead of k_maxpool_bwd_add
-#define SPFF_POOL_FOLD 1
-#endif
-#ifndef SPFF_RED_FUSE
-#define SPFF_RED_FUSE 1  // 0 (A/B diagnostics): separate tail and IN-backward reductions
-#endif
 #include "spff.h"
 
 #include <cmath>
@@ -162,7 +154,9 @@ struct spff_plan : PlanBase {
   int dbg_stop = -1;  // debug: stop backward after this many blocks (-1 = off)
   bool efilm_ready = false;  // this forward's EFiLM coefficients are computed (all blocks)
   bool keep_out = false;  // debug: store the fused block outputs too (saved views)
-  bool pool_fold = SPFF_POOL_FOLD;  // PoolAdd in the encoder backward (debug key 2: off)
+  // the encoder blocks' output gradients (skip + MaxPool backward) are formed by their two
+  // readers (PoolAdd: the tail reduction, the IN-backward apply) instead of k_maxpool_bwd_add
+  bool pool_fold = true;  // (debug key 2: off)
   bool bst_fuse = true;  // conv1's IN-backward sums in the dgrad epilogue (debug key 3: off)
   bool head_fold = true;  // the head's backward inside dec1's tail pass (debug key 4: off)
   size_t wg_bytes = 0;    // size of wg_ws (the fold's partials must fit it: the layout is fixed)
@@ -441,9 +435,9 @@ int build_plan(spff_plan* p) {
       if (world > 1 && !hsh)
         b.spec = p->alloc((size_t)B * (p->co.D_glob / 2 + 1) * 2 * sizeof(double));
     }
-    red_ws = std::max(red_ws, slab_reduce_ws_bytes(v, b.C, b.tail() && SPFF_RED_FUSE ? 6 : 2));
+    red_ws = std::max(red_ws, slab_reduce_ws_bytes(v, b.C, b.tail() ? 6 : 2));
     red_out = std::max(red_out, (size_t)B * b.C * D * 2 * sizeof(float));
-    if (b.tail() && SPFF_RED_FUSE)
+    if (b.tail())
       red_out4 = std::max(red_out4, (size_t)B * b.C * D * 4 * sizeof(float));
     gs = std::max(gs, world > 1 && !hsh ? gates_sh_scratch_bytes(v, b.C, p->co.D_glob)
                                         : gates_scratch_bytes(v, b.C));
@@ -1132,13 +1126,11 @@ int bwd_block(spff_plan* p, Blk& b, const float* dout, const Dst2* dx, const Src
     a.mean = p->F(b.mean2);
     a.rstd = p->F(b.rstd2);
     a.pa = pa;
-    // (SPFF_RED_FUSE: the IN-backward sums of y2 in the same pass, RED_BWD_TAIL6)
+    // (the IN-backward sums of y2 in the same pass, RED_BWD_TAIL6)
     if (!hs) {
       PROFB(p, 4, 0.0, 8.0 * (double)nvox(v) * C,
-            SPFF_RED_FUSE ? slab_reduce(RED_BWD_TAIL6, a, v, C, p->F(p->red_out), p->F(p->red_ws),
-                                        p->st, p->F(p->red_out4))
-                          : slab_reduce(RED_BWD_TAIL, a, v, C, p->F(p->red_out), p->F(p->red_ws),
-                                        p->st));
+            slab_reduce(RED_BWD_TAIL6, a, v, C, p->F(p->red_out), p->F(p->red_ws), p->st,
+                        p->F(p->red_out4)));
     }
     GateParams gp = gate_params(p, b);
     GateSaved sv = gate_saved(p, b);
@@ -1182,7 +1174,7 @@ int bwd_block(spff_plan* p, Blk& b, const float* dout, const Dst2* dx, const Src
     RedArgs a{};
     a.y = p->F(b.y2); a.g = dout; a.mean = p->F(b.mean2); a.rstd = p->F(b.rstd2);
     a.al = p->F(b.al2); a.de = p->F(b.de2); a.A = A; a.Bc = Bc; a.pa = pa;
-    if (b.tail() && SPFF_RED_FUSE)
+    if (b.tail())
       HIPCK(in_sums_from_tail(p->F(p->red_out4), A, Bc, p->F(p->red_out),
                               (int64_t)v.B * C * v.D, p->st));
     else
@@ -1363,7 +1355,7 @@ int backward(spff_plan* p, const float* dl) {
   // over (y2, dl) gives the head's weight gradient and dec1's tail sums, dec1's IN-backward
   // apply forms dout from dl, and G_out is first written by up1's input gradient.
   const HeadSrc hsrc = head_src(dl, hp, f, p->K);
-  const bool fold = p->head_fold && SPFF_RED_FUSE && !p->co.on() && !p->hsh && B[6].tail() &&
+  const bool fold = p->head_fold && !p->co.on() && !p->hsh && B[6].tail() &&
                     head_streams(f, p->K) && head_tail_bwd_ok(p->vol[0], f, hsrc) &&
                     head_tail_bwd_fits(p->vol[0], f, p->wg_bytes);
   if (fold) {

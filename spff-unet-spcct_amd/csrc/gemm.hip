@@ -25,10 +25,6 @@ static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 #ifndef SPFF_XTY_U1
 #define SPFF_XTY_U1 16  // voxel pairs in flight per wave of the one-block k_xty (the head wgrad)
 #endif
-// SPFF_GEMM_SPLIT=0 (A/B diagnostics): the fp32 MFMA GEMMs for every math
-#ifndef SPFF_GEMM_SPLIT
-#define SPFF_GEMM_SPLIT 1
-#endif
 __host__ __device__ inline int64_t cdiv64d(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static int num_cus() {
   static int n = [] {
@@ -40,20 +36,11 @@ static int num_cus() {
   }();
   return n;
 }
-// SPFF_GEMM_PERSIST=0 (A/B diagnostics): one row tile per workgroup
-#ifndef SPFF_GEMM_PERSIST
-#define SPFF_GEMM_PERSIST 1
-#endif
-// SPFF_GEMM_F16=0 (A/B diagnostics): the GEMMs take the bf16x6 split under SPFF_MATH_F16X3
-#ifndef SPFF_GEMM_F16
-#define SPFF_GEMM_F16 1
-#endif
 // GEMM arithmetic of a conv math mode: 0 = fp32 MFMA (k_gemm / k_atb), 1 = the exact
 // 3-plane bf16 split (bf16x6), 2 = scaled fp16 planes (f16x3, per-chunk scales, below)
 enum { GM_F32 = 0, GM_BF16X6 = 1, GM_F16X3 = 2 };
 static inline int gemm_split(int math) {
-  if (!SPFF_GEMM_SPLIT) return GM_F32;
-  if (math == SPFF_MATH_F16X3) return SPFF_GEMM_F16 ? GM_F16X3 : GM_BF16X6;
+  if (math == SPFF_MATH_F16X3) return GM_F16X3;
   return math == SPFF_MATH_BF16X6 ? GM_BF16X6 : GM_F32;
 }
 static inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
@@ -803,7 +790,7 @@ static void launch_gemm_x(const AL& A, const float* B, const CS& C, dim3 grid, i
     per_cu = 2;
   per_cu = std::max(per_cu, 1);
   const int64_t cap = std::max<int64_t>(1, (int64_t)per_cu * num_cus() / std::max(1, (int)grid.y));
-  const dim3 gx((unsigned)(SPFF_GEMM_PERSIST ? std::min<int64_t>(grid.x, cap) : grid.x), grid.y);
+  const dim3 gx((unsigned)std::min<int64_t>(grid.x, cap), grid.y);
   hipLaunchKernelGGL(kern, gx, dim3(256), 0, s, A, B, C, kpad, npad);
 }
 
