@@ -75,7 +75,8 @@ typedef struct spff_cfg {
    * gate outputs and up-conv outputs (~2.8 KB per input voxel); SPFF_MEM_LEAN keeps
    * only the conv outputs y1, y2 and per-(b,c[,d]) coefficients and recomputes the
    * rest in the backward (~1.7 KB per voxel: one 5 x 512^3 volume fits one MI355X;
-   * +~3 % step time); SPFF_MEM_AUTO (0) = lean from 2^26 voxels per plan. */
+   * +~3 % step time); SPFF_MEM_AUTO (0) = lean from 2^26 voxels per plan, never the
+   * forward-only layout; SPFF_MEM_INFER: see below. */
   int memory_mode;
   /* the axis a sharded plan (shard_world > 1) splits: SPFF_SHARD_DEPTH (0) -- above;
    * SPFF_SHARD_HEIGHT (1) -- the registry layout [B, 1, 5, H, W]: this
@@ -105,6 +106,13 @@ typedef struct spff_cfg {
 #define SPFF_MEM_AUTO 0
 #define SPFF_MEM_FULL 1
 #define SPFF_MEM_LEAN 2
+/* forward-only layout (inference): nothing is kept for a backward; the activations are
+ * placed by liveness in three level-0 buffers (~0.6 KB per input voxel at base 32: one
+ * 5 x 512^3 volume in ~73 GiB).  spff_forward returns the full layout's logits bit for bit;
+ * spff_backward returns SPFF_EINVAL; spff_saved_tensor knows only "x_cl", the pools, the
+ * per-(b,c) coefficients and "dec1.y2".  Unsharded plans without use_spatial /
+ * use_skip_gate only (SPFF_EINVAL otherwise). */
+#define SPFF_MEM_INFER 3
 
 /* The shard group's collectives, implemented by the caller (e.g. RCCL through
  * torch.distributed) and called by the engine in stream order on the stream
@@ -156,6 +164,23 @@ size_t spff_workspace_bytes(const spff_plan* plan);
 /* forward: x [B][Cin][D][H][W] -> logits [B][D][H][W][K]  (models.py:693-701) */
 int spff_forward(spff_plan* plan, const float* x, const float* params, float* logits,
                  void* workspace, void* stream);
+/* forward + class mask (test.py evaluate, per_class_metrics_3d helpers.py:668-725), on a
+ * plan of any memory mode with K <= 255: mask [V] (V = B D H W, rows in logits order) = the
+ * argmax of each voxel's logits, first maximum wins (spff_confusion's rule); with labels
+ * [V], conf = K*(K+1) int64 as spff_confusion gives for the same logits (use_ignore = 0: no
+ * voxel is masked), zeroed on the stream by a kernel (a captured graph replays it); conf is
+ * NULL exactly when labels is.  logits [V][K] channel-last as spff_forward's, or NULL: where
+ * the streaming head covers the plan (base 32 or 64, K <= 32) the head forms the class and
+ * the counts from the logits it holds in registers and NULL means they are never written;
+ * elsewhere logits must be given (SPFF_EINVAL otherwise) and a row-argmax pass reads them.
+ * No host synchronisation. */
+int spff_predict(spff_plan* plan, const float* x, const float* params,
+                 uint8_t* mask,            /* [V] class index */
+                 float* logits,            /* [V][K] channel-last, or NULL */
+                 const int64_t* labels,    /* [V] or NULL */
+                 int use_ignore, int ignore_index,
+                 int64_t* conf,            /* K*(K+1), as spff_confusion; NULL iff labels NULL */
+                 void* workspace, void* stream);
 /* backward of the last forward: dlogits [B][D][H][W][K] -> dparams (flat, every
  * entry written).  Input gradient is not produced (the hot path never needs it). */
 int spff_backward(spff_plan* plan, const float* dlogits, const float* params, float* dparams,
@@ -170,7 +195,9 @@ int spff_saved_tensor(const spff_plan* plan, void* workspace, const char* name,
  * key 1 = also store the block outputs the up-conv / head GEMMs apply on the fly
  * (bott/dec*.out; otherwise spff_saved_tensor reports them as not stored);
  * key 4 = 0: the head's backward as passes of its own (weight gradient, input gradient)
- * before the last block's tail reduction, instead of folded into that block's passes */
+ * before the last block's tail reduction, instead of folded into that block's passes;
+ * key 5 = 1: spff_forward / spff_predict run the head alone, on the last block's conv output
+ * and coefficients that the previous call left in the workspace (timing the head by itself) */
 int spff_debug_set(spff_plan* plan, int key, int value);
 
 /* optional HIP-event timing of the engine's kernels on the plan's stream (bench.py):

@@ -118,6 +118,9 @@ struct spff_plan : PlanBase {
   int efh = 32, efp = 16, fphase = 0;  // EnergyFiLM3D(hidden, pe_dims), learn_phase
   bool lean = false;  // SPFF_MEM_LEAN layout: a1 / out / up-conv outputs live in the
                       // gradient scratch and are recomputed in the backward
+  bool infer = false;  // SPFF_MEM_INFER layout: forward-only, activations placed by liveness
+                       // in three level-0 buffers (build_plan); nothing is kept for a backward
+  size_t L0[3] = {0, 0, 0};  // (infer) the three level-0 buffers, [V0][f] each
   Blk blk[7];
   UpL up[3];  // up3, up2, up1
   bool gated = false;   // use_skip_gate
@@ -159,6 +162,7 @@ struct spff_plan : PlanBase {
   bool pool_fold = true;  // (debug key 2: off)
   bool bst_fuse = true;  // conv1's IN-backward sums in the dgrad epilogue (debug key 3: off)
   bool head_fold = true;  // the head's backward inside dec1's tail pass (debug key 4: off)
+  bool head_only = false;  // debug key 5: spff_forward / spff_predict run the head alone
   size_t wg_bytes = 0;    // size of wg_ws (the fold's partials must fit it: the layout is fixed)
   // depth-sharded plans: side stream + events of the halo exchange that overlaps the
   // interior depth tiles of the next convolution (conv_halo)
@@ -248,6 +252,66 @@ void host_pe(int D, int P, std::vector<float>& pe) {
   }
 }
 
+// The forward-only layout (SPFF_MEM_INFER): nothing is kept for a backward, so every
+// block's y1 / a1 / y2 / out and the up-conv outputs are placed by liveness in three level-0
+// buffers A, B, C of g = [V0][f] floats (a level-l tensor fills g / 2^l) and two buffers for
+// the level-1 / level-2 skips, which take the decoder outputs once their skip is read:
+//   enc1        y1 A          a1 B          y2 C          out A  (alive up to dec1's conv 1)
+//   enc2, enc3  y1 B          a1 B + g/2    y2 C          out skip1, skip2
+//   bott        y1 B          a1 B + g/2    y2 C          out C + g/2
+//   up3, up2    out B         raw B + g/2
+//   dec3, dec2  y1 C          a1 C + g/2    y2 B + g/2    out skip2, skip1
+//   up1         out B         raw C
+//   dec1        y1 C          a1 A          y2 B          out A  (stored only when not fused)
+// (a1 only where conv 2 does not apply it as it loads y1.)  The conv, act_apply and GEMM
+// kernels are not in-place safe: every pass's inputs and output are checked to be disjoint.
+int infer_layout(spff_plan* p) {
+  const int f = p->f;
+  const size_t g = nvox(p->vol[0]) * f * sizeof(float);
+  for (int k = 0; k < 3; ++k) p->L0[k] = p->alloc(g);
+  const size_t A = p->L0[0], Bb = p->L0[1], Cb = p->L0[2];
+  const size_t skip[2] = {p->alloc(nvox(p->vol[1]) * 2 * f * sizeof(float)),
+                          p->alloc(nvox(p->vol[2]) * 4 * f * sizeof(float))};
+  Blk* B = p->blk;
+  B[0].y1 = A; B[0].a1 = Bb; B[0].y2 = Cb; B[0].out = A;
+  for (int i = 1; i <= 3; ++i) {
+    B[i].y1 = Bb; B[i].a1 = Bb + g / 2; B[i].y2 = Cb;
+    B[i].out = i < 3 ? skip[i - 1] : Cb + g / 2;
+  }
+  for (int i = 4; i <= 5; ++i) {
+    p->up[i - 4].out = Bb; p->up[i - 4].raw = Bb + g / 2;
+    B[i].y1 = Cb; B[i].a1 = Cb + g / 2; B[i].y2 = Bb + g / 2;
+    B[i].out = skip[5 - i];
+  }
+  p->up[2].out = Bb; p->up[2].raw = Cb;
+  B[6].y1 = Cb; B[6].a1 = A; B[6].y2 = Bb; B[6].out = A;
+  // read / write sets of the forward's passes
+  bool ok = true;
+  const auto dis = [&](size_t a, size_t an, size_t b, size_t bn) {
+    ok = ok && (a + an <= b || b + bn <= a);
+  };
+  for (int i = 0; i < 7; ++i) {
+    const Blk& b = B[i];
+    const size_t act = nvox(p->vol[b.lvl]) * b.C * sizeof(float);
+    if (i >= 4) {  // conv 1 reads [up | skip]; the up-conv reads the block below
+      const UpL& U = p->up[i - 4];
+      const Blk& src = B[i - 1], &sk = B[6 - i];
+      const size_t sa = nvox(p->vol[src.lvl]) * src.C * sizeof(float);
+      const size_t raw = nvox(p->vol[U.lvl_low]) * 4 * U.Cout * sizeof(float);
+      dis(src.out, sa, U.out, act);
+      if (U.rs) { dis(src.out, sa, U.raw, raw); dis(U.raw, raw, U.out, act); }
+      dis(U.out, act, b.y1, act);
+      dis(sk.out, act, b.y1, act);
+      dis(sk.out, act, U.out, act);
+      if (U.rs) dis(sk.out, act, U.raw, raw);
+    }
+    if (!b.fa) { dis(b.y1, act, b.a1, act); dis(b.a1, act, b.y2, act); }
+    dis(b.y1, act, b.y2, act);
+    if (!b.fout) dis(b.y2, act, b.out, act);
+  }
+  return ok ? SPFF_OK : fail(SPFF_EINVAL, "forward-only layout: a pass would read the buffer it writes");
+}
+
 int build_plan(spff_plan* p) {
   const spff_cfg& c = p->cfg;
   if (c.batch < 1 || c.in_ch < 1 || c.depth < 1 || c.num_classes < 1 ||
@@ -261,7 +325,7 @@ int build_plan(spff_plan* p) {
   if (c.in_ch > 1024) return fail(SPFF_EINVAL, "in_ch > 1024 not supported");
   if (c.math < SPFF_MATH_F32 || c.math > SPFF_MATH_F16X3)
     return fail(SPFF_EINVAL, "math must be one of SPFF_MATH_*");
-  if (c.memory_mode < SPFF_MEM_AUTO || c.memory_mode > SPFF_MEM_LEAN)
+  if (c.memory_mode < SPFF_MEM_AUTO || c.memory_mode > SPFF_MEM_INFER)
     return fail(SPFF_EINVAL, "memory_mode must be one of SPFF_MEM_*");
   p->efh = c.efilm_hidden > 0 ? c.efilm_hidden : 32;
   p->efp = c.efilm_pe_dims > 0 ? c.efilm_pe_dims : 16;
@@ -277,6 +341,13 @@ int build_plan(spff_plan* p) {
   if (attn && c.memory_mode == SPFF_MEM_LEAN)
     return fail(SPFF_EINVAL, "use_spatial / use_skip_gate: the lean layout does not recompute "
                              "them; use SPFF_MEM_FULL or SPFF_MEM_AUTO");
+  p->infer = c.memory_mode == SPFF_MEM_INFER;
+  if (p->infer && c.shard_world > 1)
+    return fail(SPFF_EINVAL, "SPFF_MEM_INFER: unsharded plans only (the forward-only layout "
+                             "has no halo slices)");
+  if (p->infer && attn)
+    return fail(SPFF_EINVAL, "SPFF_MEM_INFER: the forward-only layout does not place "
+                             "use_spatial / use_skip_gate tensors; use SPFF_MEM_FULL");
   p->lean = c.memory_mode == SPFF_MEM_LEAN ||
             (c.memory_mode == SPFF_MEM_AUTO && !attn &&
              (int64_t)c.batch * c.depth * c.height * c.width >= (int64_t(1) << 26));
@@ -327,6 +398,8 @@ int build_plan(spff_plan* p) {
     // (a stage with spatial attention stores its output: the GEMMs cannot apply the stencil)
     b.fout = (SPFF_OUTFUSE >= 2 ? i >= 3 : SPFF_OUTFUSE == 1 && i == 6) && !p->lean &&
              b.C % 4 == 0 && !b.sa;
+    // (forward-only: the decoder outputs below dec1 are stored, their y2 is overwritten)
+    if (p->infer && i != 6) b.fout = false;
     conv_dims(b.c1, b.Cin, b.C);
     conv_dims(b.c2, b.C, b.C);
   }
@@ -397,19 +470,23 @@ int build_plan(spff_plan* p) {
   const auto slice = [&](const Vol& v, int C) { return (size_t)v.H * v.W * C * sizeof(float); };
   p->x_cl = p->alloc_halo(nvox(v0) * p->ldx * sizeof(float), slice(v0, p->ldx));
   size_t red_ws = 0, red_out = 0, red_out4 = 0, gs = 0, bcd = 0, wg = 0, wt = 0, cst = 0;
+  size_t spk = 0;  // the forward convs' split-K partials alone (the forward-only layout's wg_ws)
   size_t hst = 0, gd = 0;
   for (int i = 0; i < 7; ++i) {
     Blk& b = p->blk[i];
     const Vol& v = p->vol[b.lvl];
     const size_t act = nvox(v) * b.C * sizeof(float);
     // with the fused input activation conv2 reads y1 (halo'd when sharded), not a1
-    b.y1 = b.fa ? p->alloc_halo(act, slice(v, b.C)) : p->alloc(act);
-    b.y2 = p->alloc(act);
-    if (!p->lean) {
-      if (!b.fa) b.a1 = p->alloc_halo(act, slice(v, b.C));
-      b.out = p->alloc_halo(act, slice(v, b.C));
-    } else if (i == 3) {
-      b.out = p->alloc(act);  // the bottleneck output (up3's input) is kept: 1/64 size
+    // (forward-only: y1 / a1 / y2 / out are placed by liveness below, infer_layout)
+    if (!p->infer) {
+      b.y1 = b.fa ? p->alloc_halo(act, slice(v, b.C)) : p->alloc(act);
+      b.y2 = p->alloc(act);
+      if (!p->lean) {
+        if (!b.fa) b.a1 = p->alloc_halo(act, slice(v, b.C));
+        b.out = p->alloc_halo(act, slice(v, b.C));
+      } else if (i == 3) {
+        b.out = p->alloc(act);  // the bottleneck output (up3's input) is kept: 1/64 size
+      }
     }
     const size_t bc = (size_t)B * b.C * sizeof(float);
     b.mean1 = p->alloc(bc); b.rstd1 = p->alloc(bc); b.al1 = p->alloc(bc); b.de1 = p->alloc(bc);
@@ -450,6 +527,8 @@ int build_plan(spff_plan* p) {
     wg = std::max(wg, conv3d_wgrad_ws_bytes(v, p->KD, b.C, b.C));
     wg = std::max(wg, conv3d_splitk_bytes(v, p->KD, b.Cin, b.C));
     wg = std::max(wg, conv3d_splitk_bytes(v, p->KD, b.C, b.C));
+    spk = std::max(spk, conv3d_splitk_bytes(v, p->KD, b.Cin, b.C));
+    spk = std::max(spk, conv3d_splitk_bytes(v, p->KD, b.C, b.C));
     wt = std::max(wt, conv_pack_bytes(b.c1, p->KD));
     wt = std::max(wt, conv_pack_bytes(b.c2, p->KD));
     cst = std::max(cst, conv3d_stats_bytes(v, p->KD, b.Cin, b.C));
@@ -464,9 +543,11 @@ int build_plan(spff_plan* p) {
   for (int u = 0; u < 3; ++u) {
     UpL& U = p->up[u];
     const Vol& vh = p->vol[U.lvl_low - 1];
-    if (!p->lean) U.out = p->alloc_halo(nvox(vh) * U.Cout * sizeof(float), slice(vh, U.Cout));
+    if (!p->lean && !p->infer)
+      U.out = p->alloc_halo(nvox(vh) * U.Cout * sizeof(float), slice(vh, U.Cout));
     U.pk = p->alloc(upconv_pack_floats(U.Cin, U.Cout) * sizeof(float));
-    if (U.rs) U.raw = p->alloc(nvox(p->vol[U.lvl_low]) * 4 * U.Cout * sizeof(float));
+    if (U.rs && !p->infer)
+      U.raw = p->alloc(nvox(p->vol[U.lvl_low]) * 4 * U.Cout * sizeof(float));
     wg = std::max(wg, upconv_wgrad_ws_bytes(p->vol[U.lvl_low], U.Cin, U.Cout));
   }
   p->head_pk = p->alloc(head_pack_floats(f, p->K) * sizeof(float));
@@ -501,12 +582,15 @@ int build_plan(spff_plan* p) {
   }
   p->red_ws = p->alloc(red_ws);
   p->red_out = p->alloc(red_out);
-  p->red_out4 = p->alloc(red_out4);
+  if (!p->infer) p->red_out4 = p->alloc(red_out4);  // (backward: the tail sums)
   p->gscr = p->alloc(gs);
-  p->Abuf = p->alloc(bcd);
-  p->Bbuf = p->alloc(bcd);
-  p->kk1 = p->alloc((size_t)B * 8 * f * sizeof(float));
-  p->kk2 = p->alloc((size_t)B * 8 * f * sizeof(float));
+  if (!p->infer) {  // the backward's per-(b,c[,d]) coefficients
+    p->Abuf = p->alloc(bcd);
+    p->Bbuf = p->alloc(bcd);
+    p->kk1 = p->alloc((size_t)B * 8 * f * sizeof(float));
+    p->kk2 = p->alloc((size_t)B * 8 * f * sizeof(float));
+  }
+  if (p->infer) wg = spk;
   p->wg_ws = p->alloc(wg);
   p->wg_bytes = wg;
   // (the lean layout keeps the one scratch image: it trades time for the smallest footprint)
@@ -516,6 +600,7 @@ int build_plan(spff_plan* p) {
       Blk& b = p->blk[i];
       b.pk[0] = p->alloc(conv_pack_bytes(b.c1, p->KD));
       b.pk[1] = p->alloc(conv_pack_bytes(b.c2, p->KD));
+      if (p->infer) continue;  // no input-gradient images
       b.pk[2] = p->alloc(conv_pack_bytes(b.c2, p->KD));
       if (i > 0) b.pk[3] = p->alloc(conv_pack_bytes(b.c1, p->KD));  // enc1's input: no dx
     }
@@ -528,16 +613,20 @@ int build_plan(spff_plan* p) {
   // (V0 / 4^l voxels x f 2^l channels) fills 1 / 2^l of a buffer.  Halo'd (level-0
   // slice = the largest) so any of them can hold a conv input.
   const size_t gbytes = nvox(v0) * f * sizeof(float);
-  p->G_out = p->alloc_halo(gbytes, slice(v0, f));
-  p->G_dy2 = p->alloc_halo(gbytes, slice(v0, f));
-  p->G_da1 = p->alloc_halo(gbytes, slice(v0, f));
-  p->G_dx = p->alloc_halo(gbytes, slice(v0, f));
-  // skip gradients: dskip0 needs a level-0 buffer of its own; dskip1 (alive from
-  // dec2's input gradient to enc2's backward) and dskip2 (dec3 -> enc3) sit in the
-  // upper halves of G_dx / G_out, which only level-0 tensors reach (dec1, before)
-  p->dskip[0] = p->alloc(gbytes);
-  p->dskip[1] = p->G_dx + gbytes / 2;
-  p->dskip[2] = p->G_out + gbytes / 2;
+  if (p->infer) {
+    CK(infer_layout(p));
+  } else {
+    p->G_out = p->alloc_halo(gbytes, slice(v0, f));
+    p->G_dy2 = p->alloc_halo(gbytes, slice(v0, f));
+    p->G_da1 = p->alloc_halo(gbytes, slice(v0, f));
+    p->G_dx = p->alloc_halo(gbytes, slice(v0, f));
+    // skip gradients: dskip0 needs a level-0 buffer of its own; dskip1 (alive from
+    // dec2's input gradient to enc2's backward) and dskip2 (dec3 -> enc3) sit in the
+    // upper halves of G_dx / G_out, which only level-0 tensors reach (dec1, before)
+    p->dskip[0] = p->alloc(gbytes);
+    p->dskip[1] = p->G_dx + gbytes / 2;
+    p->dskip[2] = p->G_out + gbytes / 2;
+  }
   if (p->lean) {
     // forward placement of the unsaved tensors (lifetimes in DESIGN.md §2):
     //   enc1 a1/out -> G_da1 (out alive until dec1's first conv)
@@ -911,7 +1000,8 @@ int f16_param_slots(spff_plan* p) {
       }
       ok = ok && conv3d_pack_job(&kj, p->P(b.c1.w), p->F(b.pk[0]), p->KD, b.Cin, b.C, false, w1);
       ok = ok && conv3d_pack_job(&kj, p->P(b.c2.w), p->F(b.pk[1]), p->KD, b.C, b.C, false, w2);
-      ok = ok && conv3d_pack_job(&kj, p->P(b.c2.w), p->F(b.pk[2]), p->KD, b.C, b.C, true, w2);
+      if (b.pk[2])  // (a forward-only plan has no input-gradient images)
+        ok = ok && conv3d_pack_job(&kj, p->P(b.c2.w), p->F(b.pk[2]), p->KD, b.C, b.C, true, w2);
       if (b.pk[3])
         ok = ok && conv3d_pack_job(&kj, p->P(b.c1.w), p->F(b.pk[3]), p->KD, b.Cin, b.C, true, w1);
       if (!ok) return fail(SPFF_EINVAL, "weight preparation table overflow");
@@ -1294,7 +1384,16 @@ int block_grads_ready(spff_plan* p, const Blk& b) {
   return grad_ready(p, b.se0, b.se1);
 }
 
-int forward(spff_plan* p, const float* x, float* logits) {
+// spff_predict's outputs, formed by the head as it holds a voxel's logits
+struct Predict {
+  uint8_t* mask;
+  const int64_t* labels;  // null: no counts
+  int use_ignore, ignore;
+  int64_t* conf;
+};
+
+// the network up to dec1's second conv and its coefficients, and the packed head weight
+int forward_trunk(spff_plan* p, const float* x) {
   const int f = p->f;
   const spff_cfg& c = p->cfg;
   {  // every block's EnergyFiLM coefficients in one launch (parameters only)
@@ -1338,10 +1437,40 @@ int forward(spff_plan* p, const float* x, float* logits) {
   }
   float* hp = p->F(p->head_pk);
   HIPCK(head_pack(p->P(p->out_w), hp, hp + head_pack_dgrad_offset(f, p->K), f, p->K, p->st));
+  return SPFF_OK;
+}
+
+// pr null: spff_forward.  Else logits may be null where the streaming head forms the mask.
+int forward(spff_plan* p, const float* x, float* logits, const Predict* pr = nullptr) {
+  const int f = p->f;
+  // (debug key 5: the head alone, on what the previous forward left in the workspace)
+  if (!p->head_only) CK(forward_trunk(p, x));
+  const Blk* prev = &p->blk[6];
+  float* hp = p->F(p->head_pk);
   const ActRows hact = act_rows(p, *prev);
-  PROF(p, 3, 2.0 * nvox(p->vol[0]) * f * p->K,
-       head_fwd(p->F(prev->out), hp, p->P(p->out_b), logits, nvox(p->vol[0]), f, p->K, p->st,
-                p->cfg.math, prev->fout ? &hact : nullptr));
+  const ActRows* ha = prev->fout ? &hact : nullptr;
+  const int64_t V0 = nvox(p->vol[0]);
+  const int K = p->K;
+  if (pr) {
+    // (a kernel fill, not a memset: a captured graph replays it)
+    if (pr->labels) HIPCK(spff::zero_async(pr->conf, sizeof(int64_t) * K * (K + 1), p->st));
+    if (head_mask_streams(p->F(prev->out), logits, f, K, ha)) {
+      PROFB(p, 3, 2.0 * V0 * f * K,
+            (double)V0 * (4.0 * f + 1.0 + (logits ? 4.0 * K : 0.0) + (pr->labels ? 8.0 : 0.0)),
+            head_mask(p->F(prev->out), hp, p->P(p->out_b), logits, pr->mask, pr->labels,
+                      pr->use_ignore, pr->ignore, pr->conf, V0, f, K, p->st, ha));
+      return SPFF_OK;
+    }
+    if (!logits)
+      return fail(SPFF_EINVAL, "spff_predict: logits must be given where the streaming head "
+                               "does not cover the plan (base 32 or 64, K <= 32)");
+  }
+  PROF(p, 3, 2.0 * V0 * f * K,
+       head_fwd(p->F(prev->out), hp, p->P(p->out_b), logits, V0, f, K, p->st, p->cfg.math, ha));
+  if (pr)
+    PROFB(p, 3, 0.0, (double)V0 * (4.0 * K + 1.0 + (pr->labels ? 8.0 : 0.0)),
+          argmax_rows(logits, pr->labels, V0, K, pr->use_ignore, pr->ignore, pr->mask, pr->conf,
+                      p->st));
   return SPFF_OK;
 }
 
@@ -1544,8 +1673,32 @@ int spff_forward(spff_plan* p, const float* x, const float* params, float* logit
   return coll_status(p, rc, "spff_forward");
 }
 
+int spff_predict(spff_plan* p, const float* x, const float* params, uint8_t* mask, float* logits,
+                 const int64_t* labels, int use_ignore, int ignore_index, int64_t* conf, void* ws,
+                 void* stream) {
+  if (!p || !x || !params || !mask || !ws) return fail(SPFF_EINVAL, "null argument");
+  if ((labels == nullptr) != (conf == nullptr))
+    return fail(SPFF_EINVAL, "spff_predict: conf is given exactly when labels are");
+  if (p->K > 255) return fail(SPFF_EINVAL, "spff_predict: the class index is a byte (K <= 255)");
+  if (!logits && !head_streams(p->f, p->K))
+    return fail(SPFF_EINVAL, "spff_predict: logits must be given where the streaming head does "
+                             "not cover the plan (base 32 or 64, K <= 32)");
+  p->bind(ws, params, nullptr, stream);
+  if (p->co.on() && !p->coll_set)
+    return fail(SPFF_EINVAL, "depth-sharded plan: call spff_plan_set_coll first");
+  CK(ensure_pe(p));
+  p->co.failed = nullptr;
+  p->halo_early = nullptr;
+  const Predict pr{mask, labels, use_ignore != 0, ignore_index, conf};
+  const int rc = forward(p, x, logits, &pr);
+  p->halo_early = nullptr;
+  return coll_status(p, rc, "spff_predict");
+}
+
 int spff_backward(spff_plan* p, const float* dlogits, const float* params, float* dparams,
                   void* ws, void* stream) {
+  if (p && p->infer)
+    return fail(SPFF_EINVAL, "forward-only plan (SPFF_MEM_INFER): nothing is kept for a backward");
   if (!p || !dlogits || !params || !dparams || !ws) return fail(SPFF_EINVAL, "null argument");
   p->bind(ws, params, dparams, stream);
   if (p->co.on() && !p->coll_set)
@@ -1563,6 +1716,15 @@ int spff_saved_tensor(const spff_plan* p, void* ws, const char* name, const floa
   const std::string n(name);
   const SavedOut ret{ws, ptr, nv, ch};
   if (n == "x_cl") return ret(p->x_cl, p->vol[0], p->ldx);
+  if (p->infer) {
+    // a forward-only plan keeps the input, the pools, the per-(b,c) coefficients and the
+    // last conv output; every other activation's place is reused within the forward
+    const auto dot = n.find('.');
+    const std::string tail = dot == std::string::npos ? "" : n.substr(dot + 1);
+    const bool coef = tail == "al1" || tail == "de1" || tail == "al2" || tail == "de2";
+    if (!(n.rfind("pool", 0) == 0 || coef || n == "dec1.y2"))
+      return fail(SPFF_EINVAL, "forward-only plan (SPFF_MEM_INFER) does not keep " + n);
+  }
   if (n.rfind("grad.", 0) == 0) {  // backward scratch, sized as level-0 [V0][f]
     const size_t off = n == "grad.out" ? p->G_out : n == "grad.dy2" ? p->G_dy2 :
                        n == "grad.da1" ? p->G_da1 : n == "grad.dx" ? p->G_dx : 0;
@@ -1626,6 +1788,7 @@ int spff_debug_set(spff_plan* p, int key, int value) {
   if (key == 2) p->pool_fold = value != 0;  // 0: k_maxpool_bwd_add pass instead of PoolAdd
   if (key == 3) p->bst_fuse = value != 0;   // 0: conv1's IN-backward sums by a slab_reduce pass
   if (key == 4) p->head_fold = value != 0;  // 0: head_wgrad + head_dgrad + dec1's tail reduction
+  if (key == 5) p->head_only = value != 0;  // the head alone, on the previous forward's workspace
   return SPFF_OK;
 }
 

@@ -1518,88 +1518,167 @@ static bool head_stream_ok(int Cin, int K) {
   }();
   return !off && (Cin == 32 || Cin == 64) && K >= 1 && K <= 32;
 }
+// The streaming head's tile walk, shared by k_head_fwd_s and k_head_mask_s: rows
+// [r0, r0 + nr) of A into tile [256][C + 1], loaded as coalesced float4 with the loader's
+// activation applied (Q quads per thread in flight).  The caller synchronises.
+template <int C, class L>
+__device__ __forceinline__ void head_stage_rows(const L& A, int64_t r0, int nr, float* tile) {
+  constexpr int CP = C + 1, Q = C / 4;
+  const int tid = threadIdx.x;
+  float4 v[Q];
+  bool done = false;
+  if constexpr (std::is_same<L, LoadRowsAct>::value) {
+    // HW % 256 == 0: the block's 256 rows share one (b, d), and thread tid always takes
+    // channel quad tid % Q, so its activation coefficients load once per block
+    if (A.HW % 256 == 0) {
+      const int64_t bd = r0 / A.HW, b = bd / A.D;
+      const int c = 4 * (tid % Q);
+      const float4 a = *reinterpret_cast<const float4*>(A.al + b * A.ld + c);
+      const float4 e = *reinterpret_cast<const float4*>(A.de + b * A.ld + c);
+      float4 pp = make_float4(1.f, 1.f, 1.f, 1.f), qq = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (A.PT) {
+        pp = *reinterpret_cast<const float4*>(A.PT + bd * A.ld + c);
+        qq = *reinterpret_cast<const float4*>(A.QT + bd * A.ld + c);
+      }
+#pragma unroll
+      for (int j = 0; j < Q; ++j) {
+        const int rr = (tid + j * 256) / Q;
+        v[j] = *reinterpret_cast<const float4*>(A.p + (r0 + (rr < nr ? rr : 0)) * A.ld + c);
+      }
+      auto f = [&](float y, float a_, float e_, float p_, float q_) {  // LoadRowsAct::load4's
+        const float t = y * a_ + e_;
+        return (t > 0.f ? t : A.neg * t) * p_ + q_;
+      };
+#pragma unroll
+      for (int j = 0; j < Q; ++j)
+        v[j] = make_float4(f(v[j].x, a.x, e.x, pp.x, qq.x), f(v[j].y, a.y, e.y, pp.y, qq.y),
+                           f(v[j].z, a.z, e.z, pp.z, qq.z), f(v[j].w, a.w, e.w, pp.w, qq.w));
+      done = true;
+    }
+  }
+  if (!done) {
+#pragma unroll
+    for (int j = 0; j < Q; ++j) {  // Q quads per thread in flight
+      const int i = tid + j * 256, rr = i / Q;
+      v[j] = A.load4(A.prep(r0 + (rr < nr ? rr : 0)), 4 * (i % Q));
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < Q; ++j) {
+    const int i = tid + j * 256;
+    float* t = tile + (i / Q) * CP + 4 * (i % Q);
+    t[0] = v[j].x; t[1] = v[j].y; t[2] = v[j].z; t[3] = v[j].w;
+  }
+}
+// thread tid's row of the staged tile times W = wd [K][dn]: o[k] = the fmaf chain over c
+// ascending from 0, bias added last (the head's logits; 0 for k >= K)
+template <int C, int KM>
+__device__ __forceinline__ void head_row_dots(const float* tile, const float* __restrict__ wd,
+                                              int dn, const float* __restrict__ bias, int K,
+                                              float (&o)[KM]) {
+  constexpr int CP = C + 1;
+  float a[C];
+#pragma unroll
+  for (int c = 0; c < C; ++c) a[c] = tile[threadIdx.x * CP + c];
+#pragma unroll
+  for (int k = 0; k < KM; ++k) {
+    float s = 0.f;
+    if (k < K) {
+#pragma unroll
+      for (int c = 0; c < C; ++c) s = fmaf(a[c], wd[k * dn + c], s);
+      s += bias ? bias[k] : 0.f;
+    }
+    o[k] = s;
+  }
+}
+// the block's [nr][K] outputs o (one row per thread) through the tile to y + r0 K, coalesced.
+// The caller has synchronised after the last read of the staged rows; synchronises at the end.
+template <int KM>
+__device__ __forceinline__ void head_store_rows(const float (&o)[KM], float* tile,
+                                                float* __restrict__ y, int64_t r0, int nr, int K) {
+  const int tid = threadIdx.x;
+#pragma unroll
+  for (int k = 0; k < KM; ++k)
+    if (k < K) tile[tid * K + k] = o[k];
+  __syncthreads();
+  const int n = nr * K;
+  float* yb = y + r0 * K;  // 16-B aligned: r0 is a multiple of 256
+  for (int i = tid; i < n / 4; i += 256)
+    reinterpret_cast<float4*>(yb)[i] =
+        make_float4(tile[4 * i], tile[4 * i + 1], tile[4 * i + 2], tile[4 * i + 3]);
+  for (int i = (n / 4) * 4 + tid; i < n; i += 256) yb[i] = tile[i];
+  __syncthreads();
+}
 template <int C, int KM, class L>
 __global__ __launch_bounds__(256) void k_head_fwd_s(L A, const float* __restrict__ wd, int dn,
                                                     const float* __restrict__ bias,
                                                     float* __restrict__ y, int64_t V, int K) {
-  constexpr int CP = C + 1, Q = C / 4;
-  __shared__ float tile[256 * CP];
-  const int tid = threadIdx.x;
+  __shared__ float tile[256 * (C + 1)];
   for (int64_t r0 = (int64_t)blockIdx.x * 256; r0 < V; r0 += (int64_t)gridDim.x * 256) {
     const int nr = (int)(V - r0 < 256 ? V - r0 : 256);
-    float4 v[Q];
-    bool done = false;
-    if constexpr (std::is_same<L, LoadRowsAct>::value) {
-      // HW % 256 == 0: the block's 256 rows share one (b, d), and thread tid always takes
-      // channel quad tid % Q, so its activation coefficients load once per block
-      if (A.HW % 256 == 0) {
-        const int64_t bd = r0 / A.HW, b = bd / A.D;
-        const int c = 4 * (tid % Q);
-        const float4 a = *reinterpret_cast<const float4*>(A.al + b * A.ld + c);
-        const float4 e = *reinterpret_cast<const float4*>(A.de + b * A.ld + c);
-        float4 pp = make_float4(1.f, 1.f, 1.f, 1.f), qq = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (A.PT) {
-          pp = *reinterpret_cast<const float4*>(A.PT + bd * A.ld + c);
-          qq = *reinterpret_cast<const float4*>(A.QT + bd * A.ld + c);
-        }
-#pragma unroll
-        for (int j = 0; j < Q; ++j) {
-          const int rr = (tid + j * 256) / Q;
-          v[j] = *reinterpret_cast<const float4*>(A.p + (r0 + (rr < nr ? rr : 0)) * A.ld + c);
-        }
-        auto f = [&](float y, float a_, float e_, float p_, float q_) {  // LoadRowsAct::load4's
-          const float t = y * a_ + e_;
-          return (t > 0.f ? t : A.neg * t) * p_ + q_;
-        };
-#pragma unroll
-        for (int j = 0; j < Q; ++j)
-          v[j] = make_float4(f(v[j].x, a.x, e.x, pp.x, qq.x), f(v[j].y, a.y, e.y, pp.y, qq.y),
-                             f(v[j].z, a.z, e.z, pp.z, qq.z), f(v[j].w, a.w, e.w, pp.w, qq.w));
-        done = true;
-      }
-    }
-    if (!done) {
-#pragma unroll
-      for (int j = 0; j < Q; ++j) {  // Q quads per thread in flight
-        const int i = tid + j * 256, rr = i / Q;
-        v[j] = A.load4(A.prep(r0 + (rr < nr ? rr : 0)), 4 * (i % Q));
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < Q; ++j) {
-      const int i = tid + j * 256;
-      float* t = tile + (i / Q) * CP + 4 * (i % Q);
-      t[0] = v[j].x; t[1] = v[j].y; t[2] = v[j].z; t[3] = v[j].w;
-    }
+    head_stage_rows<C>(A, r0, nr, tile);
     __syncthreads();
     float o[KM];
-    {
-      float a[C];
+    head_row_dots<C, KM>(tile, wd, dn, bias, K, o);
+    __syncthreads();
+    head_store_rows<KM>(o, tile, y, r0, nr, K);
+  }
+}
+// The fused class-mask head (spff_predict): k_head_fwd_s's tile walk and logits, bit for
+// bit, then per row the first-maximum class (spff_confusion's rule: a NaN counts as the
+// largest) as one byte -- the block's 256 bytes leave through LDS as 16-B stores (a byte
+// store per lane is a fabric write each) -- and, with labels, the (pred, label) cell of a
+// per-block LDS histogram [K][K + 1] whose non-zero bins go to conf by 64-bit integer
+// atomics after the tile loop (column K: a label outside [0, K); ignored voxels skipped).
+// LOGITS: also store the [256][K] tile as k_head_fwd_s does; else y is not touched.
+template <int C, int KM, class L, bool LOGITS>
+__global__ __launch_bounds__(256) void k_head_mask_s(L A, const float* __restrict__ wd, int dn,
+                                                     const float* __restrict__ bias,
+                                                     float* __restrict__ y,
+                                                     uint8_t* __restrict__ mask,
+                                                     const int64_t* __restrict__ lab,
+                                                     int use_ignore, int ignore,
+                                                     unsigned long long* __restrict__ conf,
+                                                     int64_t V, int K) {
+  __shared__ float tile[256 * (C + 1)];
+  __shared__ __attribute__((aligned(16))) uint8_t pm[256];
+  __shared__ unsigned hist[32 * 33];
+  const int tid = threadIdx.x, K1 = K + 1;
+  if (lab)
+    for (int i = tid; i < K * K1; i += 256) hist[i] = 0;  // (ordered by the loop's barriers)
+  const bool m16 = !(reinterpret_cast<uintptr_t>(mask) & 15);
+  for (int64_t r0 = (int64_t)blockIdx.x * 256; r0 < V; r0 += (int64_t)gridDim.x * 256) {
+    const int nr = (int)(V - r0 < 256 ? V - r0 : 256);
+    // (the label first: its load overlaps the row fetch)
+    const int64_t yl = (lab && tid < nr) ? lab[r0 + tid] : 0;
+    head_stage_rows<C>(A, r0, nr, tile);
+    __syncthreads();
+    float o[KM];
+    head_row_dots<C, KM>(tile, wd, dn, bias, K, o);
+    float m = o[0];
+    int am = 0;
 #pragma unroll
-      for (int c = 0; c < C; ++c) a[c] = tile[tid * CP + c];
-#pragma unroll
-      for (int k = 0; k < KM; ++k) {
-        float s = 0.f;
-        if (k < K) {
-#pragma unroll
-          for (int c = 0; c < C; ++c) s = fmaf(a[c], wd[k * dn + c], s);
-          s += bias ? bias[k] : 0.f;
-        }
-        o[k] = s;
+    for (int k = 1; k < KM; ++k)
+      if (k < K) {
+        const float t = o[k];
+        if (t > m || (isnan(t) && !isnan(m))) { m = t; am = k; }
       }
+    pm[tid] = (uint8_t)am;
+    if (lab && tid < nr && (!use_ignore || yl != ignore))
+      atomicAdd(&hist[am * K1 + ((yl < 0 || yl >= K) ? K : (int)yl)], 1u);
+    __syncthreads();
+    if (m16 && nr == 256) {
+      if (tid < 16) reinterpret_cast<uint4*>(mask + r0)[tid] = reinterpret_cast<const uint4*>(pm)[tid];
+    } else if (tid < nr) {
+      mask[r0 + tid] = pm[tid];
     }
+    // (the next trip writes pm only after its own staging barrier)
+    if constexpr (LOGITS) head_store_rows<KM>(o, tile, y, r0, nr, K);
+  }
+  if (lab) {
     __syncthreads();
-#pragma unroll
-    for (int k = 0; k < KM; ++k)
-      if (k < K) tile[tid * K + k] = o[k];
-    __syncthreads();
-    const int n = nr * K;
-    float* yb = y + r0 * K;  // 16-B aligned: r0 is a multiple of 256
-    for (int i = tid; i < n / 4; i += 256)
-      reinterpret_cast<float4*>(yb)[i] =
-          make_float4(tile[4 * i], tile[4 * i + 1], tile[4 * i + 2], tile[4 * i + 3]);
-    for (int i = (n / 4) * 4 + tid; i < n; i += 256) yb[i] = tile[i];
-    __syncthreads();
+    for (int i = tid; i < K * K1; i += 256)
+      if (hist[i]) atomicAdd(&conf[i], (unsigned long long)hist[i]);
   }
 }
 template <int C, int KM>
@@ -1702,6 +1781,50 @@ hipError_t head_fwd(const float* x, const float* wf, const float* b, float* y, i
                        gemm_split(math));
   LoadRowsVec A{x, Cin, Cin, V};
   return launch_gemm(A, wf, C, V, head_fk(Cin), head_fn(K), s, gemm_split(math));
+}
+
+constexpr unsigned HEAD_MASK_GRID = 1024;
+template <int C, int KM, class L>
+static hipError_t head_mask_s(const L& A, const float* wd, const float* b, float* y, uint8_t* mask,
+                              const int64_t* lab, int use_ignore, int ignore, int64_t* conf,
+                              int64_t V, int K, hipStream_t s) {
+  // with labels every block ends in up to K (K + 1) 64-bit atomics on the same few cells:
+  // one resident wave of blocks (4 per CU), each walking more tiles, not 8192 of them
+  const dim3 g(lab ? std::min(head_grid(V), HEAD_MASK_GRID) : head_grid(V)), t(256);
+  unsigned long long* cf = reinterpret_cast<unsigned long long*>(conf);
+  const int dn = head_dn(C);
+  if (y)
+    hipLaunchKernelGGL((k_head_mask_s<C, KM, L, true>), g, t, 0, s, A, wd, dn, b, y, mask, lab,
+                       use_ignore, ignore, cf, V, K);
+  else
+    hipLaunchKernelGGL((k_head_mask_s<C, KM, L, false>), g, t, 0, s, A, wd, dn, b, y, mask, lab,
+                       use_ignore, ignore, cf, V, K);
+  return hipGetLastError();
+}
+template <class L>
+static hipError_t head_mask_stream(const L& A, const float* wd, int Cin, const float* b, float* y,
+                                   uint8_t* mask, const int64_t* lab, int use_ignore, int ignore,
+                                   int64_t* conf, int64_t V, int K, hipStream_t s) {
+  if (Cin == 32)
+    return K <= 16 ? head_mask_s<32, 16>(A, wd, b, y, mask, lab, use_ignore, ignore, conf, V, K, s)
+                   : head_mask_s<32, 32>(A, wd, b, y, mask, lab, use_ignore, ignore, conf, V, K, s);
+  return K <= 16 ? head_mask_s<64, 16>(A, wd, b, y, mask, lab, use_ignore, ignore, conf, V, K, s)
+                 : head_mask_s<64, 32>(A, wd, b, y, mask, lab, use_ignore, ignore, conf, V, K, s);
+}
+bool head_mask_streams(const float* x, const float* y, int Cin, int K, const ActRows* act) {
+  return head_stream_ok(Cin, K) && !(reinterpret_cast<uintptr_t>(y) & 15) &&
+         (act ? act_ok(act, Cin) : !(reinterpret_cast<uintptr_t>(x) & 15));
+}
+hipError_t head_mask(const float* x, const float* wf, const float* b, float* y, uint8_t* mask,
+                     const int64_t* lab, int use_ignore, int ignore, int64_t* conf, int64_t V,
+                     int Cin, int K, hipStream_t s, const ActRows* act) {
+  if (!head_mask_streams(x, y, Cin, K, act)) return hipErrorInvalidValue;
+  const float* wd = wf + head_pack_dgrad_offset(Cin, K);
+  if (act)
+    return head_mask_stream(act_loader(*act, Cin, V), wd, Cin, b, y, mask, lab, use_ignore, ignore,
+                            conf, V, K, s);
+  return head_mask_stream(LoadRowsVec{x, Cin, Cin, V}, wd, Cin, b, y, mask, lab, use_ignore,
+                          ignore, conf, V, K, s);
 }
 
 hipError_t head_pack(const float* w, float* wf, float* wd, int Cin, int K, hipStream_t s) {

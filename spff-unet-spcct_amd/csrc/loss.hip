@@ -10,6 +10,7 @@
 // kernel computes ce, the hard-Dice term and the loss on the device.
 #include "spff_internal.h"
 #include <math.h>
+#include <algorithm>
 
 namespace spff {
 
@@ -346,6 +347,91 @@ hipError_t loss_fwd(const float* logits, const int64_t* labels, int64_t V, int K
   if ((e = hipGetLastError()) != hipSuccess) return e;
   hipLaunchKernelGGL(k_loss_final, dim3(1), dim3(LOSS_T), 0, s, part, LOSS_GRID, cptr,
                      reinterpret_cast<unsigned long long*>(conf), K, smooth, out4, clamp1);
+  return hipGetLastError();
+}
+
+// The class mask of stored logits rows (spff_predict where the streaming head does not
+// cover the plan): k_loss's wave-staged row walk and argmax rule (first maximum, a NaN
+// counts as the largest), the class index as one byte -- a wave's 64 bytes leave through
+// LDS as four 16-B stores -- and, with labels, k_loss's confusion histogram (use_ignore = 0:
+// no voxel is skipped).  Reads K 4 B and writes 1 B per voxel.
+__global__ __launch_bounds__(LOSS_T) void k_argmax_rows(const float* __restrict__ x,
+                                                        const int64_t* __restrict__ lab, int64_t V,
+                                                        int K, int use_ignore, int ignore,
+                                                        uint8_t* __restrict__ mask,
+                                                        unsigned long long* __restrict__ conf) {
+  extern __shared__ __attribute__((aligned(16))) float stage[];
+  __shared__ __attribute__((aligned(16))) uint8_t pm[LOSS_T];
+  const int K1 = K + 1;
+  const bool lh = K <= KHIST_LDS;
+  unsigned int* hist = reinterpret_cast<unsigned int*>(stage + LOSS_WAVES * 64 * K);
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  float* sx = stage + wv * 64 * K;
+  if (lab && lh)
+    for (int i = threadIdx.x; i < K * K1; i += LOSS_T) hist[i] = 0;
+  __syncthreads();
+  const bool m16 = !(reinterpret_cast<uintptr_t>(mask) & 15);
+  const int64_t ngroups = (V + 63) / 64;
+  for (int64_t grp = (int64_t)blockIdx.x * LOSS_WAVES + wv; grp < ngroups;
+       grp += (int64_t)gridDim.x * LOSS_WAVES) {
+    const int64_t v0 = grp * 64;
+    const int nv = (int)(V - v0 < 64 ? V - v0 : 64);
+    const int64_t y = (lab && lane < nv) ? lab[v0 + lane] : 0;  // (overlaps the row copy)
+    wave_copy_rows(sx, x + v0 * K, nv * K, lane);
+    wave_lds_sync();
+    int cell = -1;
+    if (lane < nv) {
+      const float* xr = sx + lane * K;
+      float m = xr[0];
+      int am = 0;
+      for (int k = 1; k < K; ++k) {
+        const float t = xr[k];
+        if (t > m || (isnan(t) && !isnan(m))) { m = t; am = k; }
+      }
+      pm[threadIdx.x] = (uint8_t)am;
+      if (lab && (!use_ignore || y != ignore)) cell = am * K1 + ((y < 0 || y >= K) ? K : (int)y);
+    }
+    if (lh) {
+      if (cell >= 0) atomicAdd(&hist[cell], 1u);
+    } else {  // one atomic per distinct cell per wave (k_loss)
+      unsigned long long todo = __ballot(cell >= 0);
+      while (todo) {
+        const int leader = __builtin_ctzll(todo);
+        const int c = __shfl(cell, leader);
+        const unsigned long long same = __ballot(cell == c) & todo;
+        if (lane == leader) atomicAdd(&conf[c], (unsigned long long)__popcll(same));
+        todo &= ~same;
+      }
+    }
+    wave_lds_sync();
+    if (m16 && nv == 64) {
+      if (lane < 4)
+        reinterpret_cast<uint4*>(mask + v0)[lane] = reinterpret_cast<const uint4*>(pm + wv * 64)[lane];
+    } else if (lane < nv) {
+      mask[v0 + lane] = pm[threadIdx.x];
+    }
+    wave_lds_sync();  // the next group overwrites the slice and the bytes
+  }
+  __syncthreads();
+  if (lab && lh)
+    for (int i = threadIdx.x; i < K * K1; i += LOSS_T)
+      if (hist[i]) atomicAdd(&conf[i], (unsigned long long)hist[i]);
+}
+
+hipError_t argmax_rows(const float* logits, const int64_t* labels, int64_t V, int K,
+                       int use_ignore, int ignore, uint8_t* mask, int64_t* conf, hipStream_t s) {
+  if (K > KMAX || K < 1) return hipErrorInvalidValue;
+  static int granted = 0;
+  const int shm = (int)loss_lds(K);
+  if (shm > 65536 && shm > granted) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_argmax_rows),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, shm);
+    if (e != hipSuccess) return e;
+    granted = shm;
+  }
+  const unsigned grid = (unsigned)std::min<int64_t>((V + LOSS_T - 1) / LOSS_T, LOSS_GRID);
+  hipLaunchKernelGGL(k_argmax_rows, dim3(grid), dim3(LOSS_T), shm, s, logits, labels, V, K,
+                     use_ignore, ignore, mask, reinterpret_cast<unsigned long long*>(conf));
   return hipGetLastError();
 }
 

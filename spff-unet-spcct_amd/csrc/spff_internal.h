@@ -295,6 +295,15 @@ hipError_t head_wgrad(const float* x, const float* dy, float* dw, float* db, int
                       int Cin, int K, float* ws, hipStream_t s, const ActRows* act = nullptr);
 // the streaming head kernels take (Cin, K): Cin = 32 or 64, K <= 32, SPFF_HEAD_STREAM != 0
 bool head_streams(int Cin, int K);
+// The fused class-mask head (spff_predict): head_fwd's streaming kernel with, per row, the
+// first-maximum class as a byte of mask [V] and -- lab non-null -- the (pred, label) counts
+// added to conf [K][K + 1] (zeroed by the caller; spff_confusion's columns, use_ignore = 0:
+// no voxel skipped).  y null: the logits are not written; else bitwise head_fwd's.
+// head_mask_streams: the streaming kernel takes these operands (else hipErrorInvalidValue).
+bool head_mask_streams(const float* x, const float* y, int Cin, int K, const ActRows* act);
+hipError_t head_mask(const float* x, const float* wf, const float* b, float* y, uint8_t* mask,
+                     const int64_t* lab, int use_ignore, int ignore, int64_t* conf, int64_t V,
+                     int Cin, int K, hipStream_t s, const ActRows* act = nullptr);
 // the dlogits rows and the packed head weight (head_pack's image pk) as a HeadSrc
 HeadSrc head_src(const float* dl, const float* pk, int Cin, int K);
 // fixed-order sum of head_tail_bwd's nwg per-workgroup partials part [nwg][Cin][32] and
@@ -622,6 +631,9 @@ hipError_t count_valid(const int64_t* labels, int64_t V, int ignore, int64_t* co
                        hipStream_t s);
 hipError_t confusion_only(const float* logits, const int64_t* labels, int64_t V, int K,
                           int ignore, int64_t* conf, hipStream_t s);
+// the same mask and counts from stored logits rows [V][K] (labels null: the mask alone)
+hipError_t argmax_rows(const float* logits, const int64_t* labels, int64_t V, int K,
+                       int use_ignore, int ignore, uint8_t* mask, int64_t* conf, hipStream_t s);
 // The variants' soft-Dice (+ CE) losses (soft_dice.hip): one statistics pass and one
 // gradient pass over channel-last rows (vps voxels per sample), with the reference's formula
 // in the finaliser between them.  dlogits [V][K] = dloss/dlogits; use_ignore = 0: no voxel

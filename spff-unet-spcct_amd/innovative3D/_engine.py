@@ -109,15 +109,17 @@ GRAD_READY_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, 
 
 
 # saved-activation layout (include/spff.h SPFF_MEM_*)
-MEMORY_MODES = {"auto": 0, "full": 1, "lean": 2}
+# ("infer": the forward-only layout, SPFF_MEM_INFER -- asked for by name, never a default)
+MEMORY_MODES = {"auto": 0, "full": 1, "lean": 2, "infer": 3}
+_DEFAULT_MEMORY_MODES = ("auto", "full", "lean")
 
 
 def default_memory() -> str:
     """Saved-activation layout for new plans: $SPFF_MEMORY, else "auto" (lean from 2^26
     voxels per plan)."""
     m = os.environ.get("SPFF_MEMORY", "auto")
-    if m not in MEMORY_MODES:
-        raise SpffError(f"SPFF_MEMORY={m!r}: expected one of {sorted(MEMORY_MODES)}")
+    if m not in _DEFAULT_MEMORY_MODES:
+        raise SpffError(f"SPFF_MEMORY={m!r}: expected one of {sorted(_DEFAULT_MEMORY_MODES)}")
     return m
 
 
@@ -182,6 +184,7 @@ _SIGS = {
     "spff_plan_set_coll": (_I, [_P, ctypes.POINTER(spff_coll)]),
     "spff_plan_set_grad_hook": (_I, [_P, GRAD_READY_FN, _P]),
     "spff_last_error": (ctypes.c_char_p, []),
+    "spff_predict": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P]),
     "spff_debug_set": (_I, [_P, _I, _I]),
     "spff_prof_enable": (_I, [_P, _I]),
     "spff_prof_collect": (_I, [_P, ctypes.POINTER(ctypes.c_double), _I]),
@@ -452,7 +455,7 @@ class Plan(_PlanBase):
         attn = bool(spatial) or bool(skip_gate)
         # the layout the engine resolves (engine.hip build_plan: lean from 2^26 voxels on auto)
         voxels = cfg.batch * cfg.depth * cfg.height * cfg.width
-        self.layout = ("lean" if memory == "lean" or
+        self.layout = ("infer" if memory == "infer" else "lean" if memory == "lean" or
                        (memory == "auto" and voxels >= 1 << 26 and not attn) else "full")
         # axis 0 = SPFF_SHARD_DEPTH (BASELINE config 4), 1 = SPFF_SHARD_HEIGHT (registry layout)
         cfg.shard_world, cfg.shard_rank, cfg.shard_axis = self.shard = shard
@@ -571,6 +574,8 @@ class Plan(_PlanBase):
         (innovative3D.distributed.GradBucketer); ready() is called while the
         backward is being enqueued, as each parameter group's gradient becomes
         final, and finish() after it."""
+        if self.layout == "infer":  # before any device call
+            raise SpffError("forward-only plan (memory='infer'): nothing is kept for a backward")
         dlogits_cl = dlogits_cl.contiguous()
         if dflat is None:
             dflat = torch.empty(self.nfloats, dtype=torch.float32, device=dlogits_cl.device)
@@ -625,6 +630,46 @@ class Plan(_PlanBase):
                 # group's timeout ends any collective a peer is left waiting in)
                 grad_hook.abort()
         return dflat
+
+    def streams_head(self) -> bool:
+        """The streaming head covers this plan (gemm.hip head_streams: base 32 or 64, K <= 32):
+        predict then never writes the logits unless asked."""
+        return (self.cfg.base in (32, 64) and 1 <= self.cfg.num_classes <= 32
+                and os.environ.get("SPFF_HEAD_STREAM", "1")[:1] != "0")
+
+    def predict(self, x: torch.Tensor, flat: torch.Tensor, labels: Optional[torch.Tensor] = None,
+                ignore_index: Optional[int] = None, want_logits: bool = False):
+        """spff_predict: x [B,Cin,D,H,W] -> (mask uint8 [B,D,H,W], conf int64 [K,K+1] or None,
+        logits channel-last [B,D,H,W,K] or None).  ``labels`` [B,D,H,W]: also the confusion
+        counts, as confusion() of the same logits (``ignore_index`` None: no voxel masked).
+        Where the streaming head does not cover the plan the logits are allocated here (the
+        row-argmax pass reads them) and returned only when ``want_logits``."""
+        c = self.cfg
+        require_device(x, f"{self.NAME} predict")
+        if tuple(x.shape) != (c.batch, c.in_ch, c.depth, c.height, c.width):
+            raise SpffError(f"input shape {tuple(x.shape)} does not match plan")
+        if x.dtype != torch.float32:
+            raise SpffError("the engine computes in fp32; got " + str(x.dtype))
+        x = x.contiguous()
+        dev, K = x.device, c.num_classes
+        vol = (c.batch, c.depth, c.height, c.width)
+        mask = torch.empty(vol, dtype=torch.uint8, device=dev)
+        logits = conf = None
+        if want_logits or not self.streams_head():
+            logits = torch.empty(vol + (K,), dtype=torch.float32, device=dev)
+        if labels is not None:
+            labels = labels.to(device=dev, dtype=torch.int64).contiguous()
+            if labels.numel() != mask.numel():
+                raise SpffError(f"labels {tuple(labels.shape)} do not match the volume {vol}")
+            conf = torch.empty(K * (K + 1), dtype=torch.int64, device=dev)
+        ws = self.workspace(dev)
+        self.generation += 1
+        self.coll_error = None
+        self._check(lib().spff_predict(self._h, _ptr(x), _ptr(flat), _ptr(mask), _ptr(logits),
+                                       _ptr(labels), *_ignore_args(ignore_index), _ptr(conf),
+                                       _ptr(ws), _stream(dev)), "spff_predict")
+        return (mask, None if conf is None else conf.view(K, K + 1),
+                logits if want_logits else None)
 
     PROF_CLASSES = ("conv_fwd", "conv_dgrad", "conv_wgrad", "gemm", "slab_reduce", "act_apply",
                     "in_bwd_apply", "f16_absmax")

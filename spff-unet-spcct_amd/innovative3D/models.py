@@ -380,7 +380,9 @@ class UNet3D_SpectralCore(_FlatParamMixin, nn.Module):
         return {"efilm_hidden": h, "efilm_pe_dims": pdim,
                 "fgate_learn_phase": bool(next(iter(ph))) if ph else False}
 
-    def _engine_plan(self, x: torch.Tensor, tag: str):
+    def _engine_plan(self, x: torch.Tensor, tag: str, memory: Optional[str] = None):
+        """``memory``: the layout of this plan instead of the module's ``.memory``"""
+        memory = memory or getattr(self, "memory", None)
         B, C, D, H, W = x.shape
         if C != self.in_channels:
             raise ValueError(f"expected {self.in_channels} input channels, got {C}")
@@ -393,9 +395,10 @@ class UNet3D_SpectralCore(_FlatParamMixin, nn.Module):
             if shard[0] > 1:
                 raise E.SpffError("use_spatial / use_skip_gate run on unsharded modules only: the "
                                   "3x7x7 stencil needs halos the shard collectives do not carry")
-            if getattr(self, "memory", None) == "lean":
+            if memory in ("lean", "infer"):
                 raise E.SpffError("use_spatial / use_skip_gate: the lean layout does not "
-                                  "recompute them; use memory 'full' or 'auto'")
+                                  "recompute them and the forward-only one does not place "
+                                  "them; use memory 'full' or 'auto'")
             if self.use_skip_gate and (H % 8 or W % 8):
                 raise E.SpffError("use_skip_gate needs H and W multiples of 8: the reference's "
                                   "gate fails where an up-conv output and its skip differ")
@@ -406,7 +409,7 @@ class UNet3D_SpectralCore(_FlatParamMixin, nn.Module):
                           num_classes=self.num_classes, base=self.base, ksd=self.ksd,
                           efilm=efilm, fgate=fgate, se=self.use_se, specse=self.use_specse,
                           device=x.device, math=getattr(self, "math", None), shard=shard,
-                          memory=getattr(self, "memory", None), spatial=self.use_spatial,
+                          memory=memory, spatial=self.use_spatial,
                           skip_gate=self.use_skip_gate,
                           owner=self, tag=tag, **self._gate_settings())
         if shard[0] > 1:
@@ -421,6 +424,9 @@ class UNet3D_SpectralCore(_FlatParamMixin, nn.Module):
         x = _pick_first_if_seq(x)
         E.require_device(x, "UNet3D_SpectralCore.forward")
         need_grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
+        if need_grad and getattr(self, "memory", None) == "infer":
+            raise E.SpffError("memory = 'infer' is the forward-only layout: run the forward "
+                              "under torch.no_grad(), or leave .memory unset to train")
         plan = self._engine_plan(x, "train" if need_grad else "infer")
         params = self._engine_params(plan)
         flat = self._ensure_flat(plan, params, x.device)
@@ -428,8 +434,31 @@ class UNet3D_SpectralCore(_FlatParamMixin, nn.Module):
             self._plan = plan
             return _PlanFunction.apply(x.float(), plan, flat, getattr(self, "grad_hook", None), (),
                                        *params)
+        self._infer_plan = plan
         logits_cl = plan.forward(x.float(), flat)
         return logits_cl.permute(0, 4, 1, 2, 3)
+
+    @torch.no_grad()
+    def predict(self, x, labels=None, ignore_index=None, return_logits=False):
+        """The segmentation of x on a forward-only plan (memory "infer"): the class mask uint8
+        [B, D, H, W] -- torch.argmax(self(x), 1), first maximum -- then, when ``labels``
+        [B, D, H, W] is given, the [K, K + 1] int64 confusion counts of per_class_metrics_3d
+        (``ignore_index`` None: no voxel masked), then, when ``return_logits``, the logits
+        [B, K, D, H, W].  Where the streaming head covers the plan the logits are never
+        written unless asked for."""
+        x = _pick_first_if_seq(x)
+        E.require_device(x, "UNet3D_SpectralCore.predict")
+        plan = self._engine_plan(x, "infer", memory="infer")
+        flat = self._ensure_flat(plan, self._engine_params(plan), x.device)
+        self._infer_plan = plan
+        mask, conf, logits_cl = plan.predict(x.float(), flat, labels, ignore_index,
+                                             want_logits=return_logits)
+        out = (mask,)
+        if labels is not None:
+            out += (conf,)
+        if return_logits:
+            out += (logits_cl.permute(0, 4, 1, 2, 3),)
+        return out[0] if len(out) == 1 else out
 
 
 def upgrade_spct_with_novel_blocks(m: nn.Module, use_efilm: bool = True, use_fouriergate: bool = True,
@@ -479,6 +508,11 @@ class BaseLitModel(pl.LightningModule):
 
     def forward(self, x):
         return self.model(self._normalize_input(x))
+
+    def predict(self, x, labels=None, ignore_index=None, return_logits=False):
+        """The core's predict (UNet3D_SpectralCore.predict) after forward's input handling"""
+        return self.model.predict(self._normalize_input(x), labels=labels,
+                                  ignore_index=ignore_index, return_logits=return_logits)
 
     def compute_loss(self, logits, labels):
         return ce_plus_macro_dice_loss(logits, labels, self.hparams.num_classes, ignore_index=IGNORE_INDEX)
@@ -542,6 +576,15 @@ class BaseLitModel(pl.LightningModule):
         return {"optimizer": opt, "lr_scheduler": {"scheduler": sch, "monitor": "val_macro_dice"}}
 
 
+def supports_predict(model) -> bool:
+    """``model.predict`` runs the engine's fused class-mask head: a BaseLitModel with the
+    plain forward over a UNet3D_SpectralCore, or that core itself."""
+    if isinstance(model, UNet3D_SpectralCore):
+        return True
+    return (isinstance(model, BaseLitModel) and type(model).forward is BaseLitModel.forward
+            and isinstance(getattr(model, "model", None), UNet3D_SpectralCore))
+
+
 class _LitSPCT_Base(BaseLitModel):
     def __init__(self, num_classes=NUM_CLASSES, lr=BEST_LR, pad_multiple: int = 16):
         super().__init__(num_classes=num_classes, lr=lr, is_3d=True)
@@ -553,6 +596,10 @@ class _LitSPCT_Base(BaseLitModel):
             x = x.unsqueeze(1)
         x_pad, orig = _pad_to_mult_3d(x, self._pad_multiple)
         return _center_crop_3d(self.model(x_pad), orig)
+
+    def predict(self, x, labels=None, ignore_index=None, return_logits=False):
+        raise NotImplementedError("predict: the padded forward of this wrapper crops its logits; "
+                                  "the fused head would count the padding's voxels")
 
 
 class LitSPCT_EFiLM_FourierGate(BaseLitModel):

@@ -86,12 +86,20 @@ def evaluate(model, dataset, K, device):
     rows = []
     model.eval()
     rank = not Hh.fast_simple_metrics()
+    # without the ranking metrics (they need the scores) the counts come from the head
+    # itself: no logits are written or read back (models.py predict)
+    fused = not rank and M.supports_predict(model)
     with torch.no_grad():
         for i in range(len(dataset)):
             x, y = dataset[i]
             x, y = x[None].to(device), y[None].to(device)
-            logits = model(x)
-            dice, sens, spec, *_ = Hh.per_class_metrics_3d(logits, y, K, ignore_index=255)
+            if fused:
+                _mask, conf = model.predict(x, labels=y, ignore_index=255)
+                dice, sens, spec, *_ = Hh.metrics_from_confusion(conf.cpu().numpy(), K,
+                                                                 int(y.numel()))
+            else:
+                logits = model(x)
+                dice, sens, spec, *_ = Hh.per_class_metrics_3d(logits, y, K, ignore_index=255)
             # each volume is a batch of one (train.py:773-798)
             rm = Hh.ranking_metrics(logits, y, K, per_sample=True) if rank else None
             for c in range(K):
