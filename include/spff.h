@@ -190,10 +190,35 @@ int spff_backward(spff_plan* plan, const float* dlogits, const float* params, fl
  * [nvox][channels] (k = 2 dh + dw of each 2 x 2 window, first max in scan order) */
 int spff_saved_tensor(const spff_plan* plan, void* workspace, const char* name,
                       const float** ptr, int64_t* nvox, int* channels);
+/* The backward's scratch, "grad.out", "grad.dy2", "grad.da1", "grad.dx" and
+ * "grad.dskip0" .. "grad.dskip2", holds the last block that ran (debug key 0 stops after a
+ * chosen one).  The four views are reported as level-0 [V0][base]; a level-l tensor is the
+ * flat prefix [V_l][C_l] of that.  After a block:
+ *   grad.dy2  the gradient at its conv2 output y2 (after the gate backward, the LeakyReLU
+ *             and the InstanceNorm backward);
+ *   grad.da1  the gradient at its conv1 output y1 (at a1 before the in-place IN backward);
+ *   grad.dx   its input gradient: for dec1..3 the up-conv half only, [V_l][C_l] (the skip
+ *             half goes to grad.dskip<l>, or to grad.dy2 when skips are gated); for bott,
+ *             enc3 and enc2 the gradient at the pool output; enc1 writes none;
+ *   grad.out  the gradient at the output of dec3, dec2 or bott, as the up-conv's input
+ *             gradient left it; at dec1's only with key 4 = 0 (the folded head never
+ *             stores it).  Lean plans reuse it and grad.dy2 within a decoder block;
+ *   grad.dskip<l>  [V_l][C_l]: after decoder block l the skip's share of the gradient at
+ *             encoder output l; after the whole backward with key 2 = 0 the total (skip +
+ *             MaxPool backward); with key 2 = 1 the readers form the total and it stays
+ *             the skip's share. */
 
-/* debug knobs (tests): key 0 = stop the backward after N decoder blocks (-1 off);
+/* debug knobs (tests):
+ * key 0 = stop the backward after N blocks: 1, 2, 3 = after dec1, dec2, dec3 (before that
+ * block's up-conv gradients), 4 = after bott, 5 = after enc3, 6 = after enc2; -1 (the
+ * default), 0 or 7 = the whole backward.  Parameter gradients of the blocks not run are
+ * left unwritten;
  * key 1 = also store the block outputs the up-conv / head GEMMs apply on the fly
  * (bott/dec*.out; otherwise spff_saved_tensor reports them as not stored);
+ * key 2 = 0: the encoder blocks' output gradient (skip + MaxPool backward) materialised by a
+ * pass of its own into grad.dskip<l>, instead of formed by its two readers (the default, 1);
+ * key 3 = 0: conv1's InstanceNorm-backward sums by a slab reduction over (da1, y1) instead
+ * of in the epilogue of the input-gradient conv that writes da1 (the default, 1);
  * key 4 = 0: the head's backward as passes of its own (weight gradient, input gradient)
  * before the last block's tail reduction, instead of folded into that block's passes;
  * key 5 = 1: spff_forward / spff_predict run the head alone, on the last block's conv output

@@ -127,10 +127,11 @@ def main():
 
 def dskip_compare(name="fx1_registry_k13"):
     """Engine (f32 / bf16x6) gradient at the encoder outputs vs the fp64 oracle
-    run with that engine's own LeakyReLU signs and pool argmaxes."""
+    run with that engine's own LeakyReLU signs and pool argmaxes (tests/_stage_oracle.py;
+    tests/test_gpu_stagewise_bwd.py asserts this and every other backward stage)."""
     from _golden import load, state_of, cfg_of
     from test_gpu_parity import load_core, engine_lrelu_masks
-    from oracle import spff_oracle as O
+    from _stage_oracle import stage_grads
     import innovative3D.helpers as Hh
     d = load(name)
     K, B = d["meta"]["K"], d["x"].shape[0]
@@ -142,43 +143,18 @@ def dskip_compare(name="fx1_registry_k13"):
         x = torch.from_numpy(d["x"]).to(DEV)
         y = torch.from_numpy(d["labels"]).to(DEV)
         logits = core(x)
+        # (key 2 = 0: grad.dskip<l> holds the total; with the default PoolAdd fold its
+        # readers form it and the view stays the skip's share)
+        core._plan.debug_set(2, 0)
         loss, _ = Hh.ce_dice_with_confusion(logits, y, K, 255)
         loss.backward()
         torch.cuda.synchronize()
         eng = {l: core._plan.saved(f"grad.dskip{l}").double().cpu() for l in range(3)}
         masks = engine_lrelu_masks(core, d)
-        posts = []
-        oc, op, opost = O.conv_in_lrelu, O.maxpool, O._post
-        npool = [0]
-
-        def hc(P_, pre, inp, ksd):
-            yy = F.conv3d(inp, P_[pre + ".0.weight"], None, padding=(ksd // 2, 1, 1))
-            r = F.instance_norm(yy, weight=P_[pre + ".1.weight"], bias=P_[pre + ".1.bias"], eps=1e-5)
-            return torch.where(masks[pre], r, 0.01 * r)
-
-        def hp(t):
-            k = npool[0] % 3
-            npool[0] += 1
-            B_, C_, D_, H_, W_ = t.shape
-            v = t.reshape(B_, C_, D_, H_ // 2, 2, W_ // 2, 2).permute(0, 1, 2, 3, 5, 4, 6)
-            v = v.reshape(B_, C_, D_, H_ // 2, W_ // 2, 4)
-            return v.gather(-1, masks[f"pool{k + 1}"].unsqueeze(-1)).squeeze(-1)
-
-        def hpost(P_, xx, stage, cfg_):
-            o = opost(P_, xx, stage, cfg_)
-            o.retain_grad()
-            posts.append(o)
-            return o
-        O.conv_in_lrelu, O.maxpool, O._post = hc, hp, hpost
-        try:
-            P = O.params_from_state(state_of(d), dtype=torch.float64)
-            O.fwd_bwd(P, torch.from_numpy(d["x"]).double(), torch.from_numpy(d["labels"]), cfg)
-        finally:
-            O.conv_in_lrelu, O.maxpool, O._post = oc, op, opost
+        run = stage_grads(cfg, state_of(d), d["x"], d["labels"], masks, torch.float64)
         for l in range(3):
-            g = posts[l].grad  # [B, C, D, H, W]
-            C = g.shape[1]
-            ref = g.permute(0, 2, 3, 4, 1).reshape(-1, C)
+            ref = torch.from_numpy(run.grad[f"enc{l + 1}.out"])  # the total, [V_l, C_l]
+            C = ref.shape[1]
             e = eng[l] - ref
             sc = ref.abs().max()
             per_d = e.view(B, Dd, H0 >> l, W0 >> l, C).pow(2).mean(dim=(0, 2, 3, 4)).sqrt() / sc

@@ -154,7 +154,7 @@ struct spff_plan : PlanBase {
   std::vector<ProfRec> prof;
   size_t prof_n = 0;
   bool prof_on = false;
-  int dbg_stop = -1;  // debug: stop backward after this many blocks (-1 = off)
+  int dbg_stop = -1;  // debug key 0: stop the backward after this many blocks (spff.h)
   bool efilm_ready = false;  // this forward's EFiLM coefficients are computed (all blocks)
   bool keep_out = false;  // debug: store the fused block outputs too (saved views)
   // the encoder blocks' output gradients (skip + MaxPool backward) are formed by their two
@@ -1561,6 +1561,7 @@ int backward(spff_plan* p, const float* dl) {
     if (B[3].sa) CK(sa_bwd_step(p, B[3], p->F(p->G_out)));
     CK(bwd_block(p, B[3], p->F(p->G_out), &dx, src1(p->F(p->pool[2]), 4 * f)));
     CK(block_grads_ready(p, B[3]));
+    if (p->dbg_stop == 4) return SPFF_OK;
   }
   for (int l = 2; l >= 0; --l) {
     const int C = f << l;
@@ -1583,6 +1584,7 @@ int backward(spff_plan* p, const float* dl) {
       CK(bwd_block(p, B[0], p->F(p->dskip[0]), nullptr, src1(p->F(p->x_cl), p->ldx), -1, pa));
     }
     CK(block_grads_ready(p, B[l]));
+    if (l > 0 && p->dbg_stop == 7 - l) return SPFF_OK;  // 5: after enc3, 6: after enc2
   }
   return SPFF_OK;
 }

@@ -688,9 +688,20 @@ class Plan(_PlanBase):
                 for i, c in enumerate(self.PROF_CLASSES)}
 
     def debug_set(self, key: int, value: int):
-        """spff_debug_set: key 0 = stop the backward after N decoder blocks, key 1 = store
-        the GEMM-applied block outputs too (saved("dec1.out") etc.), key 2 = 0: the encoder
-        output gradients by a k_maxpool_bwd_add pass instead of PoolAdd in their readers."""
+        """spff_debug_set (include/spff.h has the full account).
+        key 0: stop the backward after N blocks -- 1, 2, 3 = dec1, dec2, dec3, 4 = bott,
+        5 = enc3, 6 = enc2; -1 (default), 0 or 7 = the whole backward.
+        key 1: store the GEMM-applied block outputs too (saved("dec1.out") etc.).
+        key 2 = 0: the encoder output gradients by a k_maxpool_bwd_add pass instead of PoolAdd
+        in their readers.
+        key 3 = 0: conv1's IN-backward sums by a slab_reduce pass instead of the dgrad epilogue.
+        key 4 = 0: the head's backward as passes of its own instead of folded into dec1's.
+        key 5 = 1: the forward runs the head alone on the previous forward's workspace.
+        After a stop, saved("grad.dy2") / saved("grad.da1") hold that block's gradients at y2 /
+        y1, saved("grad.dx") its input gradient (decoder blocks: the up-conv half; the skip
+        half is saved("grad.dskip<l>")), saved("grad.out") the gradient at the output of
+        dec3, dec2 or bott (dec1: only with key 4 = 0); each grad.* view is [V0, base] and a
+        level-l tensor its flat prefix [V_l, C_l]."""
         check(lib().spff_debug_set(self._h, int(key), int(value)), "spff_debug_set")
 
     def saved(self, name: str) -> torch.Tensor:
