@@ -130,7 +130,7 @@ def dskip_compare(name="fx1_registry_k13"):
     run with that engine's own LeakyReLU signs and pool argmaxes (tests/_stage_oracle.py;
     tests/test_gpu_stagewise_bwd.py asserts this and every other backward stage)."""
     from _golden import load, state_of, cfg_of
-    from test_gpu_parity import load_core, engine_lrelu_masks
+    from _spff_checks import load_core, engine_branch_masks
     from _stage_oracle import stage_grads
     import innovative3D.helpers as Hh
     d = load(name)
@@ -150,7 +150,7 @@ def dskip_compare(name="fx1_registry_k13"):
         loss.backward()
         torch.cuda.synchronize()
         eng = {l: core._plan.saved(f"grad.dskip{l}").double().cpu() for l in range(3)}
-        masks = engine_lrelu_masks(core, d)
+        masks = engine_branch_masks(core, d["x"].shape, state_of(d), cfg)
         run = stage_grads(cfg, state_of(d), d["x"], d["labels"], masks, torch.float64)
         for l in range(3):
             ref = torch.from_numpy(run.grad[f"enc{l + 1}.out"])  # the total, [V_l, C_l]

@@ -1,10 +1,20 @@
-"""Fixture loading helpers shared by the tests (test infrastructure)."""
+"""Fixture loading and other helpers shared by the tests (test infrastructure)."""
 import json
 import pathlib
+import socket
 
 import numpy as np
 
 GOLDEN = pathlib.Path(__file__).resolve().parent / "golden"
+
+
+def free_port():
+    """a TCP port free on the loopback interface right now, for a test's own rendezvous"""
+    s = socket.socket()
+    s.bind(("127.0.0.1", 0))
+    p = s.getsockname()[1]
+    s.close()
+    return p
 
 
 def fixture_names():
@@ -25,6 +35,13 @@ def unet3d_state_of(d):
     if "class_weights" in d:
         st["class_weights"] = d["class_weights"]
     return st
+
+
+def synth_state_of(d):
+    """Regenerated state dict of a fixture that stores only its shapes and seed (R2UNet3D,
+    ResUNet++, UNETR), keys as in the module's state dict."""
+    from innovative3D.weightgen import synth_state
+    return synth_state([(k, tuple(v)) for k, v in d["state_shapes"].items()], d["meta"]["seed"])
 
 
 def load(name):

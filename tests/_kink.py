@@ -154,7 +154,7 @@ def resolve_kinks(st, x, labels, cfg, err, tol, n_cand=16, max_flips=3):
 
 class forced_branches:
     """Context manager: the oracle's LeakyReLUs and MaxPools take the given
-    branch decisions (``masks`` as tests/test_gpu_parity.engine_branch_masks
+    branch decisions (``masks`` as tests/_spff_checks.engine_branch_masks
     returns them: a bool sign mask per "<block>.<conv>" and an argmax-slot
     tensor per "pool1..3"), in whatever dtype the oracle runs."""
 

@@ -105,7 +105,7 @@ class forced_spatial:
     [B, D, H, W], likewise enc2, enc3, bott) and the gates' ReLUs the given sign pattern
     (``masks["g3.att"]`` bool [B, I, D, H, W], likewise g2, g1); keys that are absent keep
     the oracle's own decision.  A run on one sample of the batch the masks were taken from
-    (the per-sample gradient sums of tests/test_gpu_parity.oracle_grads_st, which walks the
+    (the per-sample gradient sums of tests/_spff_checks.oracle_grads_st, which walks the
     samples in order) takes that sample's slice: the n-th one-sample call of a key reads
     sample n mod B."""
 

@@ -1,6 +1,6 @@
 """Per-voxel stages of the oracle's forward and backward (test infrastructure).
 
-The parameter gradients that tests/test_gpu_parity.check_grads compares are sums over
+The parameter gradients that tests/_spff_checks.check_grads compares are sums over
 every voxel: a backward pass that is wrong on a thin set of voxels (a last partial tile,
 the last chunk of a split reduction, one (b, d) slab) moves them by far less than that
 check's 1e-3 of the tensor's scale.  ``stage_grads`` runs one oracle step and keeps, per
@@ -54,7 +54,7 @@ class StageRun:
 
 def stage_grads(cfg, st, x, labels, masks=None, dtype=torch.float64, keep_inputs=False):
     """One ``O.fwd_bwd`` with every stage retained.  ``masks`` (as
-    tests/test_gpu_parity.engine_branch_masks returns them) force the LeakyReLU signs and
+    tests/_spff_checks.engine_branch_masks returns them) force the LeakyReLU signs and
     the pool argmaxes, as tests/_kink.forced_branches does; None leaves the oracle's own
     branches -- recorded in ``.masks``, to force on another run -- and the parameter
     gradients bitwise those of a plain ``O.fwd_bwd``.

@@ -6,7 +6,6 @@ all-reduces the gradient (allreduce_gradients).  The result must equal the
 single-process full-batch gradient -- the exactness argument the engine's DP
 mode (bench.py --gpus N) relies on."""
 import os
-import socket
 
 import numpy as np
 import pytest
@@ -15,15 +14,7 @@ import torch.distributed as dist
 import torch.multiprocessing as mp
 import torch.nn.functional as F
 
-from _golden import cfg_of, load, state_of
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
+from _golden import cfg_of, free_port, load, state_of
 
 
 def _worker(rank, world, port, out_path):
@@ -59,7 +50,7 @@ def test_dp_two_ranks_equals_full_batch(tmp_path):
     d = load("fx3_fgate_even_b2")
     assert d["x"].shape[0] == 2
     out = str(tmp_path / "g.npz")
-    mp.spawn(_worker, args=(2, _free_port(), out), nprocs=2, join=True)
+    mp.spawn(_worker, args=(2, free_port(), out), nprocs=2, join=True)
     cfg = cfg_of(d["meta"])
     P = O.params_from_state(state_of(d), dtype=torch.float64)
     logits = O.forward(P, torch.from_numpy(d["x"]).double(), cfg)
@@ -130,7 +121,7 @@ def test_dp_global_loss_and_bucketed_allreduce(tmp_path):
     from oracle import spff_oracle as O
     d = load("fx3_fgate_even_b2")
     out = str(tmp_path / "l.npz")
-    mp.spawn(_worker_loss, args=(2, _free_port(), out), nprocs=2, join=True)
+    mp.spawn(_worker_loss, args=(2, free_port(), out), nprocs=2, join=True)
     got = np.load(out)
     cfg = cfg_of(d["meta"])
     K = cfg.num_classes
@@ -191,7 +182,7 @@ def _worker_timeout(rank, world, port, out_path):
 
 def test_host_staged_halo_times_out(tmp_path):
     out = str(tmp_path / "t.npz")
-    mp.spawn(_worker_timeout, args=(2, _free_port(), out), nprocs=2, join=True)
+    mp.spawn(_worker_timeout, args=(2, free_port(), out), nprocs=2, join=True)
     got = np.load(out)
     assert "did not complete within 2 s" in str(got["msg"]), str(got["msg"])
     assert float(got["dt"]) < 5.0

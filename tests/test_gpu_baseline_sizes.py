@@ -26,20 +26,23 @@ moves whole gradient tensors (observed: 5e-3 relative L2 on every parameter at
 config 2 against the unconstrained oracle).  So the logits, argmax and loss are
 checked against the unconstrained fp32 oracle, and the gradients against the
 fp64 oracle whose LeakyReLU signs and pool argmaxes are the engine's own
-(tests/test_gpu_parity.engine_branch_masks, tests/_kink.forced_branches),
+(tests/_spff_checks.engine_branch_masks, tests/_kink.forced_branches),
 within 1e-3 relative L2 (GRAD_DEV below: where that fp64 backward is evaluated).
 
 The module's tests are the suite's longest; tests/conftest.py runs them last.
 """
 import json
 import os
-import socket
 
 import numpy as np
 import pytest
 import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
+
+from _golden import free_port
+from _spff_checks import engine_branch_masks, gather_masks, pack_masks, synth_core
+from _swin_checks import engine_act_masks
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -52,13 +55,7 @@ def _threads():
 
 
 def _spff_state(D, in_ch=5):
-    import innovative3D.models as M
-    from innovative3D.weightgen import synth_state
-    core = M.build_spct_energyfilm_fourier(num_classes=K13, base=32, in_channels=in_ch)
-    for b in core._blocks():
-        b.fgate._ensure_mask(D, "cpu")
-    st = synth_state([(k, tuple(v.shape)) for k, v in core.state_dict().items()], seed=0)
-    return core, st
+    return synth_core(K13, 32, in_ch, D, 0)
 
 
 def _oracle_cfg(in_ch=5):
@@ -109,7 +106,6 @@ def _oracle_grads(st, x, y, masks):
 
 
 def _engine_masks(core, xshape, st):
-    from test_gpu_parity import engine_branch_masks
     return engine_branch_masks(core, xshape, st, _oracle_cfg(xshape[1]))
 
 
@@ -117,7 +113,7 @@ def _mag_scales(st, g64s):
     """FourierGate mag_scale: d/d(mag) = sum_k mask_k dL/dM_k (M = mask * mag) is a sum
     over the rfft bins that can cancel almost completely (the fp32 oracle lands 1e-3
     from fp64 on it at 512^2); judge it against the sum of its absolute terms,
-    sum_k |mask_k dL/dmask_k| / |mag|, as tests/test_gpu_parity.py does."""
+    sum_k |mask_k dL/dmask_k| / |mag|, as tests/_spff_checks.grad_scales does."""
     out = {}
     for k in g64s:
         if k.endswith("fgate.mag_scale"):
@@ -193,7 +189,7 @@ def _compare(tag, lg, loss, grads, ref_logits, ref_loss, ref_grads, loss_rtol=1e
         rel32 = float((g32s[k].double().reshape(-1) - r).norm()) / nrm if g32s is not None else 0.0
         tol = max(1e-3, 4 * rel32)
         rows.append((rel, rel32, k, g[0].item(), r[0].item(), g[-1].item(), r[-1].item()))
-        if rel > tol:
+        if not rel <= tol:
             bad.append(f"{k}: rel L2 {rel:.2e} (fp32 oracle {rel32:.2e})")
     rows.sort(reverse=True)
     for rel, rel32, k, gh, rh, gt, rt in rows[:8]:
@@ -261,7 +257,6 @@ def test_config2_headline_matches_oracle(config2_oracle, config2_fp64, mth):
     st, x, y, ref_logits, ref_loss = config2_oracle
     lg64, am64, flips32, err32 = config2_fp64
     core, _ = _spff_state(128)
-    core.load_state_dict({k: torch.from_numpy(v) for k, v in st.items()})
     core = core.to(DEV)
     core.math = mth
     logits = core(x.to(DEV))
@@ -307,14 +302,6 @@ def test_config2_headline_matches_oracle(config2_oracle, config2_fp64, mth):
 SH_SHAPE = (1, 5, 16, 512, 512)
 
 
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
 def _sh_data():
     from innovative3D.synthetic import synthetic_batch
     return synthetic_batch(*SH_SHAPE, num_classes=K13, ignore_frac=0.01, seed=4)
@@ -332,7 +319,6 @@ def _sh_worker(rank, world, port, out):
     dist.init_process_group("gloo", rank=rank, world_size=world)
     torch.cuda.set_device(0)
     core, st = _spff_state(SH_SHAPE[2])
-    core.load_state_dict({k: torch.from_numpy(v) for k, v in st.items()})
     core = core.to(DEV)
     core.math = "f16x3"
     x, y = _sh_data()
@@ -343,12 +329,8 @@ def _sh_worker(rank, world, port, out):
     torch.cuda.synchronize()
     # this rank's LeakyReLU signs / pool argmaxes over its own depth slab
     masks = _engine_masks(core, (1, SH_SHAPE[1], d) + SH_SHAPE[3:], st)
-    mk = {}
-    for k, m in masks.items():
-        a = m.numpy()
-        mk["m_" + k] = np.packbits(a) if a.dtype == np.bool_ else a.astype(np.uint8)
-        mk["s_" + k] = np.array(a.shape)
-    np.savez(f"{out}.{rank}.npz", logits=step.last_logits.cpu().numpy(), loss=float(loss), **mk,
+    np.savez(f"{out}.{rank}.npz", logits=step.last_logits.cpu().numpy(), loss=float(loss),
+             **pack_masks(masks),
              **({"g_" + k: p.grad.cpu().numpy() for k, p in core.named_parameters(remove_duplicate=False)
                  if p.grad is not None and not k.endswith("._mask")} if rank == 0 else {}))
     del step, core
@@ -360,24 +342,14 @@ def _sh_worker(rank, world, port, out):
 def test_config4_sharded_512_matches_oracle(tmp_path):
     out = str(tmp_path / "sh")
     world = 2
-    mp.spawn(_sh_worker, args=(world, _free_port(), out), nprocs=world, join=True)
+    mp.spawn(_sh_worker, args=(world, free_port(), out), nprocs=world, join=True)
     parts = [np.load(f"{out}.{r}.npz") for r in range(world)]
     lg = torch.from_numpy(np.concatenate([p["logits"] for p in parts], axis=2))
     _core, st = _spff_state(SH_SHAPE[2])
     x, y = _sh_data()
     ref_logits, ref_loss = _oracle_forward(st, x, y)
     # branch decisions: the sharded engine's own, each rank's slab concatenated along D
-    masks = {}
-    for k in (f[2:] for f in parts[0].files if f.startswith("m_")):
-        segs = []
-        for p in parts:
-            shp = tuple(int(v) for v in p["s_" + k])
-            a = p["m_" + k]
-            a = np.unpackbits(a)[:int(np.prod(shp))].astype(bool) if k[:4] != "pool" else a
-            segs.append(a.reshape(shp))
-        cat = np.concatenate(segs, axis=2)
-        masks[k] = torch.from_numpy(cat) if cat.dtype == np.bool_ else torch.from_numpy(cat.astype(np.int64))
-    ref_grads = _oracle_grads(st, x, y, masks)
+    ref_grads = _oracle_grads(st, x, y, gather_masks(parts, 2))
     grads = {k: torch.from_numpy(parts[0]["g_" + k]) for k in ref_grads[0]}
     _compare("config4 path: 1x5x16x512^2 depth-sharded world 2 (f16x3)", lg,
              float(parts[0]["loss"]), grads, ref_logits, ref_loss, ref_grads,
@@ -405,7 +377,6 @@ def _hs_worker(rank, world, port, out):
     dist.init_process_group("gloo", rank=rank, world_size=world)
     torch.cuda.set_device(0)
     core, st = _spff_state(HS_SHAPE[2], in_ch=1)
-    core.load_state_dict({k: torch.from_numpy(v) for k, v in st.items()})
     core = core.to(DEV)
     core.math = "f16x3"
     x, y = _hs_data()
@@ -416,12 +387,8 @@ def _hs_worker(rank, world, port, out):
     torch.cuda.synchronize()
     # this rank's LeakyReLU signs (global IN affine) / pool argmaxes over its rows
     masks = _engine_masks(core, HS_SHAPE[:3] + (h, HS_SHAPE[4]), st)
-    mk = {}
-    for k, m in masks.items():
-        a = m.numpy()
-        mk["m_" + k] = np.packbits(a) if a.dtype == np.bool_ else a.astype(np.uint8)
-        mk["s_" + k] = np.array(a.shape)
-    np.savez(f"{out}.{rank}.npz", logits=step.last_logits.cpu().numpy(), loss=float(loss), **mk,
+    np.savez(f"{out}.{rank}.npz", logits=step.last_logits.cpu().numpy(), loss=float(loss),
+             **pack_masks(masks),
              **({"g_" + k: p.grad.cpu().numpy() for k, p in core.named_parameters(remove_duplicate=False)
                  if p.grad is not None and not k.endswith("._mask")} if rank == 0 else {}))
     del step, core
@@ -435,23 +402,13 @@ def test_registry_height_sharded_512_matches_oracle(tmp_path):
     256-row slabs (spff_cfg.shard_axis = SPFF_SHARD_HEIGHT) vs the UNSHARDED oracle."""
     out = str(tmp_path / "hs")
     world = 2
-    mp.spawn(_hs_worker, args=(world, _free_port(), out), nprocs=world, join=True)
+    mp.spawn(_hs_worker, args=(world, free_port(), out), nprocs=world, join=True)
     parts = [np.load(f"{out}.{r}.npz") for r in range(world)]
     lg = torch.from_numpy(np.concatenate([p["logits"] for p in parts], axis=3))
     _core, st = _spff_state(HS_SHAPE[2], in_ch=1)
     x, y = _hs_data()
     ref_logits, ref_loss = _oracle_forward(st, x, y)
-    masks = {}
-    for k in (f[2:] for f in parts[0].files if f.startswith("m_")):
-        segs = []
-        for p in parts:
-            shp = tuple(int(v) for v in p["s_" + k])
-            a = p["m_" + k]
-            a = np.unpackbits(a)[:int(np.prod(shp))].astype(bool) if k[:4] != "pool" else a
-            segs.append(a.reshape(shp))
-        cat = np.concatenate(segs, axis=3)   # [B, C, D, H, W]: the row slabs
-        masks[k] = torch.from_numpy(cat) if cat.dtype == np.bool_ else torch.from_numpy(cat.astype(np.int64))
-    ref_grads = _oracle_grads(st, x, y, masks)
+    ref_grads = _oracle_grads(st, x, y, gather_masks(parts, 3))  # [B, C, D, H, W]: the row slabs
     grads = {k: torch.from_numpy(parts[0]["g_" + k]) for k in ref_grads[0]}
     _compare("registry 1x1x5x512^2 height-sharded world 2 (f16x3)", lg,
              float(parts[0]["loss"]), grads, ref_logits, ref_loss, ref_grads,
@@ -465,7 +422,6 @@ def test_config5_swin_128_matches_oracle():
     import innovative3D.models as M
     from innovative3D.weightgen import synth_state
     from innovative3D.synthetic import synthetic_batch
-    from test_gpu_swin import engine_act_masks
     cfg = S.SwinCfg(num_classes=K13)
     st = synth_state(list(S.param_shapes(cfg).items()), seed=0)
     x, y = synthetic_batch(2, 1, 128, 128, 128, K13, ignore_frac=0.01, seed=0)

@@ -6,7 +6,6 @@ gradient float once.  The all-reduced gradients, the global loss and the global
 confusion must equal the single-process engine on the concatenated batch
 (SURVEY §8(e) DP row; helpers.py:782-803).  Marked gpu."""
 import os
-import socket
 
 import numpy as np
 import pytest
@@ -14,16 +13,10 @@ import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
+from _golden import free_port
+
 pytestmark = pytest.mark.gpu
 K, BASE, SHAPE = 7, 8, (2, 5, 8, 32, 32)
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
 
 
 def _model():
@@ -80,7 +73,7 @@ def test_dp_engine_matches_full_batch(tmp_path, bucket):
     loss.backward()
     grads = {k: p.grad.cpu().numpy() for k, p in lit.named_parameters() if p.grad is not None}
     out = str(tmp_path / "dp")
-    mp.spawn(_worker, args=(2, _free_port(), bucket, out), nprocs=2, join=True)
+    mp.spawn(_worker, args=(2, free_port(), bucket, out), nprocs=2, join=True)
     parts = [np.load(f"{out}.{r}.npz") for r in range(2)]
     spans = sorted(map(tuple, parts[0]["launched"]))
     print(f"bucket {bucket} B: {len(spans)} all-reduces, loss {float(parts[0]['loss']):.8f} vs "
@@ -124,7 +117,7 @@ def test_rccl_world1_bucketed_step(tmp_path):
     torch.cuda.synchronize()
     ref = {k: p.grad.clone() for k, p in lit.named_parameters() if p.grad is not None}
     nflat = sum(g.numel() for g in ref.values())
-    dist.init_process_group("nccl", init_method=f"tcp://127.0.0.1:{_free_port()}",
+    dist.init_process_group("nccl", init_method=f"tcp://127.0.0.1:{free_port()}",
                             rank=0, world_size=1, device_id=torch.device("cuda", 0))
     try:
         backend = dist.get_backend()

@@ -15,17 +15,11 @@ DEV = "cuda"
 
 @pytest.mark.parametrize("mth", ["f16x3", "f32"])
 def test_graph_replay_equals_eager(mth):
-    import innovative3D.models as M
+    from _spff_checks import synth_core
     from innovative3D.distributed import DataParallelSPFF
     from innovative3D.synthetic import synthetic_batch
-    from innovative3D.weightgen import synth_state
     K, D = 13, 16
-    core = M.build_spct_energyfilm_fourier(num_classes=K, base=16, in_channels=5)
-    for b in core._blocks():
-        b.fgate._ensure_mask(D, "cpu")
-    st = synth_state([(k, tuple(v.shape)) for k, v in core.state_dict().items()], seed=11)
-    core.load_state_dict({k: torch.from_numpy(v) for k, v in st.items()})
-    core = core.to(DEV)
+    core = synth_core(K, 16, 5, D, 11)[0].to(DEV)
     core.math = mth
     runner = DataParallelSPFF(core, K, 255)
     x1, y1 = synthetic_batch(2, 5, D, 32, 48, num_classes=K, ignore_frac=0.02, seed=1)

@@ -14,7 +14,7 @@ worst values are in profiles/head_fold/README.md).  The folded path is determini
 import pytest
 import torch
 
-import innovative3D.models as M
+from _spff_checks import synth_core
 import innovative3D.helpers as Hh
 
 pytestmark = pytest.mark.gpu
@@ -22,13 +22,7 @@ DEV = "cuda"
 
 
 def _core(K, base, D, mth, seed):
-    from innovative3D.weightgen import synth_state
-    core = M.build_spct_energyfilm_fourier(num_classes=K, base=base, in_channels=5)
-    for b in core._blocks():
-        b.fgate._ensure_mask(D, "cpu")
-    st = synth_state([(k, tuple(v.shape)) for k, v in core.state_dict().items()], seed=seed)
-    core.load_state_dict({k: torch.from_numpy(v) for k, v in st.items()})
-    core = core.to(DEV)
+    core = synth_core(K, base, 5, D, seed)[0].to(DEV)
     core.math = mth
     return core
 

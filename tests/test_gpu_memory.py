@@ -4,7 +4,6 @@ saves.  Same kernels, same operands -> the lean engine must be BITWISE equal
 to the full-save engine (logits, loss, every gradient), unsharded and
 depth-sharded (world 2 on one GPU, host-staged gloo).  Marked gpu."""
 import os
-import socket
 
 import numpy as np
 import pytest
@@ -12,20 +11,15 @@ import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
+from _golden import free_port
+
 pytestmark = pytest.mark.gpu
 K, BASE, SHAPE = 6, 8, (2, 5, 8, 32, 32)
 
 
 def _model(math_mode, memory, shape=SHAPE):
-    import innovative3D.models as M
-    from innovative3D.weightgen import synth_state
-    core = M.build_spct_energyfilm_fourier(num_classes=K, base=BASE, in_channels=shape[1])
-    for b in core._blocks():
-        b.fgate._ensure_mask(shape[2], "cpu")
-    st = synth_state([(k, tuple(v.shape)) for k, v in core.state_dict().items()], seed=13,
-                     mask_jitter=0.25)
-    core.load_state_dict({k: torch.from_numpy(v) for k, v in st.items()})
-    core = core.to("cuda")
+    from _spff_checks import synth_core
+    core = synth_core(K, BASE, shape[1], shape[2], 13, 0.25)[0].to("cuda")
     core.math, core.memory = math_mode, memory
     return core
 
@@ -79,14 +73,6 @@ def test_lean_equals_full_ragged_hw():
         assert torch.equal(g, rl[3][k]), k
 
 
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
 SH = (1, 5, 8, 32, 32)
 
 
@@ -123,7 +109,7 @@ def test_lean_sharded_matches_full_sharded(tmp_path):
     res = {}
     for mem in ("full", "lean"):
         out = str(tmp_path / mem)
-        mp.spawn(_worker, args=(2, _free_port(), out, mem), nprocs=2, join=True)
+        mp.spawn(_worker, args=(2, free_port(), out, mem), nprocs=2, join=True)
         res[mem] = [np.load(f"{out}.{r}.npz") for r in range(2)]
     assert all(int(p["lean"]) for p in res["lean"]) and all(int(p["full"]) for p in res["full"])
     for r in range(2):

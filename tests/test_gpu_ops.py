@@ -19,10 +19,6 @@ def _cl(t):  # [B,C,D,H,W] -> [B,D,H,W,C]
     return t.permute(0, 2, 3, 4, 1).contiguous()
 
 
-def _ncdhw(t):  # [B,D,H,W,C] -> [B,C,D,H,W]
-    return t.permute(0, 4, 1, 2, 3).contiguous()
-
-
 CONV_CASES = [
     # B, D, H, W, cin, cout, ksd
     (2, 5, 16, 32, 8, 32, 3),

@@ -5,7 +5,7 @@ localisation against the CPU oracle.  Marked gpu.
 Tolerances (north star, BASELINE.json): logits within 1e-3 of the reference
 PyTorch-CPU forward, identical argmax (voxels whose reference top-2 margin is
 below 2 x the observed max |dlogit| are reported as near-ties, not failures);
-gradients vs a kink-consistent fp64 oracle (engine_lrelu_masks) within
+gradients vs a kink-consistent fp64 oracle (_spff_checks.engine_branch_masks) within
 max(1e-3, 8 x the fp32 oracle's own error) of max|g| per tensor (some
 gate-parameter gradients are cancelling sums the fp32 reference itself only
 gets to ~5e-2; FourierGate mag_scale, whose gradient sum_k mask_k dL/dM_k cancels
@@ -19,35 +19,16 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from _compare import check_logits
 from _golden import cfg_of, fixture_names, load, state_of
-from _golden import build_core as _build_core
+from _spff_checks import (check_grads, engine_branch_masks, load_core, oracle_grads,
+                          oracle_grads_st, synth_core)
 from oracle import spff_oracle as O
 import innovative3D.models as M
 import innovative3D.helpers as Hh
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
-
-
-def build_core(meta):
-    return _build_core(meta)
-
-
-def load_core(d):
-    meta = d["meta"]
-    core = build_core(meta)
-    D = d["x"].shape[2]
-    for b in core._blocks():
-        if isinstance(getattr(b, "fgate", None), M.FourierGate3D):
-            b.fgate._ensure_mask(D, "cpu")
-    st = state_of(d)
-    core.load_state_dict({k: torch.from_numpy(v) for k, v in st.items()}, strict=True)
-    return core.to(DEV)
-
-
-def near_tie_mask(ref_logits, tol):
-    top2 = np.sort(ref_logits, axis=1)[:, -2:]
-    return (top2[:, 1] - top2[:, 0]) < tol
 
 
 @pytest.mark.parametrize("mth", ["f32", "bf16x6", "bf16x3", "f16x3"])
@@ -70,14 +51,8 @@ def test_network_matches_reference(name, mth):
     torch.cuda.synchronize()
     lg = logits.detach().cpu().numpy()
     ref = d["logits"]
-    err = float(np.abs(lg - ref).max())
-    print(f"{name}/{mth}: max|dlogit| = {err:.3e}  loss {float(loss):.7f} vs {float(d['loss']):.7f}")
-    assert err <= 1e-3
-    am, am_ref = lg.argmax(1), ref.argmax(1)
-    flips = am != am_ref
-    if flips.any():
-        ties = near_tie_mask(ref, 2 * err)
-        assert not (flips & ~ties).any(), f"{int(flips.sum())} argmax flips outside near-ties"
+    _err, _nf, flips = check_logits(f"{name}/{mth}", lg, ref)
+    print(f"  loss {float(loss):.7f} vs {float(d['loss']):.7f}")
     assert math.isclose(float(loss), float(d["loss"]), rel_tol=1e-4 if mth == "bf16x3" else 1e-5)
     met = M.metrics_from_confusion(conf.cpu().numpy(), K, int(y.numel()))
     if not flips.any():
@@ -86,176 +61,10 @@ def test_network_matches_reference(name, mth):
     # gradients: vs a kink-consistent fp64 oracle (see oracle_grads), tolerance =
     # max(1e-3, 8 x the fp32 oracle's own error) of max|g| per tensor
     named = dict(core.named_parameters(remove_duplicate=False))
-    masks = engine_lrelu_masks(core, d)
+    masks = engine_branch_masks(core, d["x"].shape, state_of(d), cfg_of(d["meta"]))
     ref64, ref32, nflip, absb = oracle_grads(d, masks)
     print(f"  LeakyReLU kink flips (engine vs fp64 sign): {nflip}")
     check_grads({k: named[k].grad for k in ref64}, ref64, ref32, absb, state_of(d), mth)
-
-
-def check_grads(grads, ref64, ref32, absb, st, mth):
-    """Every engine gradient vs the kink-consistent fp64 oracle: max|g - g64| / scale
-    within max(1e-3, 8 x the fp32 oracle's own error) (bf16x3: max(5e-3, 64 x); the
-    floor alone when ``ref32`` is None); scale
-    = max over the tensor of sum_b |per-sample g_b| (absb); FourierGate mag_scale is
-    judged against the sum of its absolute terms."""
-    rows, bad = [], []
-    for kk, g64 in ref64.items():
-        g = grads[kk]
-        assert g is not None, kk
-        g = np.asarray(g.detach().double().cpu().numpy() if torch.is_tensor(g) else g, np.float64)
-        # scale: sum over samples of |per-sample gradient| (= max|g| for B=1); the batch
-        # gradient is a sum of per-sample terms that can cancel (e.g. SE biases)
-        scale = max(float(absb[kk].max()), 1e-12)
-        if kk.endswith("fgate.mag_scale"):
-            # d/d(mag) = sum_k mask_k dL/dM_k (M = mask * mag): a sum over the rfft
-            # bins that can cancel almost completely; judge it against the sum of
-            # its absolute terms, sum_k |mask_k dL/dM_k| = sum_k |mask_k g_mask_k| / |mag|
-            pre = kk[: -len("mag_scale")]
-            mk = pre + ("freq_mask" if pre + "freq_mask" in ref64 else "_mask")
-            mag = abs(float(np.asarray(st[kk]).reshape(-1)[0]))
-            terms = np.abs(np.asarray(st[pre + "freq_mask"]).reshape(-1) *
-                           absb[mk].reshape(-1)).sum()
-            scale = max(scale, float(terms) / max(mag, 1e-12))
-        e_gpu = float(np.abs(g - g64).max()) / scale
-        e_32 = float(np.abs(ref32[kk] - g64).max()) / scale if ref32 is not None else 0.0
-        tol = max(5e-3, 64 * e_32) if mth == "bf16x3" else max(1e-3, 8 * e_32)
-        rows.append((e_gpu, e_32, kk))
-        if e_gpu > tol:
-            bad.append(f"{kk}: gpu {e_gpu:.2e} vs fp32-oracle {e_32:.2e}")
-    rows.sort(reverse=True)
-    print("\n".join(f"  {k:32s} gpu {a:.2e}  fp32-oracle {b:.2e}" for a, b, k in rows[:6]))
-    assert not bad, "; ".join(bad)
-
-
-def _block_names(cfg):
-    a, b = ("pre", "body") if cfg.novel else ("b1", "b2")
-    return [(blk, a, b) for blk in ("enc1", "enc2", "enc3", "bott", "dec3", "dec2", "dec1")]
-
-
-def engine_lrelu_masks(core, d):
-    return engine_branch_masks(core, d["x"].shape, state_of(d), cfg_of(d["meta"]))
-
-
-def engine_branch_masks(core, xshape, st, cfg):
-    """Sign pattern of every LeakyReLU input, and the argmax of every max-pool
-    window, as the ENGINE saw them (the pools: from its saved pool inputs; ties
-    resolved first-max like the engine and torch).  The LeakyReLUs: the engine's
-    saved conv outputs y1/y2 under its own per-(b,c) affine (al, de).  A fp32 conv differs from the
-    reference's by ~1e-6 relative, so an input sitting within that of the kink
-    (|r| ~ 0) can take the other slope (1 vs 0.01) -- a legitimate fp32 outcome
-    the reference could equally produce.  Feeding the engine's pattern to the
-    oracle removes these knife-edge flips from the gradient comparison."""
-    B = xshape[0]
-    plan = core._plan
-    masks = {}
-    for blk, a, b in _block_names(cfg):
-        for tag, key in ((a, "y1"), (b, "y2")):
-            y = plan.saved(f"{blk}.{key}").double().cpu()
-            C = y.shape[1]
-            Dd = xshape[2]
-            lvl = {"enc1": 0, "dec1": 0, "enc2": 1, "dec2": 1, "enc3": 2, "dec3": 2, "bott": 3}[blk]
-            Hh_, Ww = xshape[3] >> lvl, xshape[4] >> lvl
-            y = y.view(B, Dd, Hh_, Ww, C).permute(0, 4, 1, 2, 3)
-            g = torch.from_numpy(st[f"{blk}.{tag}.1.weight"]).double()
-            bb = torch.from_numpy(st[f"{blk}.{tag}.1.bias"]).double()
-            m64 = F.instance_norm(y, weight=g, bias=bb, eps=1e-5) > 0
-            # the engine's own fp32 normalisation r = fma(y, al, de): its sign is the
-            # sign of the exact y*al + de, which fp64 reproduces
-            j = "1" if key == "y1" else "2"
-            al = plan.saved(f"{blk}.al{j}").double().cpu().reshape(B, C, 1, 1, 1)
-            de = plan.saved(f"{blk}.de{j}").double().cpu().reshape(B, C, 1, 1, 1)
-            # contiguous: this torch build's CPU instance_norm backward is wrong for a
-            # channels-last-strided grad_output, which torch.where would propagate
-            m = ((y * al + de) > 0).contiguous()
-            nd = int((m != m64).sum())
-            if nd:
-                print(f"  {blk}.{tag}: {nd} knife-edge signs (engine affine vs fp64 IN)")
-            masks[f"{blk}.{tag}"] = m
-    # max-pool windows: the engine's own argmax bytes (k = 2 dh + dw, first max in scan
-    # order), as its backward routed them -- also valid for lean plans, whose block
-    # outputs live in backward scratch
-    Dd = xshape[2]
-    for k in range(3):
-        Hh_, Ww = xshape[3] >> (k + 1), xshape[4] >> (k + 1)
-        idx = plan.saved(f"pool{k + 1}.idx").to(torch.int64).cpu()
-        C = idx.shape[1]
-        masks[f"pool{k + 1}"] = idx.view(B, Dd, Hh_, Ww, C).permute(0, 4, 1, 2, 3).contiguous()
-    return masks
-
-
-def oracle_grads(d, masks):
-    return oracle_grads_st(cfg_of(d["meta"]), state_of(d), d["x"], d["labels"], masks)
-
-
-def oracle_grads_st(cfg, st, x, labels, masks, device="cpu", fp32=True):
-    """fp64 and fp32 oracle parameter gradients (CPU; ``device`` evaluates the same
-    restatement through PyTorch's fp64 device kernels, ``fp32=False`` skips the fp32
-    run and returns None for it) whose LeakyReLUs take the
-    given sign patterns; also returns how many entries differ from the fp64
-    oracle's own pattern (knife-edge flips) and sum_b |g_b| (fp64 per-sample
-    gradients with the global CE normalisation; sum_b g_b = g exactly since
-    IN / SE / gates are per sample and the Dice term carries no gradient).
-    ``x``, ``labels``: numpy arrays; ``st``: the state dict (numpy)."""
-    st = {k: v for k, v in st.items() if not k.endswith("._mask")}
-    d = {"x": np.ascontiguousarray(x), "labels": np.ascontiguousarray(labels)}
-    out = []
-    nflip = [0]
-    orig, orig_pool = O.conv_in_lrelu, O.maxpool
-    npool = [0]
-    masks = {k: v.to(device) for k, v in masks.items()}
-
-    def pool_hooked(t):
-        k = npool[0] % 3
-        npool[0] += 1
-        idx = masks[f"pool{k + 1}"]
-        B_, C_, D_, H_, W_ = t.shape
-        v = t[..., :H_ // 2 * 2, :W_ // 2 * 2].reshape(B_, C_, D_, H_ // 2, 2, W_ // 2, 2)
-        v = v.permute(0, 1, 2, 3, 5, 4, 6)
-        v = v.reshape(B_, C_, D_, H_ // 2, W_ // 2, 4)
-        if t.dtype == torch.float64:
-            nflip[0] += int((v.detach().argmax(-1) != idx).sum())
-        return v.gather(-1, idx.unsqueeze(-1)).squeeze(-1)
-
-    def hooked(P_, pre, inp, ksd):
-        y = F.conv3d(inp, P_[pre + ".0.weight"], None, padding=(ksd // 2, 1, 1))
-        r = F.instance_norm(y, weight=P_[pre + ".1.weight"], bias=P_[pre + ".1.bias"], eps=1e-5)
-        m = masks[pre]
-        if r.dtype == torch.float64:
-            nflip[0] += int((m != (r.detach() > 0)).sum())
-        return torch.where(m, r, 0.01 * r)
-
-    O.conv_in_lrelu = hooked
-    O.maxpool = pool_hooked
-    try:
-        for dt in ((torch.float64, torch.float32) if fp32 else (torch.float64,)):
-            P = O.params_from_state(st, dtype=dt, device=device)
-            O.fwd_bwd(P, torch.from_numpy(d["x"]).to(device, dt),
-                      torch.from_numpy(d["labels"]).to(device), cfg)
-            out.append({k: v.grad.double().cpu().numpy() for k, v in P.items()})
-            del P
-        if not fp32:
-            out.append(None)
-        B = d["x"].shape[0]
-        absb = {k: np.abs(v) for k, v in out[0].items()}
-        if B > 1:
-            yall = torch.from_numpy(d["labels"]).to(device)
-            N = int((yall != 255).sum())
-            full = dict(masks)
-            absb = None
-            for b in range(B):
-                for k in full:
-                    masks[k] = full[k][b:b + 1]
-                P = O.params_from_state(st, dtype=torch.float64, device=device)
-                lg = O.forward(P, torch.from_numpy(d["x"][b:b + 1]).to(device, torch.float64), cfg)
-                (F.cross_entropy(lg, yall[b:b + 1], ignore_index=255, reduction="sum") / N).backward()
-                gb = {k: np.abs(v.grad.cpu().numpy()) for k, v in P.items()}
-                absb = gb if absb is None else {k: absb[k] + gb[k] for k in absb}
-            for k in full:
-                masks[k] = full[k]
-            masks.update(full)
-    finally:
-        O.conv_in_lrelu, O.maxpool = orig, orig_pool
-    return out[0], out[1], nflip[0], absb
 
 
 def _oracle_stages(P, x, cfg):
@@ -316,7 +125,7 @@ def test_stagewise_forward(name):
         e = float(np.abs(mine - rr).max()) / max(1e-6, float(np.abs(rr).max()))
         report.append((k, e))
     print("\n".join(f"  {k:10s} rel {e:.2e}" for k, e in report))
-    bad = [(k, e) for k, e in report if e > 1e-4]
+    bad = [(k, e) for k, e in report if not e <= 1e-4]
     assert not bad, f"first diverging stage: {bad[0]}"
 
 
@@ -354,15 +163,8 @@ def test_gate_channel_split_path(D, se, specse, mth):
 
 def _engine_vs_oracle(in_ch, K, base, mth, shape=(1, 4, 16, 16), se=True, specse=True):
     from innovative3D.synthetic import synthetic_batch
-    from innovative3D.weightgen import synth_state
     B, D, H, W = shape
-    core = M.build_spct_energyfilm_fourier(num_classes=K, base=base, in_channels=in_ch,
-                                           use_se=se, use_specse=specse)
-    for b in core._blocks():
-        b.fgate._ensure_mask(D, "cpu")
-    st = synth_state([(k, tuple(v.shape)) for k, v in core.state_dict().items()], seed=31,
-                     mask_jitter=0.25)
-    core.load_state_dict({k: torch.from_numpy(v) for k, v in st.items()})
+    core, st = synth_core(K, base, in_ch, D, 31, 0.25, use_se=se, use_specse=specse)
     core = core.to(DEV)
     core.math = mth
     x, y = synthetic_batch(B, in_ch, D, H, W, num_classes=K, ignore_frac=0.03, seed=32)
@@ -376,13 +178,8 @@ def _engine_vs_oracle(in_ch, K, base, mth, shape=(1, 4, 16, 16), se=True, specse
     with torch.no_grad():
         ref = O.forward(P, x, cfg)
         ref_loss = float(O.ce_plus_macro_dice(ref, y, K)[0])
-    lg = logits.detach().cpu().numpy()
-    err = float(np.abs(lg - ref.numpy()).max())
-    flips = lg.argmax(1) != ref.numpy().argmax(1)
-    print(f"in_ch {in_ch} K {K} base {base} {mth}: max|dlogit| {err:.2e}, flips {int(flips.sum())}, "
-          f"loss {float(loss):.7f} vs {ref_loss:.7f}")
-    assert err <= 1e-3
-    assert not (flips & ~near_tie_mask(ref.numpy(), 2 * err)).any()
+    check_logits(f"in_ch {in_ch} K {K} base {base} {mth}", logits, ref)
+    print(f"  loss {float(loss):.7f} vs {ref_loss:.7f}")
     assert math.isclose(float(loss), ref_loss, rel_tol=1e-5)
     assert int(conf[:, K].sum()) == 0
     masks = engine_branch_masks(core, tuple(x.shape), st, cfg)
@@ -407,14 +204,9 @@ def test_oracle_device_evaluation_matches_cpu(case):
         masks = None
     else:
         from innovative3D.synthetic import synthetic_batch
-        from innovative3D.weightgen import synth_state
-        core = M.build_spct_energyfilm_fourier(num_classes=13, base=32, in_channels=5)
-        for b in core._blocks():
-            b.fgate._ensure_mask(8, "cpu")
-        st = synth_state([(k, tuple(v.shape)) for k, v in core.state_dict().items()], seed=3)
+        core, st = synth_core(13, 32, 5, 8, 3)
         cfg = O.SpffCfg(in_ch=5, num_classes=13, base=32)
         x, y = synthetic_batch(2, 5, 8, 64, 64, 13, ignore_frac=0.01, seed=3)
-        core.load_state_dict({k: torch.from_numpy(v) for k, v in st.items()})
         core = core.to(DEV)
         lg = core(x.to(DEV))
         Hh.ce_dice_with_confusion(lg, y.to(DEV), 13, 255)[0].backward()
@@ -450,14 +242,8 @@ def test_pool_fold_bitwise(mth):
     and the IN-backward apply) against the k_maxpool_bwd_add pass it replaced (debug key 2
     = 0).  Same sum in the same order: every parameter gradient bitwise equal."""
     from innovative3D.synthetic import synthetic_batch
-    from innovative3D.weightgen import synth_state
     K = 13
-    core = M.build_spct_energyfilm_fourier(num_classes=K, base=16, in_channels=5)
-    for b in core._blocks():
-        b.fgate._ensure_mask(8, "cpu")
-    st = synth_state([(k, tuple(v.shape)) for k, v in core.state_dict().items()], seed=5)
-    core.load_state_dict({k: torch.from_numpy(v) for k, v in st.items()})
-    core = core.to(DEV)
+    core = synth_core(K, 16, 5, 8, 5)[0].to(DEV)
     core.math = mth
     x, y = synthetic_batch(2, 5, 8, 32, 48, num_classes=K, ignore_frac=0.02, seed=6)
     x, y = x.to(DEV), y.to(DEV)
@@ -489,15 +275,9 @@ def test_fused_in_backward_sums(mth, shape):
     case); the forward is untouched (logits bitwise).
     The ragged case (D = 5, H = 24: partial tiles) checks the epilogue's row masking."""
     from innovative3D.synthetic import synthetic_batch
-    from innovative3D.weightgen import synth_state
     K = 13
     B, D, H, W = shape
-    core = M.build_spct_energyfilm_fourier(num_classes=K, base=16, in_channels=5)
-    for b in core._blocks():
-        b.fgate._ensure_mask(D, "cpu")
-    st = synth_state([(k, tuple(v.shape)) for k, v in core.state_dict().items()], seed=9)
-    core.load_state_dict({k: torch.from_numpy(v) for k, v in st.items()})
-    core = core.to(DEV)
+    core = synth_core(K, 16, 5, D, 9)[0].to(DEV)
     core.math = mth
     x, y = synthetic_batch(B, 5, D, H, W, num_classes=K, ignore_frac=0.02, seed=10)
     x, y = x.to(DEV), y.to(DEV)

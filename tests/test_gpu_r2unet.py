@@ -9,7 +9,6 @@ argmaxes the engine saw: an activation within fp32 rounding of 0 may take either
 within max(1e-3, 8 x the fp32 oracle's own error) of max|g|.  The loss kernel alone
 against the fp64 loss and dlogits of four small cases; determinism; the no-grad forward;
 the H / W padding and crop."""
-import hashlib
 import math
 
 import numpy as np
@@ -18,7 +17,9 @@ import torch
 import torch.nn.functional as F
 
 import _r2u_oracle as R
-from _golden import GOLDEN, load
+from _compare import (assert_no_grad_forward_equals_train, assert_steps_bitwise, cached_oracle,
+                      check_grads_rows, check_logits, grad_errors, kink_hooks, ncdhw, track_plan)
+from _golden import GOLDEN, load, synth_state_of
 import innovative3D.models as M
 
 pytestmark = pytest.mark.gpu
@@ -31,42 +32,17 @@ def cfg_of(meta):
                     pad_multiple=meta["pad_multiple"])
 
 
-def state_of(d):
-    from innovative3D.weightgen import synth_state
-    return synth_state([(k, tuple(v)) for k, v in d["state_shapes"].items()], d["meta"]["seed"])
-
-
 def build(d, mth=None):
     meta = d["meta"]
     m = M.LitR2UNet3D_Published(num_classes=meta["K"], in_channels=meta["in_ch"],
                                 base_features=meta["base"], t=meta["t"],
                                 pad_multiple=meta["pad_multiple"],
                                 ignore_index=meta["ignore_index"])
-    m.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in state_of(d).items()},
+    m.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in synth_state_of(d).items()},
                       strict=True)
     if mth is not None:
         m.math = mth
     return m.to(DEV)
-
-
-def track_plan(m):
-    """remember the plan the module used (its saved tensors feed the kink-consistent oracle)"""
-    orig = m._plan
-
-    def _plan(x, _o=orig):
-        p = _o(x)
-        m._last_plan = p
-        return p
-    m._plan = _plan
-
-
-def near_tie_mask(ref_logits, tol):
-    top2 = np.sort(ref_logits, axis=1)[:, -2:]
-    return (top2[:, 1] - top2[:, 0]) < tol
-
-
-def _ncdhw(t_cl, B, D, H, W):
-    return t_cl.view(B, D, H, W, -1).permute(0, 4, 1, 2, 3)
 
 
 def engine_hooks(m, t):
@@ -79,53 +55,25 @@ def engine_hooks(m, t):
         l = LEVEL[n]
         dims = (c.batch, c.depth >> l, c.height >> l, c.width >> l)
         for s in [f"ru{k}" for k in range(1, t + 1)] + ["out"]:
-            a = _ncdhw(plan.saved(f"{n}.{s}").cpu(), *dims)
+            a = ncdhw(plan.saved(f"{n}.{s}").cpu(), *dims)
             masks[f"{n}.{s}"] = a > 0
         if n in ("e1", "e2", "e3", "e4"):
-            e = _ncdhw(plan.saved(f"{n}.out").cpu(), *dims)
+            e = ncdhw(plan.saved(f"{n}.out").cpu(), *dims)
             pidx[f"pool{l + 1}"] = F.max_pool3d(e, 2, return_indices=True)[1]
-    h = hashlib.sha256()
-    for k in sorted(masks):
-        h.update(np.packbits(masks[k].numpy()).tobytes())
-    for k in sorted(pidx):
-        h.update(pidx[k].numpy().tobytes())
-
-    def relu(name, r):
-        return r * masks[name].to(r.dtype)
-
-    def pool(name, v):
-        idx = pidx[name]
-        return v.flatten(2).gather(2, idx.flatten(2)).view(idx.shape)
-    return {"relu": relu, "pool": pool}, h.hexdigest()
-
-
-_ORACLE = {}  # (fixture, branch digest) -> (g64, g32): one oracle run per distinct branch set
+    return kink_hooks(masks, pidx)
 
 
 def oracle_grads(name, d, hooks, digest):
-    key = (name, digest)
-    if key not in _ORACLE:
+    """(g64, g32): one oracle run per fixture and distinct branch set"""
+    def run():
         out = []
         for dtype in (torch.float64, torch.float32):
-            P = R.params_from_state(state_of(d), dtype=dtype)
+            P = R.params_from_state(synth_state_of(d), dtype=dtype)
             R.fwd_bwd(P, torch.from_numpy(d["x"]).to(dtype), torch.from_numpy(d["labels"]),
                       cfg_of(d["meta"]), d["meta"]["ignore_index"], hooks)
             out.append({k: v.grad.detach().double().numpy() for k, v in P.items()})
-        _ORACLE[key] = tuple(out)
-    return _ORACLE[key]
-
-
-def check_logits(tag, lg, ref):
-    err = float(np.abs(lg - ref).max())
-    flips = lg.argmax(1) != ref.argmax(1)
-    nf = int(flips.sum())
-    print(f"{tag}: max|dlogit| = {err:.3e}  argmax flips = {nf} of {flips.size}")
-    assert err <= 1e-3
-    assert nf <= 8
-    if nf:
-        ties = near_tie_mask(ref, 2 * err)
-        assert not (flips & ~ties).any(), f"{nf} argmax flips outside near-ties"
-    return err, nf
+        return tuple(out)
+    return cached_oracle((name, digest), run)
 
 
 @pytest.mark.parametrize("mth", ["f32", "bf16x6", "f16x3"])
@@ -144,7 +92,7 @@ def test_r2unet_matches_reference(name, mth):
     torch.cuda.synchronize()
     lg = logits.detach().cpu().numpy()
     ref = d["logits"]
-    err, nf = check_logits(f"{name}/{mth}", lg, ref)
+    err, nf, _flips = check_logits(f"{name}/{mth}", lg, ref, max_flips=8)
     loss = loss.detach()
     print(f"  loss {float(loss):.7f} vs {float(d['loss']):.7f}  dice {float(dice):.7f} vs "
           f"{float(d['dice']):.7f}")
@@ -154,18 +102,7 @@ def test_r2unet_matches_reference(name, mth):
     hooks, digest = engine_hooks(m, meta["t"])
     g64, g32 = oracle_grads(name, d, hooks, digest)
     named = dict(m.named_parameters())
-    rows, bad = [], []
-    for k, r64 in g64.items():
-        g = named[k].grad.detach().double().cpu().numpy()
-        scale = max(float(np.abs(r64).max()), 1e-12)
-        e_gpu = float(np.abs(g - r64).max()) / scale
-        e_32 = float(np.abs(g32[k] - r64).max()) / scale
-        rows.append((e_gpu, e_32, k))
-        if e_gpu > max(1e-3, 8 * e_32):
-            bad.append(f"{k}: gpu {e_gpu:.2e} vs fp32-oracle {e_32:.2e}")
-    rows.sort(reverse=True)
-    print("\n".join(f"  {k:32s} gpu {a:.2e}  fp32-oracle {b:.2e}" for a, b, k in rows[:5]))
-    assert not bad, "; ".join(bad)
+    check_grads_rows(grad_errors({k: named[k].grad for k in g64}, g64, g32))
     if name != "r2u_registry_k13":
         return
     # train.py's path: apply_unified_loss() rebinds the steps to CE + 0.5 hard Dice.  Against
@@ -243,11 +180,7 @@ def test_r2unet_step_is_deterministic():
     m = build(d)
     x = torch.from_numpy(d["x"]).to(DEV)
     y = torch.from_numpy(d["labels"]).to(DEV)
-    l1, g1 = _step(m, x, y, 255)
-    l2, g2 = _step(m, x, y, 255)
-    assert torch.equal(l1, l2)
-    for k in g1:
-        assert torch.equal(g1[k], g2[k]), k
+    assert_steps_bitwise(lambda: _step(m, x, y, 255))
 
 
 def test_r2unet_no_grad_forward_equals_train_forward():
@@ -255,12 +188,7 @@ def test_r2unet_no_grad_forward_equals_train_forward():
     m = build(d)
     x = torch.from_numpy(d["x"]).to(DEV)
     m.train()
-    a = m(x).detach().clone()
-    m.eval()
-    with torch.no_grad():
-        b = m(x)
-    torch.cuda.synchronize()
-    assert torch.equal(a, b)
+    assert_no_grad_forward_equals_train(m, x, eval_mode=True)
 
 
 def test_r2unet_pad_crop():
@@ -273,6 +201,6 @@ def test_r2unet_pad_crop():
         loss, dice = m._dice_only_loss_with_logits(logits, y, ignore_index=255)
     torch.cuda.synchronize()
     assert tuple(logits.shape) == d["logits"].shape == (1, 13, 5, 24, 40)
-    check_logits("r2u_pad_hw", logits.cpu().numpy(), d["logits"])
+    check_logits("r2u_pad_hw", logits, d["logits"], max_flips=8)
     assert math.isclose(float(loss), float(d["loss"]), rel_tol=1e-5)
     assert math.isclose(float(dice), float(d["dice"]), rel_tol=1e-5)

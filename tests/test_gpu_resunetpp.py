@@ -9,7 +9,6 @@ argmaxes the engine saw: an activation within fp32 rounding of 0 may take either
 within max(1e-3, 8 x the fp32 oracle's own error) of max|g|.  The dilated conv alone through
 the op-level ABI against an fp64 conv; the loss kernels alone against the fp64 loss and
 dlogits of five small cases; determinism; the no-grad forward; the H / W padding and crop."""
-import hashlib
 import math
 
 import numpy as np
@@ -18,7 +17,9 @@ import torch
 import torch.nn.functional as F
 
 import _rupp_oracle as R
-from _golden import GOLDEN, load
+from _compare import (assert_no_grad_forward_equals_train, assert_steps_bitwise, cached_oracle,
+                      check_grads_rows, check_logits, grad_errors, kink_hooks, ncdhw, track_plan)
+from _golden import GOLDEN, load, synth_state_of
 import innovative3D.models as M
 from innovative3D import _engine as E
 
@@ -32,41 +33,16 @@ def cfg_of(meta):
                      pad_multiple=meta["pad_multiple"])
 
 
-def state_of(d):
-    from innovative3D.weightgen import synth_state
-    return synth_state([(k, tuple(v)) for k, v in d["state_shapes"].items()], d["meta"]["seed"])
-
-
 def build(d, mth=None):
     meta = d["meta"]
     m = M.LitResUNetPP3D_Published(num_classes=meta["K"], in_channels=meta["in_ch"],
                                    base_features=meta["base"], pad_multiple=meta["pad_multiple"],
                                    ignore_index=meta["ignore_index"])
-    m.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in state_of(d).items()},
+    m.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in synth_state_of(d).items()},
                       strict=True)
     if mth is not None:
         m.math = mth
     return m.to(DEV)
-
-
-def track_plan(m):
-    """remember the plan the module used (its saved tensors feed the kink-consistent oracle)"""
-    orig = m._plan
-
-    def _plan(x, _o=orig):
-        p = _o(x)
-        m._last_plan = p
-        return p
-    m._plan = _plan
-
-
-def near_tie_mask(ref_logits, tol):
-    top2 = np.sort(ref_logits, axis=1)[:, -2:]
-    return (top2[:, 1] - top2[:, 0]) < tol
-
-
-def _ncdhw(t_cl, B, D, H, W):
-    return t_cl.view(B, D, H, W, -1).permute(0, 4, 1, 2, 3)
 
 
 def engine_hooks(m):
@@ -79,56 +55,28 @@ def engine_hooks(m):
         return (c.batch, c.depth >> l, c.height >> l, c.width >> l)
     for n in R.UNITS:
         for s in ("a1", "out"):
-            masks[f"{n}.{s}"] = _ncdhw(plan.saved(f"{n}.{s}").cpu(), *dims(R.LEVEL[n])) > 0
+            masks[f"{n}.{s}"] = ncdhw(plan.saved(f"{n}.{s}").cpu(), *dims(R.LEVEL[n])) > 0
         if n in ("e1", "e2", "e3", "e4"):
-            e = _ncdhw(plan.saved(f"{n}.out").cpu(), *dims(R.LEVEL[n]))
+            e = ncdhw(plan.saved(f"{n}.out").cpu(), *dims(R.LEVEL[n]))
             pidx[f"pool{R.LEVEL[n] + 1}"] = F.max_pool3d(e, 2, return_indices=True)[1]
-    masks["b_aspp.out"] = _ncdhw(plan.saved("b_aspp.out").cpu(), *dims(4)) > 0
+    masks["b_aspp.out"] = ncdhw(plan.saved("b_aspp.out").cpu(), *dims(4)) > 0
     for n, l in AGS.items():
-        masks[f"{n}.att"] = _ncdhw(plan.saved(f"{n}.att").cpu(), *dims(l)) > 0
-    h = hashlib.sha256()
-    for k in sorted(masks):
-        h.update(np.packbits(masks[k].numpy()).tobytes())
-    for k in sorted(pidx):
-        h.update(pidx[k].numpy().tobytes())
-
-    def relu(name, r):
-        return r * masks[name].to(r.dtype)
-
-    def pool(name, v):
-        idx = pidx[name]
-        return v.flatten(2).gather(2, idx.flatten(2)).view(idx.shape)
-    return {"relu": relu, "pool": pool}, h.hexdigest()
-
-
-_ORACLE = {}  # (fixture, branch digest) -> (g64, g32): one oracle run per distinct branch set
+        masks[f"{n}.att"] = ncdhw(plan.saved(f"{n}.att").cpu(), *dims(l)) > 0
+    return kink_hooks(masks, pidx)
 
 
 def oracle_grads(name, d, hooks, digest):
-    key = (name, digest)
-    if key not in _ORACLE:
+    """(g64, g32): one oracle run per fixture and distinct branch set"""
+    def run():
         out = []
         torch.set_num_threads(8)
         for dtype in (torch.float64, torch.float32):
-            P = R.params_from_state(state_of(d), dtype=dtype)
+            P = R.params_from_state(synth_state_of(d), dtype=dtype)
             R.fwd_bwd(P, torch.from_numpy(d["x"]).to(dtype), torch.from_numpy(d["labels"]),
                       cfg_of(d["meta"]), d["meta"]["ignore_index"], hooks)
             out.append({k: v.grad.detach().double().numpy() for k, v in P.items()})
-        _ORACLE[key] = tuple(out)
-    return _ORACLE[key]
-
-
-def check_logits(tag, lg, ref):
-    err = float(np.abs(lg - ref).max())
-    flips = lg.argmax(1) != ref.argmax(1)
-    nf = int(flips.sum())
-    print(f"{tag}: max|dlogit| = {err:.3e}  argmax flips = {nf} of {flips.size}")
-    assert err <= 1e-3
-    assert nf <= 8
-    if nf:
-        ties = near_tie_mask(ref, 2 * err)
-        assert not (flips & ~ties).any(), f"{nf} argmax flips outside near-ties"
-    return err, nf
+        return tuple(out)
+    return cached_oracle((name, digest), run)
 
 
 @pytest.mark.parametrize("mth", ["f32", "bf16x6", "f16x3"])
@@ -146,7 +94,7 @@ def test_resunetpp_matches_reference(name, mth):
     torch.cuda.synchronize()
     loss = loss.detach()
     lg = logits.detach().cpu().numpy()
-    check_logits(f"{name}/{mth}", lg, d["logits"])
+    check_logits(f"{name}/{mth}", lg, d["logits"], max_flips=8)
     print(f"  loss {float(loss):.7f} vs {float(d['loss']):.7f}  dice {float(dice):.7f} vs "
           f"{float(d['dice']):.7f}  ce {float(ce):.7f} vs {float(d['ce']):.7f}")
     assert math.isclose(float(loss), float(d["loss"]), rel_tol=1e-5)
@@ -157,18 +105,7 @@ def test_resunetpp_matches_reference(name, mth):
     g64, g32 = oracle_grads(name, d, hooks, digest)
     named = dict(m.named_parameters())
     assert set(named) == set(g64)
-    rows, bad = [], []
-    for k, r64 in g64.items():
-        g = named[k].grad.detach().double().cpu().numpy()
-        scale = max(float(np.abs(r64).max()), 1e-12)
-        e_gpu = float(np.abs(g - r64).max()) / scale
-        e_32 = float(np.abs(g32[k] - r64).max()) / scale
-        rows.append((e_gpu, e_32, k))
-        if not e_gpu <= max(1e-3, 8 * e_32):
-            bad.append(f"{k}: gpu {e_gpu:.2e} vs fp32-oracle {e_32:.2e}")
-    rows.sort(reverse=True)
-    print("\n".join(f"  {k:40s} gpu {a:.2e}  fp32-oracle {b:.2e}" for a, b, k in rows[:5]))
-    assert not bad, "; ".join(bad)
+    check_grads_rows(grad_errors({k: named[k].grad for k in g64}, g64, g32), width=40)
 
 
 def test_resunetpp_pad_crop():
@@ -181,7 +118,7 @@ def test_resunetpp_pad_crop():
         loss, dice, ce = m._loss(logits, y)
     torch.cuda.synchronize()
     assert tuple(logits.shape) == d["logits"].shape == (1, 13, 5, 24, 40)
-    check_logits("rupp_pad_hw", logits.cpu().numpy(), d["logits"])
+    check_logits("rupp_pad_hw", logits, d["logits"], max_flips=8)
     assert math.isclose(float(loss), float(d["loss"]), rel_tol=1e-5)
     assert math.isclose(float(dice), float(d["dice"]), rel_tol=1e-5)
     assert math.isclose(float(ce), float(d["ce"]), rel_tol=1e-5)
@@ -293,11 +230,7 @@ def test_resunetpp_step_is_deterministic():
     m = build(d)
     x = torch.from_numpy(d["x"]).to(DEV)
     y = torch.from_numpy(d["labels"]).to(DEV)
-    l1, g1 = _step(m, x, y)
-    l2, g2 = _step(m, x, y)
-    assert torch.equal(l1, l2)
-    for k in g1:
-        assert torch.equal(g1[k], g2[k]), k
+    assert_steps_bitwise(lambda: _step(m, x, y))
 
 
 def test_resunetpp_no_grad_forward_equals_train_forward():
@@ -305,12 +238,7 @@ def test_resunetpp_no_grad_forward_equals_train_forward():
     m = build(d)
     x = torch.from_numpy(d["x"]).to(DEV)
     m.train()
-    a = m(x).detach().clone()
-    m.eval()
-    with torch.no_grad():
-        b = m(x)
-    torch.cuda.synchronize()
-    assert torch.equal(a, b)
+    assert_no_grad_forward_equals_train(m, x, eval_mode=True)
 
 
 def test_resunetpp_steps_log_the_reference_keys():

@@ -9,7 +9,7 @@ the halo exchange on the engine's side stream beside their interior depth tiles
 
 Gradients are judged BRANCH-CONSISTENTLY: against the fp64 oracle run with the
 sharded engine's own LeakyReLU signs and max-pool argmaxes (each rank's slab,
-gathered; test_gpu_parity.engine_branch_masks / oracle_grads_st), not against the
+gathered; _spff_checks.engine_branch_masks / oracle_grads_st), not against the
 unsharded engine.  Two fp32 engines whose reductions sum in different orders may
 put a LeakyReLU input that sits on its kink on opposite sides, which moves a
 gradient tensor by up to 14 % at these tiny sizes (round 2: the 4-wave conv tiles'
@@ -22,13 +22,15 @@ volume is checked against the kink-consistent oracle in test_gpu_baseline_sizes.
 (at 1.3 M voxels LeakyReLU / pool knife-edge flips move whole gradient tensors, so an
 engine-vs-engine comparison there is not meaningful).  Marked gpu."""
 import os
-import socket
 
 import numpy as np
 import pytest
 import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
+
+from _golden import free_port
+from _spff_checks import check_grads, engine_branch_masks, gather_masks, oracle_grads_st, pack_masks
 
 pytestmark = pytest.mark.gpu
 K, BASE, SHAPE = 5, 8, (1, 5, 8, 32, 32)
@@ -38,14 +40,6 @@ HCASES = {"small": (2, 32, 64, 5, 8)}
 
 def _shape(depth):
     return (SHAPE[0], SHAPE[1], depth, SHAPE[3], SHAPE[4])
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
 
 
 def _model(math_mode, depth=SHAPE[2], k=K, base=BASE, in_ch=SHAPE[1]):
@@ -73,38 +67,14 @@ def _cfg(k=K, base=BASE, in_ch=SHAPE[1]):
 
 def _save_masks(core, local_shape, cfg):
     """this rank's LeakyReLU signs / pool argmaxes over its own slab (npz-ready)"""
-    from test_gpu_parity import engine_branch_masks
-    masks = engine_branch_masks(core, local_shape, core._synth_state, cfg)
-    mk = {}
-    for kk, m in masks.items():
-        a = m.numpy()
-        mk["m_" + kk] = np.packbits(a) if a.dtype == np.bool_ else a.astype(np.uint8)
-        mk["s_" + kk] = np.array(a.shape)
-    return mk
-
-
-def _gather_masks(parts, axis):
-    """the ranks' branch decisions concatenated along the sharded axis (2 = D, 3 = H)"""
-    masks = {}
-    for kk in (f[2:] for f in parts[0].files if f.startswith("m_")):
-        segs = []
-        for p in parts:
-            shp = tuple(int(v) for v in p["s_" + kk])
-            a = p["m_" + kk]
-            a = np.unpackbits(a)[:int(np.prod(shp))].astype(bool) if kk[:4] != "pool" else a
-            segs.append(a.reshape(shp))
-        cat = np.concatenate(segs, axis=axis)
-        masks[kk] = (torch.from_numpy(cat) if cat.dtype == np.bool_
-                     else torch.from_numpy(cat.astype(np.int64)))
-    return masks
+    return pack_masks(engine_branch_masks(core, local_shape, core._synth_state, cfg))
 
 
 def _check_vs_oracle(parts, axis, st, cfg, x, y, mth, device="cpu"):
     """the sharded engine's gradients (rank 0; all ranks hold the same all-reduced
     gradient) vs the fp64 oracle with the sharded engine's own branch decisions
     (``device`` != "cpu": the fp64 oracle alone, evaluated there, floor tolerance)"""
-    from test_gpu_parity import check_grads, oracle_grads_st
-    masks = _gather_masks(parts, axis)
+    masks = gather_masks(parts, axis)
     ref64, ref32, nflip, absb = oracle_grads_st(cfg, st, x.numpy(), y.numpy(), masks,
                                                 device=device, fp32=device == "cpu")
     print(f"  branch decisions differing from the fp64 oracle's own: {nflip}")
@@ -190,7 +160,7 @@ def test_depth_sharded_engine_matches_unsharded(tmp_path, world, math_mode, dept
     ref = logits.detach().cpu().numpy()
     grads = {k: p.grad.cpu().numpy() for k, p in core.named_parameters(remove_duplicate=False) if p.grad is not None}
     out = str(tmp_path / "sh")
-    mp.spawn(_worker, args=(world, _free_port(), math_mode, out, depth), nprocs=world, join=True)
+    mp.spawn(_worker, args=(world, free_port(), math_mode, out, depth), nprocs=world, join=True)
     parts = [np.load(f"{out}.{r}.npz") for r in range(world)]
     lg = np.concatenate([p["logits"] for p in parts], axis=2)
     e = float(np.abs(lg - ref).max())
@@ -226,7 +196,7 @@ def test_height_sharded_engine_matches_unsharded(tmp_path, world, math_mode, cas
     del core, logits, loss
     torch.cuda.empty_cache()
     out = str(tmp_path / "hsh")
-    mp.spawn(_hworker, args=(world, _free_port(), math_mode, out, case, memory), nprocs=world,
+    mp.spawn(_hworker, args=(world, free_port(), math_mode, out, case, memory), nprocs=world,
              join=True)
     parts = [np.load(f"{out}.{r}.npz") for r in range(world)]
     lg = np.concatenate([p["logits"] for p in parts], axis=3)
@@ -305,7 +275,7 @@ def test_depth_sharded_world8_f16x3_overlapped(tmp_path):
     del core, logits, loss
     torch.cuda.empty_cache()
     out = str(tmp_path / "w8")
-    mp.spawn(_w8_worker, args=(world, _free_port(), mth, out), nprocs=world, join=True)
+    mp.spawn(_w8_worker, args=(world, free_port(), mth, out), nprocs=world, join=True)
     parts = [np.load(f"{out}.{r}.npz") for r in range(world)]
     lg = np.concatenate([p["logits"] for p in parts], axis=2)
     e = float(np.abs(lg - ref).max())
@@ -373,7 +343,7 @@ def test_depth_sharded_rccl_two_gpus(tmp_path, overlap):
     ref, loss_ref = logits.detach().cpu().numpy(), float(loss)
     del core, logits, loss
     out = str(tmp_path / "rccl")
-    mp.spawn(_rccl_worker, args=(2, _free_port(), out, overlap), nprocs=2, join=True)
+    mp.spawn(_rccl_worker, args=(2, free_port(), out, overlap), nprocs=2, join=True)
     parts = [np.load(f"{out}.{r}.npz") for r in range(2)]
     lg = np.concatenate([p["logits"] for p in parts], axis=2)
     e = float(np.abs(lg - ref).max())

@@ -14,6 +14,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from _compare import fp32_bound
 from innovative3D import _engine as E
 
 pytestmark = pytest.mark.gpu
@@ -21,12 +22,6 @@ DEV = "cuda"
 
 SHAPES = [(1, 1, 1, 1, 8), (2, 3, 5, 9, 8), (1, 2, 7, 7, 64), (1, 5, 24, 40, 32),
           (1, 2, 3, 5, 256), (2, 6, 33, 40, 24), (1, 4100, 1, 1, 8)]
-
-
-def _bound(ref, cpu32):
-    ref_max = float(ref.abs().max())
-    e32 = float((cpu32.double() - ref).abs().max())
-    return max(16.0 * e32, 1e-6 * ref_max), e32, ref_max
 
 
 def _case(shape):
@@ -67,7 +62,7 @@ def test_spatial_attn_matches_fp64(shape):
     got = {"y": y, "attn": attn, "dx": dx, "dw": dw}
     bad = []
     for name in ("y", "attn", "dx", "dw"):
-        bound, e32, ref_max = _bound(ref[name], cpu32[name])
+        bound, e32, ref_max = fp32_bound(ref[name], cpu32[name])
         err = float((got[name].cpu().double() - ref[name]).abs().max())
         print(f"[spatial_attn {shape}] {name}: err {err:.3e}  cpu-fp32 err {e32:.3e}  "
               f"bound {bound:.3e}  max|ref| {ref_max:.3e}")
@@ -97,7 +92,7 @@ def test_spatial_attn_lowest_index_takes_a_tie():
     assert torch.equal(idx.cpu().long(), top.clamp(max=5))
     dx, _dw = E.spatial_attn_bwd(dy.to(DEV), xd, wd, attn, amap, idx)
     ref, cpu32 = _torch_ref(x, w, dy, torch.float64), _torch_ref(x, w, dy, torch.float32)
-    bound, e32, _ = _bound(ref["dx"], cpu32["dx"])
+    bound, e32, _ = fp32_bound(ref["dx"], cpu32["dx"])
     err = float((dx.cpu().double() - ref["dx"]).abs().max())
     print(f"[spatial_attn tie] dx: err {err:.3e}  cpu-fp32 err {e32:.3e}  bound {bound:.3e}")
     assert err <= bound
@@ -107,18 +102,19 @@ def test_spatial_attn_lowest_index_takes_a_tie():
 # The rules of tests/test_gpu_resunetpp.py: max|dlogit| <= 1e-3, at most 8 argmax flips, all
 # at near-ties (top-2 margin below 2 x the error), loss within 1e-5 relative; every parameter
 # gradient against the fp64 test oracle (tests/_spatial_oracle.py) run with the engine's own
-# branch decisions -- LeakyReLU signs and pool argmaxes (test_gpu_parity.engine_branch_masks),
+# branch decisions -- LeakyReLU signs and pool argmaxes (_spff_checks.engine_branch_masks),
 # the sa argmax indices and the gates' ReLU signs read through plan.saved -- within
 # max(1e-3, 8 x the fp32 oracle's error), scaled by max|ref|.
 import math  # noqa: E402
 
-import numpy as np  # noqa: E402
 
 import _spatial_oracle as S  # noqa: E402
 import innovative3D.helpers as Hh  # noqa: E402
 import innovative3D.models as M  # noqa: E402
+from _compare import (assert_no_grad_forward_equals_train, assert_steps_bitwise,  # noqa: E402
+                      check_grads_rows, check_logits, grad_errors)
 from _golden import cfg_of, load, state_of  # noqa: E402
-from test_gpu_parity import engine_branch_masks, near_tie_mask, oracle_grads_st  # noqa: E402
+from _spff_checks import engine_branch_masks, oracle_grads_st  # noqa: E402
 
 FIXTURES = ("spa_full_b8", "spa_only_d1", "spa_ragged_hw", "gate_only_cin5", "spa_lit_k13")
 LVL = {"enc1": 0, "enc2": 1, "enc3": 2, "bott": 3, "g1": 0, "g2": 1, "g3": 2}
@@ -166,17 +162,6 @@ def engine_masks(core, d):
     return masks, extra
 
 
-def check_logits(tag, lg, ref):
-    err = float(np.abs(lg - ref).max())
-    flips = lg.argmax(1) != ref.argmax(1)
-    nf = int(flips.sum())
-    print(f"{tag}: max|dlogit| = {err:.3e}  argmax flips = {nf} of {flips.size}")
-    assert err <= 1e-3
-    assert nf <= 8
-    if nf:
-        assert not (flips & ~near_tie_mask(ref, 2 * err)).any(), f"{nf} flips outside near-ties"
-
-
 def train_step(core, d):
     x = torch.from_numpy(d["x"]).to(DEV)
     y = torch.from_numpy(d["labels"]).to(DEV)
@@ -196,7 +181,7 @@ def test_network_matches_reference(name, mth):
     meta = d["meta"]
     _top, core = build_fixture_core(d, mth)
     logits, loss = train_step(core, d)
-    check_logits(f"{name}/{mth}", logits.cpu().numpy(), d["logits"])
+    check_logits(f"{name}/{mth}", logits, d["logits"], max_flips=8)
     print(f"  loss {float(loss):.7f} vs {float(d['loss']):.7f}")
     assert math.isclose(float(loss), float(d["loss"]), rel_tol=1e-5)
     masks, extra = engine_masks(core, d)
@@ -207,41 +192,27 @@ def test_network_matches_reference(name, mth):
     named = {k: v for k, v in core.named_parameters(remove_duplicate=False)
              if not k.endswith("._mask")}
     assert set(named) == set(g64)
-    rows, bad = [], []
-    for k, r64 in g64.items():
-        g = named[k].grad.detach().double().cpu().numpy()
-        scale = max(float(np.abs(r64).max()), 1e-12)
-        e_gpu = float(np.abs(g - r64).max()) / scale
-        e_32 = float(np.abs(g32[k] - r64).max()) / scale
-        rows.append((e_gpu, e_32, k))
-        if not e_gpu <= max(1e-3, 8 * e_32):
-            bad.append(f"{k}: gpu {e_gpu:.2e} vs fp32-oracle {e_32:.2e}")
-    rows.sort(reverse=True)
-    print("\n".join(f"  {k:36s} gpu {a:.2e}  fp32-oracle {b:.2e}" for a, b, k in rows[:6]))
-    assert not bad, "; ".join(bad)
+    check_grads_rows(grad_errors({k: named[k].grad for k in g64}, g64, g32), top=6, width=36)
 
 
 @pytest.mark.parametrize("name", ["spa_full_b8", "spa_ragged_hw"])
 def test_no_grad_forward_is_the_train_forward(name):
     d = load(name)
     _top, core = build_fixture_core(d)
-    logits, _loss = train_step(core, d)
-    with torch.no_grad():
-        lg = core(torch.from_numpy(d["x"]).to(DEV))
-    torch.cuda.synchronize()
+    logits, _loss = train_step(core, d)  # a backward lies between that forward and the next
+    lg = assert_no_grad_forward_equals_train(core, torch.from_numpy(d["x"]).to(DEV))
     assert torch.equal(lg, logits)
 
 
 def test_forward_backward_is_deterministic():
     d = load("spa_full_b8")
     _top, core = build_fixture_core(d)
-    runs = []
-    for _ in range(2):
+
+    def step():
         logits, _loss = train_step(core, d)
-        runs.append([logits.clone()] + [p.grad.clone() for p in core.parameters()])
-    assert len(runs[0]) == len(runs[1]) > 40
-    for a, b in zip(*runs):
-        assert torch.equal(a, b)
+        return logits.clone(), {k: p.grad.clone() for k, p in core.named_parameters()}
+    _logits, grads = assert_steps_bitwise(step)
+    assert len(grads) >= 40
 
 
 def test_lit_training_step_and_adam():

@@ -1,6 +1,6 @@
 """Every stage of the engine's backward, per voxel, against the fp64 oracle.  Marked gpu.
 
-check_grads (tests/test_gpu_parity.py) sees the backward only through parameter gradients,
+check_grads (tests/_spff_checks.py) sees the backward only through parameter gradients,
 each a sum over all voxels: a pass that is wrong on one row of a ragged tile, on the last
 chunk of a split reduction or on one (b, d) slab stays far below its 1e-3
 (tests/test_stage_oracle_cpu.py measures one such case).  Here the backward is stopped
@@ -18,15 +18,13 @@ f32, bf16x6 and f16x3 are held to the same bar.
 Out of scope: use_spatial / use_skip_gate plans (ds lives in grad.dy2 and sa_bwd_step runs
 first) and sharded plans.
 """
-import numpy as np
 import pytest
 import torch
 
 from _golden import cfg_of, load, state_of
+from _spff_checks import engine_branch_masks, load_core, synth_core
 from _stage_oracle import failing, format_rows, stage_errors, stage_grads
 from oracle import spff_oracle as O
-from test_gpu_parity import engine_branch_masks, load_core
-import innovative3D.models as M
 import innovative3D.helpers as Hh
 
 pytestmark = pytest.mark.gpu
@@ -65,15 +63,8 @@ def _build(case):
         x, y = torch.from_numpy(d["x"]), torch.from_numpy(d["labels"])
     else:
         from innovative3D.synthetic import synthetic_batch
-        from innovative3D.weightgen import synth_state
         B, D, H, W = case["shape"]
-        core = M.build_spct_energyfilm_fourier(num_classes=K_SYNTH, base=case["base"],
-                                               in_channels=IN_CH)
-        for b in core._blocks():
-            b.fgate._ensure_mask(D, "cpu")
-        st = synth_state([(k, tuple(v.shape)) for k, v in core.state_dict().items()], seed=31,
-                         mask_jitter=0.25)
-        core.load_state_dict({k: torch.from_numpy(v) for k, v in st.items()})
+        core, st = synth_core(K_SYNTH, case["base"], IN_CH, D, 31, 0.25)
         core = core.to(DEV)
         cfg = O.SpffCfg(in_ch=IN_CH, num_classes=K_SYNTH, base=case["base"])
         x, y = synthetic_batch(B, IN_CH, D, H, W, num_classes=K_SYNTH, ignore_frac=0.03, seed=32)

@@ -15,6 +15,8 @@ import numpy as np
 import pytest
 import torch
 
+from _compare import check_grads_rows, check_logits, grad_errors
+from _swin_checks import engine_act_masks
 from oracle import swin_oracle as S
 from innovative3D.weightgen import synth_state
 import innovative3D.models as M
@@ -66,47 +68,12 @@ def test_swin_matches_oracle(shape, mth):
     finally:
         S.ACT_MASKS = None
     r64 = ref[torch.float64]
-    err = float((lg - r64[0]).abs().max())
-    print(f"{shape}/{mth}: max|dlogit| {err:.3e}  loss {float(loss):.7f} vs {float(r64[1]):.7f}")
-    assert err <= 1e-3
-    am, am_ref = lg.argmax(1), r64[0].argmax(1)
-    top2 = r64[0].topk(2, dim=1).values
-    ties = (top2[:, 0] - top2[:, 1]) < 2 * err
-    assert not ((am != am_ref) & ~ties).any()
+    check_logits(f"{shape}/{mth}", lg, r64[0])
+    print(f"  loss {float(loss):.7f} vs {float(r64[1]):.7f}")
     assert abs(float(loss) - float(r64[1])) <= 1e-5 * abs(float(r64[1]))
     named = dict(m.named_parameters())
-    rows, bad = [], []
-    for k, g64 in r64[2].items():
-        g = named[k].grad.detach().cpu().double()
-        scale = max(float(g64.abs().max()), 1e-12)
-        e = float((g - g64).abs().max()) / scale
-        e32 = float((ref[torch.float32][2][k] - g64).abs().max()) / scale
-        rows.append((e, e32, k))
-        if e > max(1e-3, 16 * e32):
-            bad.append(f"{k}: {e:.2e} (fp32 oracle {e32:.2e})")
-    rows.sort(reverse=True)
-    print("\n".join(f"  {k:60s} gpu {a:.2e}  fp32-oracle {b:.2e}" for a, b, k in rows[:8]))
-    assert not bad, "; ".join(bad)
-
-
-RB_LEVEL = {"encoder1.layer": 0, "encoder2.layer": 1, "encoder3.layer": 2, "encoder4.layer": 3,
-            "encoder10.layer": 5, "decoder5.conv_block": 4, "decoder4.conv_block": 3,
-            "decoder3.conv_block": 2, "decoder2.conv_block": 1, "decoder1.conv_block": 0}
-
-
-def engine_act_masks(m, xshape):
-    """Sign patterns of the residual blocks' LeakyReLU inputs as the engine saw
-    them: sign(a1) and sign(out) (a LeakyReLU keeps the sign of its input)."""
-    plan = m._plan(torch.empty(xshape, device=DEV))
-    B, _, D, H, W = xshape
-    out = {}
-    for name, lvl in RB_LEVEL.items():
-        for key, act in (("a1", "act1"), ("out", "act2")):
-            t = plan.saved(f"{name}.{key}").cpu()
-            C = t.shape[1]
-            t = t.view(B, D >> lvl, H >> lvl, W >> lvl, C).permute(0, 4, 1, 2, 3)
-            out[f"{name}.{act}"] = (t > 0).contiguous()
-    return out
+    rows = grad_errors({k: named[k].grad for k in r64[2]}, r64[2], ref[torch.float32][2])
+    check_grads_rows(rows, factor=16, top=8, width=60)
 
 
 # (K, B, (D, H, W), fraction of voxels at 255, include_bg, ce_weight, classes drawn)

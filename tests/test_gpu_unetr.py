@@ -21,18 +21,13 @@ import torch.nn.functional as F
 
 import _unetr_oracle as U
 import innovative3D.models as M
-from _golden import load
+from _compare import (assert_no_grad_forward_equals_train, assert_steps_bitwise, check_grads_rows,
+                      check_logits, fp32_bound, grad_errors, lrelu_act_masks)
+from _golden import load, synth_state_of
 from innovative3D import _engine as E
-from innovative3D.weightgen import synth_state
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
-
-
-def _bound(ref, cpu32):
-    ref_max = float(ref.abs().max())
-    e32 = float((cpu32.double() - ref).abs().max())
-    return max(16.0 * e32, 1e-6 * ref_max), e32, ref_max
 
 
 # ------------------------------------------------------------------ attention --
@@ -63,7 +58,7 @@ def test_vit_attention_matches_fp64(shape):
     torch.cuda.synchronize()
     for name, got, k in (("O", O, 0), ("dqkv", dqkv, 1)):
         ref = res[torch.float64][k]
-        bound, e32, ref_max = _bound(ref, res[torch.float32][k])
+        bound, e32, ref_max = fp32_bound(ref, res[torch.float32][k])
         err = float((got.cpu().double() - ref).abs().max())
         print(f"[vit_attn {shape}] {name}: err {err:.3e}  cpu-fp32 err {e32:.3e}  "
               f"bound {bound:.3e}  max|ref| {ref_max:.3e}")
@@ -113,7 +108,7 @@ def test_resize3d_matches_fp64(src, dst, C):
     torch.cuda.synchronize()
     for name, got, k in (("y", y, 0), ("dx", dx, 1)):
         ref = cl(res[torch.float64][k])
-        bound, e32, ref_max = _bound(ref, cl(res[torch.float32][k]))
+        bound, e32, ref_max = fp32_bound(ref, cl(res[torch.float32][k]))
         err = float((got.cpu().double() - ref).abs().max())
         print(f"[resize3d {src}->{dst} C={C}] {name}: err {err:.3e}  cpu-fp32 err {e32:.3e}  "
               f"bound {bound:.3e}  max|ref| {ref_max:.3e}")
@@ -156,8 +151,7 @@ _FIX = {}
 def _fixture(name):
     if name not in _FIX:
         d = load(name)
-        d["state"] = synth_state([(k, tuple(v)) for k, v in d["state_shapes"].items()],
-                                 d["meta"]["seed"])
+        d["state"] = synth_state_of(d)
         _FIX[name] = d
     return _FIX[name]
 
@@ -188,28 +182,12 @@ def _engine_act_masks(lit, d):
     B, _c, D, H, W = d["x"].shape
     pad = [-(-v // 16) * 16 for v in (D, H, W)]
     plan = lit.net.net._plan(torch.empty((B, 1, *pad), device=DEV))
-    g = d["meta"]["img"]
-    out = {}
-    for name, lvl in RB_LEVEL.items():
-        for key, act in (("a1", "act1"), ("out", "act2")):
-            t = plan.saved(f"{name}.{key}").cpu()
-            t = t.view(B, g[0] >> lvl, g[1] >> lvl, g[2] >> lvl, t.shape[1]).permute(0, 4, 1, 2, 3)
-            out[f"{name}.{act}"] = (t > 0).contiguous()
-    return out
+    return lrelu_act_masks(plan, RB_LEVEL, B, *d["meta"]["img"])
 
 
 def _check_forward(tag, d, logits, loss):
-    ref = torch.from_numpy(d["logits"]).double()
-    lg = logits.cpu().double()
-    err = float((lg - ref).abs().max())
-    top2 = ref.topk(2, dim=1).values
-    ties = (top2[:, 0] - top2[:, 1]) < 2 * err
-    flips = (lg.argmax(1) != ref.argmax(1))
-    print(f"[{tag}] max|dlogit| {err:.3e}  argmax flips {int(flips.sum())} "
-          f"(outside near-ties {int((flips & ~ties).sum())})  loss {float(loss):.7f} vs "
-          f"{float(d['loss']):.7f}")
-    assert err <= 1e-3
-    assert not (flips & ~ties).any()
+    check_logits(tag, logits.cpu().double(), d["logits"].astype(np.float64))
+    print(f"  loss {float(loss):.7f} vs {float(d['loss']):.7f}")
     assert abs(float(loss) - float(d["loss"])) <= 1e-5 * abs(float(d["loss"]))
 
 
@@ -229,18 +207,9 @@ def test_unetr_matches_fixture_and_kink_consistent_oracle(name, mth):
     finally:
         U.ACT_MASKS = None
     named = dict(lit.net.net.named_parameters())
-    rows, bad = [], []
-    for k, g64 in ref[torch.float64].items():
-        g = named[k].grad.detach().cpu().double()
-        scale = max(float(g64.abs().max()), 1e-12)
-        e = float((g - g64).abs().max()) / scale
-        e32 = float((ref[torch.float32][k] - g64).abs().max()) / scale
-        rows.append((e, e32, k))
-        if e > max(1e-3, 16 * e32):
-            bad.append(f"{k}: {e:.2e} (fp32 oracle {e32:.2e})")
-    rows.sort(reverse=True)
-    print("\n".join(f"  {k:56s} gpu {a:.2e}  fp32-oracle {b:.2e}" for a, b, k in rows[:6]))
-    assert not bad, "; ".join(bad)
+    g64 = ref[torch.float64]
+    rows = grad_errors({k: named[k].grad for k in g64}, g64, ref[torch.float32])
+    check_grads_rows(rows, factor=16, top=6, width=56)
     unused = [k for k, p in named.items() if k not in ref[torch.float64]]
     assert unused and all("cross_attn" in k and named[k].grad is None for k in unused)
 
@@ -279,7 +248,7 @@ def test_unetr_registry_width_matches_fixture(mth):
         else:
             es = 0.0
         rows.append((e / gmax, en, tol, k))
-        if e / gmax > tol or en > tol or es > tol:
+        if not (e / gmax <= tol and en <= tol and es <= tol):
             bad.append(f"{k}: entries {e / gmax:.2e} norm {en:.2e} sum {es:.2e} (bound {tol:.2e})")
     rows.sort(reverse=True)
     print("\n".join(f"  {k:56s} entries {a:.2e}  norm {b:.2e}  bound {t:.2e}"
@@ -291,26 +260,19 @@ def test_unetr_registry_width_matches_fixture(mth):
 def test_unetr_two_steps_are_bitwise_equal():
     d = _fixture("unetr_resample_b2")
     lit = _lit(d, "f16x3")
-    runs = []
-    for _ in range(2):
+
+    def step():
         logits, loss = _step(lit, d)
-        runs.append((logits.clone(), loss.clone(),
-                     {k: p.grad.clone() for k, p in lit.named_parameters() if p.grad is not None}))
-    assert torch.equal(runs[0][0], runs[1][0]) and torch.equal(runs[0][1], runs[1][1])
-    assert runs[0][2].keys() == runs[1][2].keys()
-    for k, g in runs[0][2].items():
-        assert torch.equal(g, runs[1][2][k]), k
+        grads = {k: p.grad.clone() for k, p in lit.named_parameters() if p.grad is not None}
+        return logits.clone(), {"loss": loss.clone(), **grads}
+    assert_steps_bitwise(step)
 
 
 def test_unetr_inference_equals_training_forward():
     d = _fixture("unetr_resample_b2")
     lit = _lit(d, "f16x3")
     x = torch.from_numpy(d["x"]).to(DEV)
-    a = lit(x).detach().clone()
-    with torch.no_grad():
-        b = lit(x)
-    torch.cuda.synchronize()
-    assert not b.requires_grad and torch.equal(a, b)
+    assert_no_grad_forward_equals_train(lit, x)
 
 
 def test_unetr_registry_training_step():

@@ -16,7 +16,6 @@ same all-reduced gradient, and the gradient's relative L2 distance to the 1-GPU 
 printed per tensor (two fp32 sums over 134 M voxels in different orders, with
 LeakyReLU / max-pool knife edges; reported, bounded loosely).  Marked gpu."""
 import os
-import socket
 
 import numpy as np
 import pytest
@@ -24,28 +23,16 @@ import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
+from _golden import free_port
+
 pytestmark = pytest.mark.gpu
 SHAPE, K, BASE, WORLD = (1, 5, 512, 512, 512), 13, 32, 8
 SHM = "/dev/shm"
 
 
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
 def _model(D):
-    import innovative3D.models as M
-    from innovative3D.weightgen import synth_state
-    core = M.build_spct_energyfilm_fourier(num_classes=K, base=BASE, in_channels=SHAPE[1])
-    for b in core._blocks():
-        b.fgate._ensure_mask(D, "cpu")
-    st = synth_state([(k, tuple(v.shape)) for k, v in core.state_dict().items()], seed=0)
-    core.load_state_dict({k: torch.from_numpy(v) for k, v in st.items()})
-    core = core.to("cuda")
+    from _spff_checks import synth_core
+    core = synth_core(K, BASE, SHAPE[1], D, 0)[0].to("cuda")
     core.math = "f16x3"
     core.memory = "lean"
     return core
@@ -108,7 +95,7 @@ def test_volume512_depth_sharded_8_ranks_matches_one_gpu():
         E.release_plans()
         torch.cuda.empty_cache()
         # --- 8 depth slabs of 64 slices, one process each, host-staged gloo ---
-        mp.spawn(_worker, args=(WORLD, _free_port(), tag), nprocs=WORLD, join=True)
+        mp.spawn(_worker, args=(WORLD, free_port(), tag), nprocs=WORLD, join=True)
         files += [f"{SHM}/{tag}_lg{r}.npy" for r in range(WORLD)]
         files += [f"{SHM}/{tag}_g{r}.npz" for r in range(WORLD)]
         amax = float(np.abs(ref).max())

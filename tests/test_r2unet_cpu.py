@@ -8,7 +8,8 @@ import pytest
 import torch
 
 import _r2u_oracle as R
-from _golden import load
+from _compare import check_fixture_grads
+from _golden import load, synth_state_of
 
 NET_FIXTURES = ["r2u_registry_k13", "r2u_core_b8_t3", "r2u_pad_hw"]
 LOSS_CASES = ["a", "b", "c", "d"]
@@ -17,11 +18,6 @@ LOSS_CASES = ["a", "b", "c", "d"]
 def cfg_of(meta):
     return R.R2UCfg(num_classes=meta["K"], base=meta["base"], in_ch=meta["in_ch"], t=meta["t"],
                     pad_multiple=meta["pad_multiple"])
-
-
-def state_of(d):
-    from innovative3D.weightgen import synth_state
-    return synth_state([(k, tuple(v)) for k, v in d["state_shapes"].items()], d["meta"]["seed"])
 
 
 def build_lit(meta):
@@ -37,7 +33,7 @@ def test_r2u_oracle_matches_reference(name):
     d = load(name)
     meta = d["meta"]
     torch.set_num_threads(8)
-    P = R.params_from_state(state_of(d))
+    P = R.params_from_state(synth_state_of(d))
     x, y = torch.from_numpy(d["x"]), torch.from_numpy(d["labels"])
     logits, loss, dice = R.fwd_bwd(P, x, y, cfg_of(meta), meta["ignore_index"])
     ref = d["logits"]
@@ -48,27 +44,8 @@ def test_r2u_oracle_matches_reference(name):
     assert torch.equal(logits.argmax(1), torch.from_numpy(ref).argmax(1))
     assert math.isclose(float(loss), float(d["loss"]), rel_tol=1e-5)
     assert math.isclose(float(dice), float(d["dice"]), rel_tol=1e-5)
-    gkeys = [k for k in d if k.startswith("grad/") or k.startswith("gradhead/")]
-    if not gkeys:
-        return  # r2u_pad_hw: logits, loss and dice only
-    # gradients: the rule of test_unet3d_cpu.py (5e-4 of max|ref| + 2e-5 of the model's
-    # largest gradient entry; the fixture is one CPU's fp32 result)
-    gmax = max(float(np.abs(d[k]).max()) for k in gkeys)
-    for k in d["param_names"]:
-        k = str(k)
-        g = P[k].grad.numpy()
-        if "grad/" + k in d:
-            ref_g = d["grad/" + k]
-            scale = max(1e-6, float(np.abs(ref_g).max()))
-            assert float(np.abs(g - ref_g).max()) <= 5e-4 * scale + 2e-5 * gmax, k
-        else:
-            flat = g.reshape(-1)
-            scale = max(1e-6, float(np.abs(d["gradhead/" + k]).max()))
-            np.testing.assert_allclose(flat[:64], d["gradhead/" + k], atol=5e-4 * scale + 2e-5 * gmax)
-            np.testing.assert_allclose(flat[-64:], d["gradtail/" + k], atol=5e-4 * scale + 2e-5 * gmax)
-            s = d["gradsum/" + k]
-            assert math.isclose(float(np.sqrt((flat.astype(np.float64) ** 2).sum())), float(s[1]),
-                                rel_tol=1e-4, abs_tol=1e-9), k
+    if any(k.startswith(("grad/", "gradhead/")) for k in d):  # r2u_pad_hw: logits, loss and dice only
+        check_fixture_grads(d, lambda k: P[k].grad)
 
 
 @pytest.mark.parametrize("case", LOSS_CASES)

@@ -8,7 +8,8 @@ import pytest
 import torch
 
 import _rupp_oracle as R
-from _golden import GOLDEN, load
+from _compare import check_fixture_grads
+from _golden import GOLDEN, load, synth_state_of
 
 NET_FIXTURES = ["rupp_registry_k13", "rupp_core_b8", "rupp_aspp_wide", "rupp_pad_hw"]
 LOSS_CASES = ["a", "b", "c", "d", "e"]
@@ -17,11 +18,6 @@ LOSS_CASES = ["a", "b", "c", "d", "e"]
 def cfg_of(meta):
     return R.RUPPCfg(num_classes=meta["K"], base=meta["base"], in_ch=meta["in_ch"],
                      pad_multiple=meta["pad_multiple"])
-
-
-def state_of(d):
-    from innovative3D.weightgen import synth_state
-    return synth_state([(k, tuple(v)) for k, v in d["state_shapes"].items()], d["meta"]["seed"])
 
 
 def build_lit(meta):
@@ -37,7 +33,7 @@ def test_rupp_oracle_matches_reference(name):
     d = load(name)
     meta = d["meta"]
     torch.set_num_threads(8)
-    P = R.params_from_state(state_of(d))
+    P = R.params_from_state(synth_state_of(d))
     x, y = torch.from_numpy(d["x"]), torch.from_numpy(d["labels"])
     logits, loss, dice, ce = R.fwd_bwd(P, x, y, cfg_of(meta), meta["ignore_index"])
     ref = d["logits"]
@@ -49,34 +45,15 @@ def test_rupp_oracle_matches_reference(name):
     assert math.isclose(float(loss), float(d["loss"]), rel_tol=1e-5)
     assert math.isclose(float(dice), float(d["dice"]), rel_tol=1e-5)
     assert math.isclose(float(ce), float(d["ce"]), rel_tol=1e-5)
-    gkeys = [k for k in d if k.startswith("grad/") or k.startswith("gradhead/")]
-    if not gkeys:
-        return  # rupp_pad_hw: logits, loss and dice only
-    # gradients: the rule of test_r2unet_cpu.py (5e-4 of max|ref| + 2e-5 of the model's
-    # largest gradient entry; the fixture is one CPU's fp32 result)
-    gmax = max(float(np.abs(d[k]).max()) for k in gkeys)
-    for k in d["param_names"]:
-        k = str(k)
-        g = P[k].grad.numpy()
-        if "grad/" + k in d:
-            ref_g = d["grad/" + k]
-            scale = max(1e-6, float(np.abs(ref_g).max()))
-            assert float(np.abs(g - ref_g).max()) <= 5e-4 * scale + 2e-5 * gmax, k
-        else:
-            flat = g.reshape(-1)
-            scale = max(1e-6, float(np.abs(d["gradhead/" + k]).max()))
-            np.testing.assert_allclose(flat[:64], d["gradhead/" + k], atol=5e-4 * scale + 2e-5 * gmax)
-            np.testing.assert_allclose(flat[-64:], d["gradtail/" + k], atol=5e-4 * scale + 2e-5 * gmax)
-            s = d["gradsum/" + k]
-            assert math.isclose(float(np.sqrt((flat.astype(np.float64) ** 2).sum())), float(s[1]),
-                                rel_tol=1e-4, abs_tol=1e-9), k
+    if any(k.startswith(("grad/", "gradhead/")) for k in d):  # rupp_pad_hw: logits, loss and dice only
+        check_fixture_grads(d, lambda k: P[k].grad)
 
 
 def test_rupp_aspp_wide_reaches_every_dilation():
     """The fixture's bottleneck (1 x 1 x 10) has off-centre taps inside for dilation 8."""
     d = load("rupp_aspp_wide")
     k = "backbone.b_aspp.branches.3.weight"
-    P = R.params_from_state(state_of(d))
+    P = R.params_from_state(synth_state_of(d))
     R.fwd_bwd(P, torch.from_numpy(d["x"]), torch.from_numpy(d["labels"]), cfg_of(d["meta"]), 255)
     g = P[k].grad.numpy().reshape(P[k].shape[0], P[k].shape[1], 27)
     assert np.abs(g[:, :, 12]).max() > 0 and np.abs(g[:, :, 14]).max() > 0

@@ -6,7 +6,6 @@ exchange plan the engine's sharded plans implement: conv halos, distributed
 InstanceNorm / SE statistics, the FourierGate all-gather, global-D EFiLM
 encodings and the global CE normalisation."""
 import os
-import socket
 
 import numpy as np
 import pytest
@@ -15,15 +14,7 @@ import torch.distributed as dist
 import torch.multiprocessing as mp
 import torch.nn.functional as F
 
-from _golden import cfg_of, load, state_of
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
+from _golden import cfg_of, free_port, load, state_of
 
 
 def _worker(rank, world, port, name, out_path, axis=2):
@@ -72,7 +63,7 @@ def test_sharded_equals_unsharded(tmp_path, name, world, axis):
     dice = O.macro_dice_loss(O.confusion(logits.detach(), y, K, 255), K)
     ce.backward()
     out = str(tmp_path / "sh")
-    mp.spawn(_worker, args=(world, _free_port(), name, out, axis), nprocs=world, join=True)
+    mp.spawn(_worker, args=(world, free_port(), name, out, axis), nprocs=world, join=True)
     parts = [np.load(f"{out}.{r}.npz") for r in range(world)]
     lg = np.concatenate([p["logits"] for p in parts], axis=axis)
     ref = logits.detach().numpy()

@@ -13,14 +13,9 @@ import torch
 import torch.nn.functional as F
 
 import _unetr_oracle as U
-from _golden import load
+from _golden import load, synth_state_of
 
 NET_FIXTURES = ["unetr_same_k4", "unetr_resample_b2", "unetr_registry_k13"]
-
-
-def state_of(d):
-    from innovative3D.weightgen import synth_state
-    return synth_state([(k, tuple(v)) for k, v in d["state_shapes"].items()], d["meta"]["seed"])
 
 
 def test_registry_has_unetr(monkeypatch):
@@ -65,7 +60,7 @@ def test_state_dict_and_flat_layout(name):
     assert list(sd.keys()) == [str(k) for k in d["state_keys"]]
     assert {k: list(v.shape) for k, v in sd.items()} == d["state_shapes"]
     # a reference checkpoint loads strictly, the unused cross-attention holders included
-    lit.load_state_dict({k: torch.from_numpy(v) for k, v in state_of(d).items()}, strict=True)
+    lit.load_state_dict({k: torch.from_numpy(v) for k, v in synth_state_of(d).items()}, strict=True)
     unused = [str(k) for k in d["unused_params"]]
     assert unused and all("cross_attn" in k for k in unused)
     try:
@@ -94,7 +89,7 @@ def test_oracle_reproduces_fixture(name):
     d = load(name)
     meta = d["meta"]
     torch.set_num_threads(8)
-    net = U.build(meta, state_of(d))
+    net = U.build(meta, synth_state_of(d))
     logits, loss, grads = U.fwd_bwd(net, torch.from_numpy(d["x"]), torch.from_numpy(d["labels"]),
                                     meta)
     ref = d["logits"]
