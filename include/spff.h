@@ -524,6 +524,38 @@ int spff_rupp_loss(const float* logits, const int64_t* labels, int batch, int64_
                    int num_classes, int use_ignore, int ignore_index, int include_bg,
                    double ce_weight, double dice_weight, float* out4, float* dlogits, void* ws,
                    void* stream);
+/* The two losses below run on the same two passes.  m_v = [y_v != ignore_index] (use_ignore
+ * = 0: no such mask), and m_v = 0 too for a label outside [0, K): such a voxel enters no sum
+ * and its dlogits row is zero.  p = softmax(logits) in fp32, g = one-hot(y).  logits /
+ * dlogits [B][vox_per_sample][K] channel-last rows; K in 2..32; SPFF_EINVAL (before any
+ * device call) for K outside that range, batch < 1, vox_per_sample < 1 or a null out4,
+ * dlogits or ws.
+ *
+ * spff_unet3d_loss: LitCicek3DUNet_DepthAdapter_Published._weighted_softmax_ce + ._dice_loss.
+ *   ce = sum_v m u w[y] nll / max(sum_v m u, 1), u = voxel_weights [B vox_per_sample] (NULL:
+ *   1), w = class_weights [K] (NULL: 1; class weights never enter the denominator);
+ *   per sample b and class k = 1..K-1 (include_bg: 0..K-1) dice = 2 I / (P + G + 1e-6),
+ *   I = sum m p g, P = sum m p, G = sum m g;  dice_loss = 1 - mean_{b,k} dice;
+ *   loss = ce_weight ce + dice_weight dice_loss.
+ *   out4 = [ce, loss, dice_loss, sum_v m u (before the clamp)].
+ *   ws >= spff_unet3d_loss_ws_bytes device bytes. */
+size_t spff_unet3d_loss_ws_bytes(int batch, int num_classes);
+int spff_unet3d_loss(const float* logits, const int64_t* labels, int batch, int64_t vox_per_sample,
+                     int num_classes, int use_ignore, int ignore_index,
+                     const float* class_weights, const float* voxel_weights, int include_bg,
+                     double ce_weight, double dice_weight, float* out4, float* dlogits, void* ws,
+                     void* stream);
+/* spff_nnunet_loss: models.dice_ce_loss (soft_dice_loss_from_logits + cross_entropy).
+ *   I = sum m p g, Q = sum m p^2, G = sum m g over the whole batch;
+ *   dice_k = (2 I_k + 1e-5) / (Q_k + G_k + 1e-5) over the classes 1..K-1 (include_bg: 0..K-1);
+ *   loss = ce_weight CE + dice_weight (1 - mean_k dice_k), CE the mean over the voxels with
+ *   m = 1 (NaN when there is none).
+ *   out4 = [ce, loss, dice_mean, N_valid].  ws >= spff_nnunet_loss_ws_bytes device bytes. */
+size_t spff_nnunet_loss_ws_bytes(int batch, int num_classes);
+int spff_nnunet_loss(const float* logits, const int64_t* labels, int batch, int64_t vox_per_sample,
+                     int num_classes, int use_ignore, int ignore_index, int include_bg,
+                     double ce_weight, double dice_weight, float* out4, float* dlogits, void* ws,
+                     void* stream);
 /* Op-level dilated 3x3x3 convolution (the ASPP branches): dilation = padding = `dilation`
  * in all three axes, channel-last rows with pitches ldx / ldy (multiples of 4 floats, so a
  * branch can write its channel range of a wider row), weight W[cout][cin][3][3][3]; cin and

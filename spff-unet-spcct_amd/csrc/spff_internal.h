@@ -647,13 +647,23 @@ hipError_t argmax_rows(const float* logits, const int64_t* labels, int64_t V, in
 //   DICE_RUPP  LitResUNetPP3D_Published._loss (dice_ce_loss_with_metrics, K >= 2): dw soft
 //              Dice with I, P, G pooled over the whole batch (classes >= sc) + cw mean CE over
 //              the valid voxels;  out4 = [ce, loss, dice_mean, N_valid]
-enum DiceKind { DICE_SWIN, DICE_R2U, DICE_RUPP };
+//   DICE_UNET3D LitCicek3DUNet_DepthAdapter_Published._weighted_softmax_ce + ._dice_loss
+//              (K >= 2): cw sum m u w[y] nll / max(sum m u, 1), u = voxel_w (null: 1), w =
+//              class_w (null: 1), + dw per-sample soft Dice 2 I / (P + G + 1e-6) over the
+//              classes >= sc;  out4 = [ce, loss, dice_loss, sum m u]
+//   DICE_NNUNET models.dice_ce_loss (K >= 2): cw mean CE over the valid voxels + dw soft Dice
+//              (2 I + 1e-5) / (Q + G + 1e-5), Q = sum m p^2, pooled over the batch (classes >=
+//              sc);  out4 = [ce, loss, dice_mean, N_valid]
+// The last two also mask a label outside [0, K): no term in any sum and a zero dlogits row.
+enum DiceKind { DICE_SWIN, DICE_R2U, DICE_RUPP, DICE_UNET3D, DICE_NNUNET };
 struct DiceFinal {
   DiceKind kind;
   int sc = 1;                // first class of the Dice mean (0: background included)
-  double cw = 0.0, dw = 0.0; // CE weight; Dice weight (DICE_RUPP)
+  double cw = 0.0, dw = 0.0; // CE weight; Dice weight (all but DICE_SWIN / DICE_R2U)
+  const float* class_w = nullptr;  // DICE_UNET3D: [K] device floats, or null
+  const float* voxel_w = nullptr;  // DICE_UNET3D: [B vps] device floats, or null
 };
-size_t dice_ce_ws_bytes(int B, int K);
+size_t dice_ce_ws_bytes(int B, int K, DiceKind kind = DICE_SWIN);
 hipError_t soft_dice_loss(const DiceFinal& f, const float* logits, const int64_t* labels, int B,
                           int64_t vps, int K, int use_ignore, int ignore, float* out4,
                           float* dlogits, void* ws, hipStream_t s);

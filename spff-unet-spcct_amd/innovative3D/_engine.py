@@ -229,6 +229,13 @@ _SIGS = {
     "spff_rupp_loss_ws_bytes": (_S, [_I, _I]),
     "spff_rupp_loss": (_I, [_P, _P, _I, _L, _I, _I, _I, _I, ctypes.c_double, ctypes.c_double,
                             _P, _P, _P, _P]),
+    # the voxel-weighted 3DUNet loss and the nnU-Net Dice + CE loss
+    "spff_unet3d_loss_ws_bytes": (_S, [_I, _I]),
+    "spff_unet3d_loss": (_I, [_P, _P, _I, _L, _I, _I, _I, _P, _P, _I, ctypes.c_double,
+                              ctypes.c_double, _P, _P, _P, _P]),
+    "spff_nnunet_loss_ws_bytes": (_S, [_I, _I]),
+    "spff_nnunet_loss": (_I, [_P, _P, _I, _L, _I, _I, _I, _I, ctypes.c_double, ctypes.c_double,
+                              _P, _P, _P, _P]),
     "spff_conv3d_dil_ws_bytes": (_S, [_I, _I]),
     "spff_conv3d_dil_fwd": (_I, [_P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
     "spff_conv3d_dil_dgrad": (_I, [_P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
@@ -1288,6 +1295,42 @@ def rupp_loss_forward(logits_cl: torch.Tensor, labels: torch.Tensor, K: int,
     returns (out4 = [ce, loss, dice_mean, N_valid], dlogits_cl).  Dice sums are pooled over
     the whole batch; ``ignore_index`` None: no voxel is masked."""
     return _variant_loss("ResUNet++", "spff_rupp_loss", logits_cl, labels, K,
+                         *_ignore_args(ignore_index), int(bool(include_bg)), float(ce_weight),
+                         float(dice_weight))
+
+
+def unet3d_loss_forward(logits_cl: torch.Tensor, labels: torch.Tensor, K: int,
+                        ignore_index: Optional[int],
+                        class_weights: Optional[torch.Tensor] = None,
+                        voxel_weights: Optional[torch.Tensor] = None, include_bg: bool = False,
+                        ce_weight: float = 1.0, dice_weight: float = 0.0):
+    """The 3DUNet wrapper's _weighted_softmax_ce (per-class and per-voxel weights, denominator
+    max(sum m u, 1)) + dice_weight times its per-sample _dice_loss, on the HIP kernels: returns
+    (out4 = [ce, loss, dice_loss, sum m u], dlogits_cl).  ``voxel_weights``: one weight per
+    label, in the labels' order; ``ignore_index`` None: no voxel is masked."""
+    dev = logits_cl.device
+    cw = vw = None
+    if class_weights is not None:
+        cw = class_weights.to(device=dev, dtype=torch.float32).contiguous()
+        if cw.numel() != K:
+            raise SpffError(f"class_weights has {cw.numel()} entries, expected {K}")
+    if voxel_weights is not None:
+        vw = voxel_weights.to(device=dev, dtype=torch.float32).contiguous()
+        if vw.numel() != labels.numel():
+            raise SpffError(f"voxel_weights ({tuple(vw.shape)}) / labels "
+                            f"({tuple(labels.shape)}) mismatch")
+    return _variant_loss("3DUNet", "spff_unet3d_loss", logits_cl, labels, K,
+                         *_ignore_args(ignore_index), _ptr(cw), _ptr(vw), int(bool(include_bg)),
+                         float(ce_weight), float(dice_weight))
+
+
+def nnunet_loss_forward(logits_cl: torch.Tensor, labels: torch.Tensor, K: int,
+                        ignore_index: Optional[int] = -1, include_bg: bool = False,
+                        ce_weight: float = 1.0, dice_weight: float = 1.0):
+    """models.dice_ce_loss (nnU-Net style soft Dice with a squared-probability denominator,
+    pooled over the batch, + mean CE) on the HIP kernels: returns
+    (out4 = [ce, loss, dice_mean, N_valid], dlogits_cl)."""
+    return _variant_loss("nnU-Net Dice+CE", "spff_nnunet_loss", logits_cl, labels, K,
                          *_ignore_args(ignore_index), int(bool(include_bg)), float(ce_weight),
                          float(dice_weight))
 

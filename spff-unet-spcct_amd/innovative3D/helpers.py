@@ -12,8 +12,9 @@
   ``BaseLitModel._shared_step`` (models.py:510-584) -- the ranking part is the exact
   segmented sort + scan of csrc/rank.hip instead of scikit-learn on the host.
 
-Only ``ce_plus_macro_dice`` is on the SPFF path (config.LOSS_NAME is never read
-by it); the other LOSS_REGISTRY entries are out of scope and raise.
+``LOSS_REGISTRY``: ``ce_plus_macro_dice`` is the SPFF path's loss (config.LOSS_NAME is never
+read by it); ``dice_ce_nnunet`` is models.dice_ce_loss on the soft-Dice loss driver;
+``focal_plus_gradient`` raises, because the reference's own function cannot run.
 """
 from __future__ import annotations
 
@@ -28,7 +29,7 @@ from . import _engine as E
 __all__ = ["ce_plus_macro_dice_loss", "macro_dice_loss", "per_class_metrics_3d",
            "per_class_metrics_2d", "metrics_from_confusion", "ce_dice_with_confusion",
            "ce_dice_parts", "dice_loss_from_confusion_t", "ranking_metrics",
-           "iou_precision_from_confusion", "LOSS_REGISTRY"]
+           "iou_precision_from_confusion", "dice_ce_loss_adapter", "LOSS_REGISTRY"]
 
 
 def _logits_cl(logits: torch.Tensor) -> torch.Tensor:
@@ -275,18 +276,25 @@ def fast_simple_metrics() -> bool:
     return os.environ.get("FAST_SIMPLE_METRICS", "0").strip().lower() in ("1", "true", "yes", "on")
 
 
-def _out_of_scope(name):
-    def _f(*a, **k):
-        raise NotImplementedError(f"loss '{name}' is not on the SPFF hot path (config.LOSS_NAME is "
-                                  f"never read by it); only 'ce_plus_macro_dice' is implemented")
-    return _f
+def dice_ce_loss_adapter(logits, labels, num_classes, ignore_index):
+    """helpers.py:947-949: models.dice_ce_loss with its own weights and background setting."""
+    from .models import dice_ce_loss as _dice_ce
+    return _dice_ce(logits, labels, num_classes, ignore_index=ignore_index)
+
+
+def _focal_plus_gradient(*a, **k):
+    raise NotImplementedError(
+        "loss 'focal_plus_gradient': the reference's focal_plus_gradient_loss raises IndexError "
+        "in _spatial_grad_3d (its shift writes pad[2 * dim + 1] of a six-entry list with dim = "
+        "3, 4), so there is no behaviour to reproduce")
 
 
 LOSS_REGISTRY = {
     "ce_plus_macro_dice": lambda logits, labels, nc, ignore_index: ce_plus_macro_dice_loss(
         logits, labels, nc, ignore_index=ignore_index),
-    "focal_plus_gradient": _out_of_scope("focal_plus_gradient"),
-    "dice_ce_nnunet": _out_of_scope("dice_ce_nnunet"),
+    "focal_plus_gradient": _focal_plus_gradient,
+    "dice_ce_nnunet": lambda logits, labels, nc, ignore_index: dice_ce_loss_adapter(
+        logits, labels, nc, ignore_index),
 }
 
 

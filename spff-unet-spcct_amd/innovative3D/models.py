@@ -30,7 +30,7 @@ import torch.nn.functional as F
 
 from . import _engine as E
 from .config import BEST_LR, IGNORE_INDEX, NUM_CLASSES, NUM_FRAMES  # noqa: F401
-from .helpers import (LOSS_REGISTRY, _DeviceLoss, ce_plus_macro_dice_loss,  # noqa: F401
+from .helpers import (LOSS_REGISTRY, _DeviceLoss, _logits_cl, ce_plus_macro_dice_loss,  # noqa: F401
                       ce_dice_with_confusion, fast_simple_metrics, metrics_from_confusion,
                       per_class_metrics_2d, per_class_metrics_3d, ranking_metrics)
 from .lightning_compat import pl
@@ -99,6 +99,50 @@ def _center_crop_to_3d(x: torch.Tensor, orig_dhw):
 
 
 _center_crop_3d = _center_crop_to_3d
+
+
+# ------------------------------------------- nnU-Net style Dice + CE loss --
+class _NNUNetLoss(_DeviceLoss):
+    """(logits, labels, K, ignore_index, include_bg, ce_weight, dice_weight) ->
+    (loss, out4 = [ce, loss, dice_mean, N_valid]); only the loss carries a gradient."""
+
+    WHAT = "nnU-Net Dice+CE loss"
+
+    @staticmethod
+    def run(lcl, labels, *args):
+        out4, dl = E.nnunet_loss_forward(lcl, labels, *args)
+        return dl, out4[1].clone(), out4
+
+
+def _nnunet_loss(logits, labels, num_classes, ignore_index, include_background, ce_weight,
+                 dice_weight, eps=1e-5):
+    if eps != 1e-5:
+        raise NotImplementedError("the loss kernel's eps is 1e-5")
+    if logits.ndim != 5 or labels.ndim != 4:
+        raise ValueError(f"expected [B,K,D,H,W] logits and [B,D,H,W] labels, got "
+                         f"{tuple(logits.shape)} and {tuple(labels.shape)}")
+    if int(num_classes) != logits.shape[1]:
+        raise ValueError(f"num_classes {num_classes} != logits' {logits.shape[1]} channels")
+    return _NNUNetLoss.apply(logits, labels, int(num_classes), int(ignore_index),
+                             bool(include_background), float(ce_weight), float(dice_weight))[0]
+
+
+def soft_dice_loss_from_logits(logits: torch.Tensor, labels: torch.Tensor, num_classes: int,
+                               ignore_index: int = -1, include_background: bool = False,
+                               eps: float = 1e-5) -> torch.Tensor:
+    """models.py:254-275: 1 - mean_k (2 I_k + eps) / (sum m p_k^2 + sum m g_k + eps), the sums
+    pooled over the batch.  The HIP loss driver with ce_weight 0."""
+    return _nnunet_loss(logits, labels, num_classes, ignore_index, include_background, 0.0, 1.0,
+                        eps)
+
+
+def dice_ce_loss(logits: torch.Tensor, labels: torch.Tensor, num_classes: int,
+                 ignore_index: int = -1, ce_weight: float = 1.0, dice_weight: float = 1.0,
+                 include_background: bool = False) -> torch.Tensor:
+    """models.py:277-290: ce_weight * cross_entropy + dice_weight * soft_dice_loss_from_logits,
+    one call of the HIP loss driver."""
+    return _nnunet_loss(logits, labels, num_classes, ignore_index, include_background, ce_weight,
+                        dice_weight)
 
 
 def _norm3d(c: int, kind: str = "instance") -> nn.Module:
@@ -771,12 +815,27 @@ class _WeightedCE(_DeviceLoss):
         return dl, out4[0], conf
 
 
+class _UNet3DLoss(_DeviceLoss):
+    """(logits, labels, K, ignore_index, class_weights, voxel_weights, include_bg, ce_weight,
+    dice_weight) -> (loss, out4 = [ce, loss, dice_loss, sum m u]); only the loss carries a
+    gradient."""
+
+    WHAT = "3DUNet loss"
+
+    @staticmethod
+    def run(lcl, labels, *args):
+        out4, dl = E.unet3d_loss_forward(lcl, labels, *args)
+        return dl, out4[1].clone(), out4
+
+
 class LitCicek3DUNet_DepthAdapter_Published(pl.LightningModule):
     """models.py:756-853 (registry "3DUNet", config.py:283-311): depth adapter
     (resample D -> target_depth -> backbone -> back, fused into the engine),
     weighted softmax CE with ignore_index on the fused HIP loss kernel (class
     weights optional; denominator max(N_valid, 1)), macro-Dice logging from its
-    confusion counts, SGD(momentum) as configure_optimizers."""
+    confusion counts, SGD(momentum) as configure_optimizers.  Per-voxel CE weights
+    (``voxel_weight_key``) and the per-sample soft-Dice term (``dice_weight`` > 0) run as one
+    call of the soft-Dice loss driver (_UNet3DLoss)."""
 
     def __init__(self, num_classes: int, target_depth: int = 16,
                  lr: float = 1e-2, momentum: float = 0.99, nesterov: bool = False,
@@ -809,12 +868,35 @@ class LitCicek3DUNet_DepthAdapter_Published(pl.LightningModule):
     def forward(self, x):
         return self.backbone.run(_pick_first_if_seq(x), self.target_depth)
 
+    def _voxel_weights(self, voxel_weights, target):
+        """The weights in the labels' shape (a size-1 channel dimension squeezed), or None.
+        The reference would broadcast any other shape silently; here it is an error."""
+        if voxel_weights is None:
+            return None
+        vw = torch.as_tensor(voxel_weights)
+        if vw.ndim == target.ndim + 1 and vw.shape[1] == 1:
+            vw = vw[:, 0]
+        if vw.shape != target.shape:
+            raise ValueError(f"voxel weights {tuple(vw.shape)} do not match the labels "
+                             f"{tuple(target.shape)}")
+        return vw
+
+    def _device_loss(self, logits, target, voxel_weights, ce_weight, dice_weight):
+        """One call of the loss driver: (ce_weight ce + dice_weight dice_loss, out4)."""
+        if target.ndim == 5 and target.shape[1] == 1:
+            target = target[:, 0]
+        ign = None if self.ignore_index is None else int(self.ignore_index)
+        return _UNet3DLoss.apply(logits, target, int(self.hparams.num_classes), ign,
+                                 getattr(self, "class_weights", None),
+                                 self._voxel_weights(voxel_weights, target),
+                                 bool(self.include_bg_in_dice), float(ce_weight),
+                                 float(dice_weight))
+
     def _weighted_softmax_ce(self, logits, target, voxel_weights: Optional[torch.Tensor]):
         if target.ndim == 5 and target.shape[1] == 1:
             target = target[:, 0]
         if voxel_weights is not None:
-            raise NotImplementedError("per-voxel CE weights (voxel_weight_key) are off on the "
-                                      "registry path (config.py:297)")
+            return self._device_loss(logits, target, voxel_weights, 1.0, 0.0)[0]
         ign = self.ignore_index if self.ignore_index is not None else -1000
         loss, conf = _WeightedCE.apply(logits, target, int(self.hparams.num_classes), int(ign),
                                        getattr(self, "class_weights", None))
@@ -822,15 +904,22 @@ class LitCicek3DUNet_DepthAdapter_Published(pl.LightningModule):
         return loss
 
     def _dice_loss(self, logits, y, eps=1e-6):
-        raise NotImplementedError("the soft-Dice term (dice_weight > 0) is off on the registry "
-                                  "path (config.py:300: dice_weight=0.0)")
+        if eps != 1e-6:
+            raise NotImplementedError("the loss kernel's eps is 1e-6")
+        return self._device_loss(logits, y, None, 0.0, 1.0)[0]
 
     def _loss_and_log(self, logits, y, stage: str, voxel_w: Optional[torch.Tensor],
                       log_metrics: bool = True):
-        ce = self._weighted_softmax_ce(logits, y, voxel_w) * self.ce_weight
-        loss = ce
-        if self.dice_weight > 0.0:
-            loss = loss + self._dice_loss(logits, y) * self.dice_weight
+        K = int(self.hparams.num_classes)
+        if voxel_w is not None or self.dice_weight > 0.0:
+            # CE (class and voxel weights) and the soft-Dice term in one pass pair; the
+            # argmax counts of the metrics come from their own kernel
+            loss, _out4 = self._device_loss(logits, y, voxel_w, self.ce_weight,
+                                            max(self.dice_weight, 0.0))
+            conf = None
+        else:
+            loss = self._weighted_softmax_ce(logits, y, None) * self.ce_weight
+            conf = self._last_conf
         self.log(f"{stage}_loss", loss, prog_bar=(stage == "train"), on_step=False, on_epoch=True,
                  sync_dist=True)
         if log_metrics:
@@ -838,8 +927,10 @@ class LitCicek3DUNet_DepthAdapter_Published(pl.LightningModule):
             # loss kernel already produced (ignore_index None <-> the loss's -1000: no label
             # equals either, so the counts are the same)
             tgt = _canonicalize_targets_3d(y)
-            K = int(self.hparams.num_classes)
-            met = metrics_from_confusion(self._last_conf.cpu().numpy(), K, int(tgt.numel()))
+            if conf is None:
+                conf = E.confusion(_logits_cl(logits.detach()), tgt.to(logits.device), K,
+                                   self.ignore_index)
+            met = metrics_from_confusion(conf.cpu().numpy(), K, int(tgt.numel()))
             self.log(f"{stage}_macro_dice", met[3], on_step=False, on_epoch=True, prog_bar=True,
                      sync_dist=True)
         return loss
