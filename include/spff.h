@@ -284,6 +284,46 @@ size_t spff_rank_auc_ws_bytes(int batch, int64_t vox_per_sample, int num_classes
 int spff_rank_auc(const float* scores, const int64_t* labels, int batch, int64_t vox_per_sample,
                   int num_classes, int from_logits, int per_sample, double* out, void* ws,
                   void* stream);
+/* The qualitative views of the reference's figures (views.hip), formed where the logits
+ * lie instead of on the host after a copy.
+ * spff_pred_views: _prediction_views_and_mip (train.py:649-671, 933-951) for every sample
+ * of logits [B][D][H][W][K] channel-last fp32, K in 1..32.  Per voxel the reference's
+ * fp32 softmax (max-subtracted expf summed in class order, divided by sum + 1e-8f);
+ *   center_pred  uint8 [B][H][W]     argmax over the classes at depth D / 2, first maximum
+ *   alpha_center float [B][H][W]     that row's largest probability
+ *   mip_prob     float [B][H][W][K]  the maximum over depth of every class's probability
+ *   mip_pred     uint8 [B][H][W]     argmax over the classes of mip_prob, first maximum
+ *                                    (the reference's summary_pred and mip_pred)
+ * depth_split = 0: the depth is split over workgroups as the kernel sees fit; n in 1..D:
+ * over n ranges.  A maximum does not depend on grouping or order: every split, and every
+ * call, gives the same bits.  ws >= spff_pred_views_ws_bytes device bytes (0 for arguments
+ * that spff_pred_views rejects); it needs no clearing.  No allocation, no host
+ * synchronisation.  SPFF_EINVAL before any device call: a null pointer, K outside 1..32,
+ * an extent below 1, depth_split < 0 or > D. */
+size_t spff_pred_views_ws_bytes(int B, int D, int H, int W, int num_classes);
+int spff_pred_views(const float* logits, int B, int D, int H, int W, int num_classes,
+                    int depth_split, uint8_t* center_pred, float* alpha_center, float* mip_prob,
+                    uint8_t* mip_pred, void* ws, void* stream);
+/* The input's two grey images (_center_frame_from_input and _mip_from_input_tensor,
+ * train.py:616-634): x [B][C][D][H][W] fp32; center [B][H][W] = x[b][0][D / 2],
+ * mip [B][H][W] = the maximum over depth of x[b][0]; range [B][4] = (min, max) of center
+ * and (min, max) of mip, which imshow's grey scale needs. */
+int spff_input_views(const float* x, int B, int C, int D, int H, int W, float* center, float* mip,
+                     float* range, void* stream);
+/* The five panels of _render_buffer (train.py:1096-1111; test.py:581-744 draws the same)
+ * as one strip rgb uint8 [B][H][5 W][3], without titles and legend.  Grey value of an image:
+ * g = rint(255 (v - min) / (max - min)), 0 where max == min.  Panels: 0 the centre frame;
+ * 1 it under the ground-truth centre slice; 2 it under center_pred; 3 the MIP under
+ * mip_pred; 4 the centre frame under center_pred with confidence-weighted alpha.  A blended
+ * pixel is rint((1 - a) g + a colour[class]): a = 0.85 in panels 1..3 and
+ * 0.8 clamp(alpha_center, 0.35, 1) in panel 4.  colors: uint8 [256][3] on the device (a class
+ * without an entry is black: _color_mask, train.py:636-641).  labels_center: int64 [B][H][W],
+ * may be NULL (panel 1 is then the grey frame); a label of 255 or >= num_classes leaves the
+ * grey pixel.  center, mip, range: as spff_input_views writes them. */
+int spff_overlay_rgb(const float* center, const float* mip, const float* range,
+                     const int64_t* labels_center, const uint8_t* center_pred,
+                     const uint8_t* mip_pred, const float* alpha_center, const uint8_t* colors,
+                     int B, int H, int W, int num_classes, uint8_t* rgb, void* stream);
 /* x[i] *= *scale (scale is a device scalar) */
 int spff_scale(float* x, int64_t n, const float* scale, void* stream);
 

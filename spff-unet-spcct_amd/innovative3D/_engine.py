@@ -204,6 +204,10 @@ _SIGS = {
     "spff_count_valid": (_I, [_P, _L, _I, _P, _P]),
     "spff_rank_auc_ws_bytes": (_S, [_I, _L, _I, _I]),
     "spff_rank_auc": (_I, [_P, _P, _I, _L, _I, _I, _I, _P, _P, _P]),
+    "spff_pred_views_ws_bytes": (_S, [_I, _I, _I, _I, _I]),
+    "spff_pred_views": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
+    "spff_input_views": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
+    "spff_overlay_rgb": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P]),
     "spff_scale": (_I, [_P, _L, _P, _P]),
     "spff_conv3d_ws_bytes": (_S, [_I, _I, _I, _I, _I, _I, _I]),
     "spff_conv3d_fwd": (_I, [_P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
@@ -1370,6 +1374,87 @@ def rank_auc(scores_cl: torch.Tensor, labels: torch.Tensor, K: int, from_logits:
                           int(bool(per_sample)), _ptr(out), _ptr(ws), _stream(dev)),
           "spff_rank_auc")
     return out
+
+
+def pred_views_ws_bytes(B: int, D: int, H: int, W: int, K: int) -> int:
+    return int(lib().spff_pred_views_ws_bytes(B, D, H, W, K))
+
+
+def pred_views(logits_cl: torch.Tensor, depth_split: int = 0, ws: Optional[torch.Tensor] = None):
+    """spff_pred_views on channel-last logits [B, D, H, W, K]: (center_pred uint8 [B, H, W],
+    alpha_center float [B, H, W], mip_prob float [B, H, W, K], mip_pred uint8 [B, H, W]) on
+    the logits' device.  ``depth_split`` 0 leaves the split of the depth to the kernel;
+    ``ws`` is a uint8 device tensor of at least pred_views_ws_bytes (allocated when None).
+    No host sync."""
+    require_device(logits_cl, "pred_views")
+    if logits_cl.ndim != 5:
+        raise SpffError(f"pred_views: expected [B, D, H, W, K] logits, got {tuple(logits_cl.shape)}")
+    logits_cl = logits_cl.to(torch.float32).contiguous()
+    B, D, H, W, K = (int(v) for v in logits_cl.shape)
+    dev = logits_cl.device
+    L = lib()
+    need = int(L.spff_pred_views_ws_bytes(B, D, H, W, K))
+    if ws is None:
+        ws = torch.empty(max(1, need), dtype=torch.uint8, device=dev)
+    elif ws.device != dev or ws.dtype != torch.uint8 or not ws.is_contiguous() or ws.numel() < need:
+        raise SpffError(f"pred_views: ws must be a contiguous uint8 tensor of >= {need} bytes on {dev}")
+    center_pred = torch.empty((B, H, W), dtype=torch.uint8, device=dev)
+    alpha_center = torch.empty((B, H, W), dtype=torch.float32, device=dev)
+    mip_prob = torch.empty((B, H, W, K), dtype=torch.float32, device=dev)
+    mip_pred = torch.empty((B, H, W), dtype=torch.uint8, device=dev)
+    check(L.spff_pred_views(_ptr(logits_cl), B, D, H, W, K, int(depth_split), _ptr(center_pred),
+                            _ptr(alpha_center), _ptr(mip_prob), _ptr(mip_pred), _ptr(ws),
+                            _stream(dev)), "spff_pred_views")
+    return center_pred, alpha_center, mip_prob, mip_pred
+
+
+def input_views(x: torch.Tensor):
+    """spff_input_views on x [B, C, D, H, W]: (center [B, H, W] = x[:, 0, D // 2],
+    mip [B, H, W] = x[:, 0].amax(1), range [B, 4] = their (min, max) pairs).  No host sync."""
+    require_device(x, "input_views")
+    if x.ndim != 5:
+        raise SpffError(f"input_views: expected [B, C, D, H, W], got {tuple(x.shape)}")
+    x = x.to(torch.float32).contiguous()
+    B, C, D, H, W = (int(v) for v in x.shape)
+    center = torch.empty((B, H, W), dtype=torch.float32, device=x.device)
+    mip = torch.empty_like(center)
+    rng = torch.empty((B, 4), dtype=torch.float32, device=x.device)
+    check(lib().spff_input_views(_ptr(x), B, C, D, H, W, _ptr(center), _ptr(mip), _ptr(rng),
+                                 _stream(x.device)), "spff_input_views")
+    return center, mip, rng
+
+
+def overlay_rgb(center: torch.Tensor, mip: torch.Tensor, rng: torch.Tensor,
+                labels_center: Optional[torch.Tensor], center_pred: torch.Tensor,
+                mip_pred: torch.Tensor, alpha_center: torch.Tensor, colors: torch.Tensor,
+                K: int) -> torch.Tensor:
+    """spff_overlay_rgb: the five-panel strip uint8 [B, H, 5 W, 3] from what input_views and
+    pred_views return, the labels' centre slice [B, H, W] (or None) and a uint8 [256, 3]
+    colour table.  No host sync."""
+    require_device(center, "overlay_rgb")
+    dev = center.device
+    B, H, W = (int(v) for v in center.shape)
+
+    def dev_t(t, dtype, shape, what):
+        if tuple(t.shape) != shape:
+            raise SpffError(f"overlay_rgb: {what} is {tuple(t.shape)}, expected {shape}")
+        return t.to(device=dev, dtype=dtype).contiguous()
+
+    center = dev_t(center, torch.float32, (B, H, W), "center")
+    mip = dev_t(mip, torch.float32, (B, H, W), "mip")
+    rng = dev_t(rng, torch.float32, (B, 4), "range")
+    if labels_center is not None:
+        labels_center = dev_t(labels_center, torch.int64, (B, H, W), "labels_center")
+    center_pred = dev_t(center_pred, torch.uint8, (B, H, W), "center_pred")
+    mip_pred = dev_t(mip_pred, torch.uint8, (B, H, W), "mip_pred")
+    alpha_center = dev_t(alpha_center, torch.float32, (B, H, W), "alpha_center")
+    colors = dev_t(colors, torch.uint8, (256, 3), "colors")
+    rgb = torch.empty((B, H, 5 * W, 3), dtype=torch.uint8, device=dev)
+    check(lib().spff_overlay_rgb(_ptr(center), _ptr(mip), _ptr(rng), _ptr(labels_center),
+                                 _ptr(center_pred), _ptr(mip_pred), _ptr(alpha_center),
+                                 _ptr(colors), B, H, W, int(K), _ptr(rgb), _stream(dev)),
+          "spff_overlay_rgb")
+    return rgb
 
 
 def count_valid(labels: torch.Tensor, ignore_index: int) -> torch.Tensor:

@@ -11,6 +11,10 @@
 * ``ranking_metrics``: the test-only PR-AUC / ROC-AUC / IoU / precision block of
   ``BaseLitModel._shared_step`` (models.py:510-584) -- the ranking part is the exact
   segmented sort + scan of csrc/rank.hip instead of scikit-learn on the host.
+* ``prediction_views`` / ``render_overlays`` / ``write_png``: the qualitative figures of
+  train.py:649-671 and 1071-1119 -- class maps, confidence and the depth-wise maximum of
+  the softmax come from csrc/views.hip in one read of the logits; the five panels are
+  composed on the device and written as a PNG with zlib (no matplotlib).
 
 ``LOSS_REGISTRY``: ``ce_plus_macro_dice`` is the SPFF path's loss (config.LOSS_NAME is never
 read by it); ``dice_ce_nnunet`` is models.dice_ce_loss on the soft-Dice loss driver;
@@ -29,7 +33,9 @@ from . import _engine as E
 __all__ = ["ce_plus_macro_dice_loss", "macro_dice_loss", "per_class_metrics_3d",
            "per_class_metrics_2d", "metrics_from_confusion", "ce_dice_with_confusion",
            "ce_dice_parts", "dice_loss_from_confusion_t", "ranking_metrics",
-           "iou_precision_from_confusion", "dice_ce_loss_adapter", "LOSS_REGISTRY"]
+           "iou_precision_from_confusion", "dice_ce_loss_adapter", "LOSS_REGISTRY",
+           "prediction_views", "render_overlays", "write_png", "default_palette", "color_table",
+           "main_logits"]
 
 
 def _logits_cl(logits: torch.Tensor) -> torch.Tensor:
@@ -267,6 +273,121 @@ def ranking_metrics(logits, labels, num_classes, per_sample=False):
             "iou_macro": iou_ma, "precision_macro": prec_ma,
             "pr_auc_micro": float(auc[K, 0]), "roc_auc_micro": float(auc[K, 1]),
             "iou_micro": iou_mi, "precision_micro": prec_mi}
+
+
+def main_logits(out):
+    """The tensor a figure shows of whatever ``model(x)`` returns (train.py:1029-1051): the
+    tensor itself, a dict's ``"logits"``, or -- deep supervision -- the tensor of a tuple or
+    list with the largest spatial volume."""
+    if torch.is_tensor(out):
+        return out
+    if isinstance(out, dict) and torch.is_tensor(out.get("logits")):
+        return out["logits"]
+    if isinstance(out, (tuple, list)):
+        ts = [t for t in out if torch.is_tensor(t)]
+        if ts:
+            return max(ts, key=lambda t: int(np.prod(t.shape[2:])) if t.ndim >= 4 else 0)
+    raise TypeError(f"no logits tensor in a model output of type {type(out).__name__}")
+
+
+def prediction_views(logits):
+    """_prediction_views_and_mip (train.py:649-671) for every sample of logits [B, K, D, H, W],
+    or [B, K, H, W] (the reference's 2-D branch: D = 1, all three class maps are the centre
+    one), on the device (csrc/views.hip: one read of the logits, no copy to the host).
+    Returns ``center_pred, summary_pred, alpha_center, mip_pred`` in the reference's order:
+    uint8 class maps and the fp32 confidence, each [B, H, W]; ``summary_pred`` is
+    ``mip_pred``, as in the reference."""
+    E.require_device(logits, "prediction_views")
+    center_pred, alpha_center, _mip_prob, mip_pred = E.pred_views(_logits_cl(logits.detach()))
+    return center_pred, mip_pred, alpha_center, mip_pred
+
+
+def default_palette(num_classes: int) -> dict:
+    """{class: (r, g, b)} for classes 0 .. K-1: class 0 black, the others evenly spaced hues
+    at full saturation and value."""
+    import colorsys
+    K = int(num_classes)
+    pal = {0: (0, 0, 0)}
+    for c in range(1, K):
+        r, g, b = colorsys.hsv_to_rgb((c - 1) / max(1, K - 1), 1.0, 1.0)
+        pal[c] = (int(round(255 * r)), int(round(255 * g)), int(round(255 * b)))
+    return pal
+
+
+def color_table(colors, num_classes: int) -> torch.Tensor:
+    """uint8 [256, 3] (host) from a ``{class: (r, g, b)}`` dict, the shape config.label_colors
+    has; ``None``: default_palette.  A class without an entry stays black."""
+    colors = default_palette(num_classes) if colors is None else colors
+    tab = np.zeros((256, 3), dtype=np.uint8)
+    for c, col in colors.items():
+        if not 0 <= int(c) < 256 or len(col) != 3 or not all(0 <= int(v) <= 255 for v in col):
+            raise ValueError(f"colour table entry {c!r}: {col!r}")
+        tab[int(c)] = [int(v) for v in col]
+    return torch.from_numpy(tab)
+
+
+def render_overlays(x, labels, logits, colors=None, max_items=2):
+    """The five panels of the reference's overlay figure (train.py:1071-1119: original,
+    ground truth, centre prediction, prediction over the MIP, confidence-weighted overlay)
+    for the first ``max_items`` samples, as one uint8 strip [n, H, 5 W, 3] on the device.
+    x [B, C, D, H, W] (or [B, C, H, W]: the frame C // 2, train.py:620-622), labels
+    [B, D, H, W], [B, 1, D, H, W], [B, H, W] or None, logits whatever the model returned.
+    ``colors``: a ``{class: (r, g, b)}`` dict; None: default_palette."""
+    logits = main_logits(logits)
+    E.require_device(logits, "render_overlays")
+    n = max(1, min(int(max_items), int(logits.shape[0])))
+    lcl = _logits_cl(logits.detach()[:n])
+    _B, D, H, W, K = lcl.shape
+    x = x.detach()[:n].to(lcl.device)
+    if x.ndim == 4:
+        x = x[:, x.shape[1] // 2][:, None, None]
+    if x.ndim != 5 or tuple(x.shape[-2:]) != (H, W):
+        raise ValueError(f"input {tuple(x.shape)} does not match logits {tuple(logits.shape)}")
+    yc = None
+    if labels is not None:
+        y = labels.detach()[:n]
+        if y.ndim == 5 and y.shape[1] == 1:
+            y = y[:, 0]
+        if y.ndim == 4:
+            y = y[:, y.shape[1] // 2]
+        if y.ndim != 3 or tuple(y.shape[-2:]) != (H, W):
+            raise ValueError(f"labels {tuple(labels.shape)} do not match logits {tuple(logits.shape)}")
+        yc = y.to(lcl.device).long()
+    center_pred, alpha_center, _mip_prob, mip_pred = E.pred_views(lcl)
+    center, mip, rng = E.input_views(x)
+    tab = color_table(colors, K).to(lcl.device)
+    return E.overlay_rgb(center, mip, rng, yc, center_pred, mip_pred, alpha_center, tab, K)
+
+
+def write_png(path, rgb):
+    """An 8-bit RGB PNG of ``rgb`` (uint8 [H, W, 3], tensor or array) with zlib and struct
+    only; written under a temporary name and moved into place (train.py:894-900), so a
+    reader never sees half a file."""
+    import os
+    import pathlib
+    import struct
+    import zlib
+    if torch.is_tensor(rgb):
+        rgb = rgb.detach().cpu().numpy()
+    rgb = np.ascontiguousarray(rgb)
+    if rgb.dtype != np.uint8 or rgb.ndim != 3 or rgb.shape[2] != 3 or 0 in rgb.shape:
+        raise ValueError(f"write_png: expected uint8 [H, W, 3], got {rgb.dtype} {rgb.shape}")
+    h, w, _ = rgb.shape
+    raw = np.zeros((h, 1 + 3 * w), dtype=np.uint8)  # filter type 0 in front of every row
+    raw[:, 1:] = rgb.reshape(h, 3 * w)
+
+    def chunk(tag, data):
+        return (struct.pack(">I", len(data)) + tag + data +
+                struct.pack(">I", zlib.crc32(tag + data) & 0xFFFFFFFF))
+
+    png = (b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, 2, 0, 0, 0)) +
+           chunk(b"IDAT", zlib.compress(raw.tobytes(), 6)) + chunk(b"IEND", b""))
+    path = pathlib.Path(path)
+    path.parent.mkdir(parents=True, exist_ok=True)
+    tmp = path.with_name(path.name + ".part.png")
+    tmp.write_bytes(png)
+    os.replace(tmp, path)
+    return path
 
 
 def fast_simple_metrics() -> bool:

@@ -12,8 +12,12 @@ reference's test.py that touch the model (test.py:98-113 checkpoint lookup,
   aggregate mean +- std over seeds into analysis/per_class_summary.csv -- the
   table the reference turns into heatmaps.
 
-Plots (heatmaps, Bland-Altman, overlays) are host-side matplotlib analytics
-outside the engine's scope; every number they draw is in the CSVs written here.
+``--overlays N`` also draws the reference's qualitative overlays (test.py:581-744) for the
+first N test volumes of every evaluated checkpoint into
+<out>/overlays/<model>_seed<k>_case<i>.png: class maps, confidence and the softmax's
+depth-wise maximum are formed on the device (csrc/views.hip), the five panels too, and the
+PNG is written with zlib.  The other plots (heatmaps, Bland-Altman, violins, montages) are
+host-side matplotlib drawings of numbers that are all in the CSVs written here.
 """
 from __future__ import annotations
 
@@ -110,9 +114,26 @@ def evaluate(model, dataset, K, device):
     return rows
 
 
+def write_case_overlays(model, dataset, n, out_dir, stem, device):
+    """<out_dir>/<stem>_case<i>.png for the first ``n`` volumes: one forward each, then
+    helpers.render_overlays."""
+    paths = []
+    model.eval()
+    with torch.no_grad():
+        for i in range(min(int(n), len(dataset))):
+            x, y = dataset[i]
+            x, y = x[None].to(device), y[None].to(device)
+            strip = Hh.render_overlays(x, y, model(x), colors=getattr(C, "label_colors", None),
+                                       max_items=1)
+            paths.append(Hh.write_png(out_dir / f"{stem}_case{i}.png", strip[0]))
+    return paths
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default="analysis")
+    ap.add_argument("--overlays", type=int, default=0, metavar="N",
+                    help="draw the overlay figure of the first N test volumes per checkpoint")
     args = ap.parse_args(argv)
     S = Settings()
     device = torch.device("cuda", torch.cuda.current_device())
@@ -134,6 +155,9 @@ def main(argv=None):
             ds = SyntheticSPCCT(n=S.n_test, in_ch=S.in_ch, depth=S.depth, height=S.height,
                                 width=S.width, num_classes=K, seed=seed + 20_000)
             rows = evaluate(model, ds, K, device)
+            if args.overlays > 0:
+                write_case_overlays(model, ds, args.overlays, out / "overlays",
+                                    f"{name}_seed{seed}", device)
             det = ck.parent / "test_details.csv"
             with open(det, "w", newline="") as f:
                 w = csv.DictWriter(f, fieldnames=detail_fields())

@@ -21,7 +21,13 @@ Environment (defaults = the registry's constants, config.py): CHECKPOINT_DIR,
 SEEDS ("42,123,999"), MAX_EPOCHS, BATCH_SIZE, NUM_FRAMES (depth), IMAGE_HEIGHT,
 IMAGE_WIDTH, IN_CHANNELS (1 = registry layout, 5 = north-star layout),
 N_TRAIN / N_VAL / N_TEST (synthetic volumes), FAST_TEST / --fast (one short
-epoch of FAST_TEST_LIMIT batches), SPFF_MATH (conv arithmetic).
+epoch of FAST_TEST_LIMIT batches), SPFF_MATH (conv arithmetic),
+VIZ_EVERY_N_EPOCHS (default 0 = off; the reference's callback is on by default) and
+VIZ_MAX_ITEMS (2): every N epochs the first training and the first validation batch of
+the epoch are drawn as the reference's five-panel overlays (VisualizeEveryNEpochsBuffered,
+train.py:881-1165) into <run dir>/viz/{phase}_epoch{e:03d}/overlay_b{b}.png -- views and
+panels are formed on the device (csrc/views.hip), the PNG is written with zlib.
+FAST_SKIP_VIZ=1 turns them off, as in the reference.
 """
 from __future__ import annotations
 
@@ -41,6 +47,7 @@ import torch  # noqa: E402
 
 from innovative3D import _engine as E  # noqa: E402
 from innovative3D import config as C  # noqa: E402
+from innovative3D import helpers as Hh  # noqa: E402
 from innovative3D.lightning_compat import pl  # noqa: E402
 from innovative3D.synthetic import SyntheticSPCCT  # noqa: E402
 
@@ -78,6 +85,8 @@ class Settings:
         self.fast = _env_flag("FAST_TEST")
         self.fast_limit = _env_int("FAST_TEST_LIMIT", 2)
         self.patience = _env_int("EARLY_STOP_PATIENCE", 12)
+        self.viz_every = 0 if _env_flag("FAST_SKIP_VIZ") else max(0, _env_int("VIZ_EVERY_N_EPOCHS", 0))
+        self.viz_max_items = max(1, _env_int("VIZ_MAX_ITEMS", 2))
 
 
 def _build_lit(builder, in_ch):
@@ -99,14 +108,17 @@ def _scalar(v):
     return float(v.detach().float().mean()) if torch.is_tensor(v) else float(v)
 
 
-def _run_epoch(model, loader, step_fn, limit, device, opt=None):
-    """One pass; returns the batch-size-weighted mean of every logged metric."""
+def _run_epoch(model, loader, step_fn, limit, device, opt=None, keep=None):
+    """One pass; returns the batch-size-weighted mean of every logged metric.  ``keep``
+    (a list) receives the first batch, on the device."""
     sums, n = {}, 0
     model.train(opt is not None)
     for i, (x, y) in enumerate(loader):
         if limit and i >= limit:
             break
         x, y = x.to(device, non_blocking=True), y.to(device, non_blocking=True)
+        if keep is not None and i == 0:
+            keep.append((x, y))
         model.logged_metrics = {}
         if opt is not None:
             opt.zero_grad(set_to_none=True)
@@ -129,6 +141,28 @@ def _run_epoch(model, loader, step_fn, limit, device, opt=None):
 def _save_ckpt(path, model, epoch, metrics):
     torch.save({"state_dict": {k: v.detach().cpu() for k, v in model.state_dict().items()},
                 "epoch": epoch, "metrics": metrics}, path)
+
+
+def _is_rank0():
+    dist = torch.distributed
+    return not (dist.is_available() and dist.is_initialized()) or dist.get_rank() == 0
+
+
+def write_overlays(model, batch, out_dir, max_items=2, colors=None):
+    """VisualizeEveryNEpochsBuffered._stash + _render_buffer (train.py:1001-1119) for one
+    kept batch: the module runs under no_grad in eval mode (its mode is restored), whatever
+    it returns goes to helpers.render_overlays, one overlay_b{b}.png per sample."""
+    x, y = batch
+    was_training = model.training
+    model.eval()
+    try:
+        with torch.no_grad():
+            strips = Hh.render_overlays(x, y, model(x), colors=colors, max_items=max_items)
+    finally:
+        model.train(was_training)
+    strips = strips.cpu()
+    return [Hh.write_png(pathlib.Path(out_dir) / f"overlay_b{b}.png", strips[b])
+            for b in range(strips.shape[0])]
 
 
 def train_and_log(model_name, builder, seed, S: Settings, datasets=None):
@@ -160,8 +194,14 @@ def train_and_log(model_name, builder, seed, S: Settings, datasets=None):
     rows = []
     for epoch in range(epochs):
         t0 = time.perf_counter()
-        trm = _run_epoch(model, tr, model.training_step, limit, device, opt)
-        vam = _run_epoch(model, va, model.validation_step, limit, device)
+        viz = S.viz_every > 0 and (epoch + 1) % S.viz_every == 0 and _is_rank0()
+        kept = {"train": [], "val": []} if viz else {}
+        trm = _run_epoch(model, tr, model.training_step, limit, device, opt, kept.get("train"))
+        vam = _run_epoch(model, va, model.validation_step, limit, device, keep=kept.get("val"))
+        for phase, batches in kept.items():
+            if batches:
+                write_overlays(model, batches[0], folder / "viz" / f"{phase}_epoch{epoch + 1:03d}",
+                               S.viz_max_items, getattr(C, "label_colors", None))
         score = vam.get(monitor, float("nan"))
         if sch is not None and not math.isnan(score):
             sch.step(score)
