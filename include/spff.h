@@ -324,6 +324,46 @@ int spff_overlay_rgb(const float* center, const float* mip, const float* range,
                      const int64_t* labels_center, const uint8_t* center_pred,
                      const uint8_t* mip_pred, const float* alpha_center, const uint8_t* colors,
                      int B, int H, int W, int num_classes, uint8_t* rgb, void* stream);
+/* Sliding-window inference (tile.hip): the network runs on overlapping windows
+ * [rd][rh][rw] of one volume and the window outputs are blended with a separable
+ * window-centred weight.  windows: a HOST array [n][4] = z0, y0, x0, flip bits (1 = D,
+ * 2 = H, 4 = W), n in 1..SPFF_TILE_MAX_WINDOWS; it travels to the kernels by value and is
+ * validated first.  A flipped window is gathered mirrored along its axes and accumulated
+ * mirrored back.
+ *   gather      out [n][C][rd][rh][rw] = the windows of x [C][D][H][W].
+ *   accumulate  acc[v][k] += (wz wy wx)(v) s[v][k] over the n windows in table order, fp32
+ *               fmaf; s is the tile value or (softmax = 1) the fp32 softmax of the tile's row
+ *               (max-subtracted expf summed in class order, a true division).  Windows of
+ *               one call may overlap; a voxel's sum does not depend on how the table is
+ *               split into calls.  tiles may hold more than n windows: the rest is not read.
+ *   finalize    mask = the first maximum of each acc row (the rule of the confusion counts: a
+ *               NaN counts as the largest); with labels, conf = K (K + 1) int64 counts as the
+ *               confusion entry gives for the same rows, zeroed on the stream by a kernel;
+ *               scores (may be NULL, may be acc itself) = acc / (flips nz[z] ny[y] nx[x]).
+ * Stream-ordered, no allocation, no host synchronisation; a captured graph replays them.
+ * Before any device call: SPFF_EINVAL for K outside 2..32, n outside 1..64, a null required
+ * pointer, an extent below 1, flip bits outside 0..7, conf NULL without labels NULL or the
+ * reverse; SPFF_ESHAPE for a window extent above the volume's or a window not wholly inside
+ * the volume. */
+#define SPFF_TILE_MAX_WINDOWS 64
+int spff_tile_gather(const float* x, int C, int D, int H, int W, /* one volume [C][D][H][W] */
+                     const int32_t* windows, int n, int rd, int rh, int rw,
+                     float* out, /* [n][C][rd][rh][rw] */
+                     void* stream);
+int spff_tile_accumulate(const float* tiles, /* [n][rd][rh][rw][K] channel-last */
+                         const int32_t* windows, int n, int rd, int rh, int rw, int K,
+                         int D, int H, int W,
+                         const float* wz, const float* wy, const float* wx, /* device [rd], [rh], [rw] */
+                         int softmax,
+                         float* acc, /* [D][H][W][K], zeroed by the caller */
+                         void* stream);
+int spff_tile_finalize(const float* acc, int D, int H, int W, int K,
+                       const float* nz, const float* ny, const float* nx, float flips, /* scores only */
+                       uint8_t* mask,  /* [D][H][W] */
+                       float* scores,  /* [D][H][W][K] or NULL */
+                       const int64_t* labels, int use_ignore, int ignore_index,
+                       int64_t* conf,  /* K*(K+1); NULL iff labels NULL */
+                       void* stream);
 /* x[i] *= *scale (scale is a device scalar) */
 int spff_scale(float* x, int64_t n, const float* scale, void* stream);
 

@@ -208,6 +208,10 @@ _SIGS = {
     "spff_pred_views": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
     "spff_input_views": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
     "spff_overlay_rgb": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P]),
+    "spff_tile_gather": (_I, [_P, _I, _I, _I, _I, _P, _I, _I, _I, _I, _P, _P]),
+    "spff_tile_accumulate": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P]),
+    "spff_tile_finalize": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, ctypes.c_float, _P, _P, _P, _I,
+                                _I, _P, _P]),
     "spff_scale": (_I, [_P, _L, _P, _P]),
     "spff_conv3d_ws_bytes": (_S, [_I, _I, _I, _I, _I, _I, _I]),
     "spff_conv3d_fwd": (_I, [_P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
@@ -1455,6 +1459,113 @@ def overlay_rgb(center: torch.Tensor, mip: torch.Tensor, rng: torch.Tensor,
                                  _ptr(colors), B, H, W, int(K), _ptr(rgb), _stream(dev)),
           "spff_overlay_rgb")
     return rgb
+
+
+def _tile_table(what: str, windows, n: Optional[int]):
+    """The HOST window table [n][4] (z0, y0, x0, flip bits) as a C int32 array: its first
+    ``n`` rows (None: all).  -> (array, n)"""
+    rows = [[int(v) for v in row] for row in windows]
+    n = len(rows) if n is None else int(n)
+    if not 1 <= n <= len(rows) or any(len(r) != 4 for r in rows):
+        raise SpffError(f"{what}: expected a window table [n][4] and 1 <= n <= {len(rows)}")
+    return (ctypes.c_int32 * (4 * n))(*[v for r in rows[:n] for v in r]), n
+
+
+def _tile_dev(what: str, t: torch.Tensor, name: str, dev, shape, dtype=torch.float32):
+    if t.device != dev or t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise SpffError(f"{what}: {name} must be a contiguous {dtype} tensor {tuple(shape)} on "
+                        f"{dev}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+    return t
+
+
+def tile_gather(x: torch.Tensor, windows, roi, out: Optional[torch.Tensor] = None,
+                n: Optional[int] = None) -> torch.Tensor:
+    """spff_tile_gather: the first ``n`` windows of the table (None: all) of one volume x
+    [C, D, H, W] into out[:n] of out [m >= n, C, rd, rh, rw] (allocated [n, ...] when None);
+    a window with flip bits is gathered mirrored.  No host sync."""
+    require_device(x, "tile_gather")
+    if x.ndim != 4 or x.dtype != torch.float32 or not x.is_contiguous():
+        raise SpffError(f"tile_gather: expected a contiguous fp32 volume [C, D, H, W], got "
+                        f"{x.dtype} {tuple(x.shape)}")
+    tab, n = _tile_table("tile_gather", windows, n)
+    C, D, H, W = (int(v) for v in x.shape)
+    rd, rh, rw = (int(v) for v in roi)
+    if out is None:
+        out = torch.empty((n, C, rd, rh, rw), dtype=torch.float32, device=x.device)
+    elif out.ndim != 5 or out.shape[0] < n:
+        raise SpffError(f"tile_gather: out {tuple(out.shape)} holds fewer than {n} windows")
+    _tile_dev("tile_gather", out, "out", x.device, (out.shape[0], C, rd, rh, rw))
+    check(lib().spff_tile_gather(_ptr(x), C, D, H, W, tab, n, rd, rh, rw, _ptr(out),
+                                 _stream(x.device)), "spff_tile_gather")
+    return out
+
+
+def tile_accumulate(tiles_cl: torch.Tensor, windows, weights, acc: torch.Tensor,
+                    softmax: bool = False, n: Optional[int] = None) -> torch.Tensor:
+    """spff_tile_accumulate: acc [D, H, W, K] += w s over the first ``n`` windows of the table
+    (None: all), in table order; tiles_cl [m >= n, rd, rh, rw, K] channel-last window outputs,
+    ``weights`` = (wz [rd], wy [rh], wx [rw]) fp32 device tensors; ``softmax``: s is the fp32
+    softmax of the tile's row instead of its value.  In place; no host sync."""
+    require_device(acc, "tile_accumulate")
+    tab, n = _tile_table("tile_accumulate", windows, n)
+    if acc.ndim != 4 or tiles_cl.ndim != 5 or tiles_cl.shape[0] < n:
+        raise SpffError(f"tile_accumulate: acc {tuple(acc.shape)} / tiles {tuple(tiles_cl.shape)} "
+                        f"for {n} windows")
+    dev = acc.device
+    D, H, W, K = (int(v) for v in acc.shape)
+    m, rd, rh, rw = (int(v) for v in tiles_cl.shape[:4])
+    _tile_dev("tile_accumulate", acc, "acc", dev, (D, H, W, K))
+    _tile_dev("tile_accumulate", tiles_cl, "tiles", dev, (m, rd, rh, rw, K))
+    wz, wy, wx = (_tile_dev("tile_accumulate", w, nm, dev, (r,))
+                  for w, nm, r in zip(weights, ("wz", "wy", "wx"), (rd, rh, rw)))
+    check(lib().spff_tile_accumulate(_ptr(tiles_cl), tab, n, rd, rh, rw, K, D, H, W, _ptr(wz),
+                                     _ptr(wy), _ptr(wx), int(bool(softmax)), _ptr(acc),
+                                     _stream(dev)), "spff_tile_accumulate")
+    return acc
+
+
+def tile_finalize(acc: torch.Tensor, norms=None, flips: int = 1,
+                  labels: Optional[torch.Tensor] = None, ignore_index: Optional[int] = None,
+                  scores=False, mask: Optional[torch.Tensor] = None,
+                  conf: Optional[torch.Tensor] = None):
+    """spff_tile_finalize on acc [D, H, W, K]: (mask uint8 [D, H, W] = the first maximum of
+    every row, conf int64 [K, K + 1] as confusion() of the same rows or None without
+    ``labels`` [D, H, W], scores or None).  ``scores``: False, True (a new tensor), or the
+    tensor to write -- acc itself is allowed; scores = acc / (flips nz[z] ny[y] nx[x]) with
+    ``norms`` = (nz [D], ny [H], nx [W]) fp32 device tensors.  ``mask`` / ``conf``: the
+    tensors to write (allocated when None).  No host sync."""
+    require_device(acc, "tile_finalize")
+    if acc.ndim != 4:
+        raise SpffError(f"tile_finalize: expected acc [D, H, W, K], got {tuple(acc.shape)}")
+    dev = acc.device
+    D, H, W, K = (int(v) for v in acc.shape)
+    _tile_dev("tile_finalize", acc, "acc", dev, (D, H, W, K))
+    if mask is None:
+        mask = torch.empty((D, H, W), dtype=torch.uint8, device=dev)
+    _tile_dev("tile_finalize", mask, "mask", dev, (D, H, W), torch.uint8)
+    out_scores, nz, ny, nx = None, None, None, None
+    if scores is not False and scores is not None:
+        if norms is None:
+            raise SpffError("tile_finalize: scores need the norm vectors")
+        nz, ny, nx = (_tile_dev("tile_finalize", v, nm, dev, (r,))
+                      for v, nm, r in zip(norms, ("nz", "ny", "nx"), (D, H, W)))
+        out_scores = torch.empty_like(acc) if scores is True else scores
+        _tile_dev("tile_finalize", out_scores, "scores", dev, (D, H, W, K))
+    if labels is not None:
+        labels = labels.to(device=dev, dtype=torch.int64).contiguous()
+        if labels.numel() != D * H * W:
+            raise SpffError(f"tile_finalize: labels {tuple(labels.shape)} do not match the "
+                            f"volume {(D, H, W)}")
+        if conf is None:
+            conf = torch.empty(K * (K + 1), dtype=torch.int64, device=dev)
+        _tile_dev("tile_finalize", conf, "conf", dev, (K * (K + 1),), torch.int64)
+    else:
+        conf = None
+    check(lib().spff_tile_finalize(_ptr(acc), D, H, W, K, _ptr(nz), _ptr(ny), _ptr(nx),
+                                   float(flips), _ptr(mask), _ptr(out_scores), _ptr(labels),
+                                   *_ignore_args(ignore_index), _ptr(conf), _stream(dev)),
+          "spff_tile_finalize")
+    return mask, None if conf is None else conf.view(K, K + 1), out_scores
 
 
 def count_valid(labels: torch.Tensor, ignore_index: int) -> torch.Tensor:

@@ -15,6 +15,9 @@
   train.py:649-671 and 1071-1119 -- class maps, confidence and the depth-wise maximum of
   the softmax come from csrc/views.hip in one read of the logits; the five panels are
   composed on the device and written as a PNG with zlib (no matplotlib).
+* ``predict_tiled``: sliding-window inference with Gaussian blending for any module that
+  returns [B, K, D, H, W] logits -- window gather, blend, class map and counts are the
+  kernels of csrc/tile.hip; the window geometry is innovative3D/tiling.py.
 
 ``LOSS_REGISTRY``: ``ce_plus_macro_dice`` is the SPFF path's loss (config.LOSS_NAME is never
 read by it); ``dice_ce_nnunet`` is models.dice_ce_loss on the soft-Dice loss driver;
@@ -35,7 +38,7 @@ __all__ = ["ce_plus_macro_dice_loss", "macro_dice_loss", "per_class_metrics_3d",
            "ce_dice_parts", "dice_loss_from_confusion_t", "ranking_metrics",
            "iou_precision_from_confusion", "dice_ce_loss_adapter", "LOSS_REGISTRY",
            "prediction_views", "render_overlays", "write_png", "default_palette", "color_table",
-           "main_logits"]
+           "main_logits", "predict_tiled"]
 
 
 def _logits_cl(logits: torch.Tensor) -> torch.Tensor:
@@ -288,6 +291,92 @@ def main_logits(out):
         if ts:
             return max(ts, key=lambda t: int(np.prod(t.shape[2:])) if t.ndim >= 4 else 0)
     raise TypeError(f"no logits tensor in a model output of type {type(out).__name__}")
+
+
+@torch.no_grad()
+def predict_tiled(model, x, roi, overlap=0.5, blend="gaussian", sigma_scale=0.125,
+                  blend_of="logits", window_batch=1, mirror_axes=(), labels=None,
+                  ignore_index=None, return_scores=False, *, forward_cl=None):
+    """Sliding-window inference: ``model`` runs on overlapping windows of
+    ``roi`` = (D, H, W) voxels (clamped to the volume) of x [B, C, D, H, W], ``window_batch``
+    windows per forward, and the window outputs -- the logits, or with ``blend_of="probs"``
+    their fp32 softmax -- are blended on the device (csrc/tile.hip) with a window-centred
+    ``gaussian`` or a ``constant`` weight; ``mirror_axes``, a subset of (0, 1, 2) = (D, H, W),
+    adds one pass over all windows per subset of mirrored axes.  Volumes are processed one
+    after another.  Returns like ``predict``: the class mask uint8 [B, D, H, W] (the first
+    maximum of the blend), then with ``labels`` [B, D, H, W] the [K, K + 1] int64 confusion
+    counts summed over the batch (``ignore_index`` None: no voxel masked), then with
+    ``return_scores`` the normalised blend [B, K, D, H, W].
+
+    ``model(x)`` must return [B, K, D, H, W] logits (or what main_logits finds them in).
+    One staging tensor and one window-output buffer serve every window; a partial last batch
+    repeats its last window in the unused slots, which the blend leaves out.
+    ``forward_cl(stage, out)``: the engine modules' own forward, channel-last into ``out``."""
+    from . import tiling as T
+    E.require_device(x, "predict_tiled")
+    if x.ndim != 5:
+        raise ValueError(f"predict_tiled: expected x [B, C, D, H, W], got {tuple(x.shape)}")
+    if blend_of not in ("logits", "probs"):
+        raise ValueError(f"blend_of={blend_of!r}: expected 'logits' or 'probs'")
+    x = x.detach().float()
+    dev = x.device
+    B, C, D, H, W = (int(v) for v in x.shape)
+    r = T.clamp_roi((D, H, W), roi)
+    table = T.window_table((D, H, W), r, overlap, mirror_axes)
+    wb = int(window_batch)
+    spans = T.batches(len(table), wb)
+    weights = tuple(torch.from_numpy(T.axis_weights(ri, blend, sigma_scale)).to(dev) for ri in r)
+    norms = None
+    if return_scores:
+        norms = tuple(torch.from_numpy(v).to(dev)
+                      for v in T.norm_vectors((D, H, W), r, overlap, blend, sigma_scale))
+    if labels is not None:
+        labels = labels.detach().to(dev)
+        if labels.ndim == 5 and labels.shape[1] == 1:
+            labels = labels[:, 0]
+        if tuple(labels.shape) != (B, D, H, W):
+            raise ValueError(f"predict_tiled: labels {tuple(labels.shape)} do not match the "
+                             f"volumes {(B, D, H, W)}")
+    stage = torch.empty((wb, C) + r, dtype=torch.float32, device=dev)
+    mask = torch.empty((B, D, H, W), dtype=torch.uint8, device=dev)
+    tiles = acc = scores = conf = None
+    for b in range(B):
+        vol = x[b].contiguous()
+        if acc is not None:
+            acc.zero_()
+        for i0, i1 in spans:
+            rows = table[i0:i1]
+            if i1 - i0 < wb:  # the partial last batch: same plan, the last window repeated
+                rows = np.concatenate([rows, np.repeat(rows[-1:], wb - (i1 - i0), axis=0)])
+            E.tile_gather(vol, rows, r, out=stage)
+            if forward_cl is not None:
+                tiles = forward_cl(stage, tiles)
+            else:
+                lg = main_logits(model(stage))
+                if lg.ndim != 5 or tuple(lg.shape[2:]) != r or lg.shape[0] != wb:
+                    raise ValueError(f"predict_tiled: the model returned {tuple(lg.shape)} for "
+                                     f"windows {tuple(stage.shape)}")
+                if tiles is None:
+                    tiles = torch.empty((wb,) + r + (int(lg.shape[1]),), dtype=torch.float32,
+                                        device=dev)
+                tiles.copy_(lg.detach().permute(0, 2, 3, 4, 1))
+            if acc is None:
+                K = int(tiles.shape[-1])
+                acc = torch.zeros((D, H, W, K), dtype=torch.float32, device=dev)
+                if return_scores:
+                    scores = torch.empty((B, D, H, W, K), dtype=torch.float32, device=dev)
+            E.tile_accumulate(tiles, table[i0:i1], weights, acc, softmax=blend_of == "probs")
+        _m, cf, _s = E.tile_finalize(acc, norms, len(T.flip_passes(mirror_axes)),
+                                     None if labels is None else labels[b], ignore_index,
+                                     scores=scores[b] if return_scores else False, mask=mask[b])
+        if cf is not None:
+            conf = cf if conf is None else conf + cf
+    out = (mask,)
+    if labels is not None:
+        out += (conf,)
+    if return_scores:
+        out += (scores.permute(0, 4, 1, 2, 3),)
+    return out[0] if len(out) == 1 else out
 
 
 def prediction_views(logits):

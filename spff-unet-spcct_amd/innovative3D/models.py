@@ -33,6 +33,7 @@ from .config import BEST_LR, IGNORE_INDEX, NUM_CLASSES, NUM_FRAMES  # noqa: F401
 from .helpers import (LOSS_REGISTRY, _DeviceLoss, _logits_cl, ce_plus_macro_dice_loss,  # noqa: F401
                       ce_dice_with_confusion, fast_simple_metrics, metrics_from_confusion,
                       per_class_metrics_2d, per_class_metrics_3d, ranking_metrics)
+from .helpers import predict_tiled as _predict_tiled
 from .lightning_compat import pl
 
 # ----------------------------------------------------------------- utilities --
@@ -504,6 +505,29 @@ class UNet3D_SpectralCore(_FlatParamMixin, nn.Module):
             out += (logits_cl.permute(0, 4, 1, 2, 3),)
         return out[0] if len(out) == 1 else out
 
+    @torch.no_grad()
+    def predict_tiled(self, x, roi, overlap=0.5, blend="gaussian", sigma_scale=0.125,
+                      blend_of="logits", window_batch=1, mirror_axes=(), labels=None,
+                      ignore_index=None, return_scores=False):
+        """helpers.predict_tiled with the windows on ONE forward-only plan (memory "infer")
+        of shape [window_batch, C, roi], its logits written channel-last into one buffer.
+        Whatever the forward refuses for the window shape is refused here the same way."""
+        x = _pick_first_if_seq(x)
+        E.require_device(x, "UNet3D_SpectralCore.predict_tiled")
+        held = []
+
+        def forward_cl(stage, out):
+            if not held:
+                plan = self._engine_plan(stage, "infer", memory="infer")
+                held.extend((plan, self._ensure_flat(plan, self._engine_params(plan),
+                                                     stage.device)))
+                self._infer_plan = plan
+            return held[0].forward(stage, held[1], out=out)
+        return _predict_tiled(self, x, roi, overlap=overlap, blend=blend, sigma_scale=sigma_scale,
+                              blend_of=blend_of, window_batch=window_batch,
+                              mirror_axes=mirror_axes, labels=labels, ignore_index=ignore_index,
+                              return_scores=return_scores, forward_cl=forward_cl)
+
 
 def upgrade_spct_with_novel_blocks(m: nn.Module, use_efilm: bool = True, use_fouriergate: bool = True,
                                    use_moe: bool = False, moe_K: int = 3):
@@ -557,6 +581,11 @@ class BaseLitModel(pl.LightningModule):
         """The core's predict (UNet3D_SpectralCore.predict) after forward's input handling"""
         return self.model.predict(self._normalize_input(x), labels=labels,
                                   ignore_index=ignore_index, return_logits=return_logits)
+
+    def predict_tiled(self, x, roi, **kw):
+        """The core's predict_tiled (UNet3D_SpectralCore.predict_tiled, same keywords) after
+        forward's input handling"""
+        return self.model.predict_tiled(self._normalize_input(x), roi, **kw)
 
     def compute_loss(self, logits, labels):
         return ce_plus_macro_dice_loss(logits, labels, self.hparams.num_classes, ignore_index=IGNORE_INDEX)
@@ -644,6 +673,11 @@ class _LitSPCT_Base(BaseLitModel):
     def predict(self, x, labels=None, ignore_index=None, return_logits=False):
         raise NotImplementedError("predict: the padded forward of this wrapper crops its logits; "
                                   "the fused head would count the padding's voxels")
+
+    def predict_tiled(self, x, roi, **kw):
+        raise NotImplementedError("predict_tiled: the padded forward of this wrapper crops its "
+                                  "logits; use helpers.predict_tiled(model, x, roi, ...), which "
+                                  "runs the windows through forward")
 
 
 class LitSPCT_EFiLM_FourierGate(BaseLitModel):

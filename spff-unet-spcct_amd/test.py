@@ -18,6 +18,11 @@ first N test volumes of every evaluated checkpoint into
 depth-wise maximum are formed on the device (csrc/views.hip), the five panels too, and the
 PNG is written with zlib.  The other plots (heatmaps, Bland-Altman, violins, montages) are
 host-side matplotlib drawings of numbers that are all in the CSVs written here.
+
+``--roi D H W`` evaluates every variant by sliding-window inference (helpers.predict_tiled):
+the network runs on overlapping windows of that size (``--overlap``, ``--window-batch`` per
+forward, ``--mirror AXES`` for test-time mirroring), the window logits are blended with a
+Gaussian weight on the device (csrc/tile.hip), and the metrics come from the blend.
 """
 from __future__ import annotations
 
@@ -86,7 +91,18 @@ def detail_fields():
     return DETAIL_FIELDS + ([] if Hh.fast_simple_metrics() else RANK_FIELDS)
 
 
-def evaluate(model, dataset, K, device):
+def predict_tiled(model, x, tiled, **kw):
+    """Sliding-window inference of ``model`` with the ``tiled`` settings (--roi ...): on the
+    forward-only plan where the module has one, through its forward otherwise."""
+    if M.supports_predict(model):
+        return model.predict_tiled(x, **tiled, **kw)
+    return Hh.predict_tiled(model, x, **tiled, **kw)
+
+
+def evaluate(model, dataset, K, device, tiled=None):
+    """``tiled``: None, or the keywords of predict_tiled (roi, overlap, window_batch,
+    mirror_axes): every variant is then evaluated on overlapping windows of ``roi`` whose
+    logits are blended on the device; the ranking metrics take the blended scores as logits."""
     rows = []
     model.eval()
     rank = not Hh.fast_simple_metrics()
@@ -97,7 +113,13 @@ def evaluate(model, dataset, K, device):
         for i in range(len(dataset)):
             x, y = dataset[i]
             x, y = x[None].to(device), y[None].to(device)
-            if fused:
+            if tiled is not None:
+                out = predict_tiled(model, x, tiled, labels=y, ignore_index=255,
+                                    return_scores=rank)
+                logits = out[2] if rank else None
+                dice, sens, spec, *_ = Hh.metrics_from_confusion(out[1].cpu().numpy(), K,
+                                                                 int(y.numel()))
+            elif fused:
                 _mask, conf = model.predict(x, labels=y, ignore_index=255)
                 dice, sens, spec, *_ = Hh.metrics_from_confusion(conf.cpu().numpy(), K,
                                                                  int(y.numel()))
@@ -134,7 +156,22 @@ def main(argv=None):
     ap.add_argument("--out", default="analysis")
     ap.add_argument("--overlays", type=int, default=0, metavar="N",
                     help="draw the overlay figure of the first N test volumes per checkpoint")
+    ap.add_argument("--roi", type=int, nargs=3, default=None, metavar=("D", "H", "W"),
+                    help="sliding-window inference: run the network on overlapping windows of "
+                         "this size and blend their logits with a Gaussian weight")
+    ap.add_argument("--overlap", type=float, default=0.5, help="window overlap in [0, 1) (--roi)")
+    ap.add_argument("--window-batch", type=int, default=1, help="windows per forward (--roi)")
+    ap.add_argument("--mirror", default="", metavar="AXES",
+                    help="test-time mirroring along these axes, e.g. 12 or 0,2 "
+                         "(0 = D, 1 = H, 2 = W; --roi)")
     args = ap.parse_args(argv)
+    tiled = None
+    if args.roi is not None:
+        tiled = {"roi": tuple(args.roi), "overlap": args.overlap,
+                 "window_batch": args.window_batch,
+                 "mirror_axes": tuple(sorted({int(c) for c in args.mirror if c.isdigit()}))}
+    elif args.mirror or args.window_batch != 1 or args.overlap != 0.5:
+        ap.error("--overlap, --window-batch and --mirror need --roi")
     S = Settings()
     device = torch.device("cuda", torch.cuda.current_device())
     out = pathlib.Path(args.out)
@@ -154,7 +191,7 @@ def main(argv=None):
             K = int(model.hparams.num_classes)
             ds = SyntheticSPCCT(n=S.n_test, in_ch=S.in_ch, depth=S.depth, height=S.height,
                                 width=S.width, num_classes=K, seed=seed + 20_000)
-            rows = evaluate(model, ds, K, device)
+            rows = evaluate(model, ds, K, device, tiled)
             if args.overlays > 0:
                 write_case_overlays(model, ds, args.overlays, out / "overlays",
                                     f"{name}_seed{seed}", device)
